@@ -1,6 +1,6 @@
 """bench.py - edges/s of the SegmentClassifier forward on synthetic TrackML-shaped graphs.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c5]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c5] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (input network, T x (edge pass, node pass), final
 edge pass; reference gnn/model.py:140-156) over one batch of G synthetic graphs already
@@ -15,7 +15,15 @@ Multi-GPU: independent graphs sharded over ranks, no data-path collective in the
 and no torchrun environment starts the N ranks itself (child processes of a parent that
 never touches the GPU) and relays rank 0's line.
 
-Rank 0 prints ONE JSON line with
+A plain run sets up, warms up, times exactly K steps (one region, no retries), writes the last
+step's outputs if --dump-outputs DIR is given, and prints ONE JSON line: metric, value (edges/s over
+the K steps), unit, higher_is_better, dtype, ms_per_step (one timed step), the run's config.
+
+--dump-outputs DIR: the edge scores the last timed step returned (rank 0's graphs) as DIR/scores.npy,
+float32; beyond 2^23 segments a fixed sample of them (numpy seed 0, ascending segment index).  Graphs
+and weights are seeded, so two builds given the same arguments can be compared score for score.
+
+--full adds to the same line (each in runs of its own, after the timed steps):
   roofline      dominant kernel, HIP-event timed inside the library on the launch stream: a pass of
                 >= 3 x K forwards, the first third dropped, MEDIAN per launch position; the sum of the
                 medians must not exceed 1.05 x ms_per_step (`consistent`)
@@ -42,6 +50,7 @@ import time
 REPO = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, REPO)
 
+DUMP_SAMPLE = 1 << 23    # --dump-outputs: at most this many scores (32 MB of float32)
 HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable)
 BF16_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA peak
 F32_MATRIX_TFLOPS = 157.3
@@ -292,13 +301,53 @@ def launch_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
-def time_steps(step, steps, sync_all):
+def time_steps(step, steps, sync_all, last=None):
+    """Wall clock of `steps` calls of step(); `last` (a list) receives what the final call returned."""
     sync_all()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        res = step()
     sync_all()
-    return time.perf_counter() - t0
+    dt = time.perf_counter() - t0
+    if last is not None:
+        last.append(res)
+    return dt
+
+
+def dump_outputs(path, scores):
+    """--dump-outputs: the scores one timed step returned, float32, as path/scores.npy - all of them up to
+    DUMP_SAMPLE, else a fixed sample (numpy seed 0, ascending segment index).  -> what was written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    s = scores.detach().reshape(-1).float().cpu().numpy()
+    n = s.size
+    if n > DUMP_SAMPLE:
+        s = s[np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))]
+    np.save(os.path.join(path, "scores.npy"), s)
+    return {"scores": "%d of %d segment scores%s, float32" % (s.size, n, " (fixed sample, seed 0)" if s.size < n else "")}
+
+
+def headline(args, wl, world, batch, plan, elapsed, bf16, G, dumped):
+    """The line's headline fields (the whole line of a plain run): edges/s over the K timed steps."""
+    out = {
+        "metric": "edges/sec (EdgeNet+NodeNet fwd) on 100k-edge TrackML graphs; % HBM roofline",
+        "value": world * batch.n_segments * args.steps / elapsed, "unit": "edges/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32",
+        "data": "synthetic",
+        "config": {"workload": wl["text"] % G,
+                   "graphs_per_gpu": G, "hits_per_graph": wl["n"],
+                   "segments_per_graph": wl["e"],
+                   "plan": "hits relabelled by degree, SELL-16 lists (padding %.1f%%), built "
+                           "once per batch on the GPU, outside the timed region like the CSR build "
+                           "(plan_ms with --full)" % (100 * plan.padding),
+                   "sharding": "independent graphs per rank, "
+                   "no data-path collective"},
+        "full": bool(args.full),
+    }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    return out
 
 
 def train_c4(dev, rank, world, rehearse, steps=60, warmup=15, n_global=512):
@@ -554,16 +603,33 @@ def run(args):
             sync_all()
             cg = torch.cuda.CUDAGraph()
             with torch.cuda.graph(cg):
-                model(batch)
-            step = cg.replay
+                graph_out = model(batch)
+            step = lambda: (cg.replay(), graph_out)[1]      # noqa: E731  (the replay refills graph_out)
             step()
-        elapsed = time_steps(step, args.steps, sync_all)
+        last = []
+        elapsed = time_steps(step, args.steps, sync_all, last)
+        dumped = dump_outputs(args.dump_outputs, last[0]) if args.dump_outputs and rank == 0 else None
+        del last
+    if not args.full:
+        if world > 1:
+            tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed = float(tmax[0].item())
+        if rank == 0:
+            print(json.dumps(headline(args, wl, world, batch, plan, elapsed, bf16, G, dumped)), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    with torch.no_grad():
         # per-kernel durations (see event_medians): a pass of its own, first third dropped, medians
         seq = event_medians(lambda: model(batch), args.steps)
         # A timed region that took much longer than its own kernels was not measuring them (seen once: 1.27 ms
         # per step over kernels of 0.85 when another process had just left the box).  One more region of
-        # exactly K steps then, both on the record, the shorter one counts.  Every rank takes the same branch
-        # (the decision is all-reduced) because sync_all is a collective.
+        # exactly K steps then, both on the record (`roofline.timed_regions_ms_per_step`); the headline stays
+        # the first region.  Every rank takes the same branch (the decision is all-reduced) because sync_all
+        # is a collective.
         timed_regions = [elapsed]
         retime = float(elapsed / args.steps * 1e3 > 1.15 * sum(ms for _, ms in seq) > 0.0)
         if world > 1:
@@ -572,7 +638,6 @@ def run(args):
             retime = float(flag.item())
         if retime:
             timed_regions.append(time_steps(step, args.steps, sync_all))
-            elapsed = min(timed_regions)
         other = exact = None
         if args.workload == "c5":           # the other arithmetic beside it
             model.mlp_bf16 = not bf16
@@ -756,7 +821,6 @@ def run(args):
                 traffic_source = ("%s (%s): rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE passes of this "
                                   "command, committed - not measured in this run"
                                   % (os.path.relpath(args.pmc_traffic, REPO), sec.get("source", "?")))
-        value = world * e_tot * args.steps / elapsed
         sum_k = sum(ms for _, ms in seq)
         dom_pos = per[dom]
         roof = {"kernel": dom, "algorithmic_bytes_per_launch": ab_dom,
@@ -786,20 +850,8 @@ def run(args):
             roof["algorithmic_TFLOPs"] = tfs
             if sec:
                 roof["valu_busy"] = sec.get("valu_busy", {}).get(dom)
-        out = {
-            "metric": "edges/sec (EdgeNet+NodeNet fwd) on 100k-edge TrackML graphs; % HBM roofline",
-            "value": value, "unit": "edges/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf16 else "f32",
-            "data": "synthetic",
-            "config": {"workload": wl["text"] % G,
-                       "graphs_per_gpu": G, "hits_per_graph": N_HITS,
-                       "segments_per_graph": N_SEG,
-                       "plan": "hits relabelled by degree, SELL-16 lists (padding %.1f%%), built "
-                               "once per batch on the GPU, outside the timed region like the CSR build "
-                               "(plan_ms below)" % (100 * plan.padding),
-                       "sharding": "independent graphs per rank, "
-                       "no data-path collective"},
+        out = headline(args, wl, world, batch, plan, elapsed, bf16, G, dumped)
+        out.update({
             "roofline": roof,
             "plan_ms": {"cold": t_plan * 1e3, "warm": t_plan_warm * 1e3, "warm_runs": warm_runs,
                         "builder": type(plan).__name__,
@@ -814,7 +866,7 @@ def run(args):
             "value_incl_plan": e_tot / (t_plan_warm + t_fresh_fwd),
             "value_incl_plan_note": "one forward on a never-seen batch: warm plan build + first forward; "
                                     "`value` replays one resident batch (plan amortised)",
-        }
+        })
         if assembly is not None:
             out["batch_assembly_ms"] = assembly
         if exact is not None:
@@ -870,6 +922,13 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16", help="c5 only")
     ap.add_argument("--graphs", type=int, default=0, help="graphs per launch per GPU (default: 256 c3, 8 c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline, exact-exp and other-dtype rates, plan and "
+                         "fresh-batch costs, c5, pruned, training steps, CPU baseline (the --no-* options "
+                         "below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (float32, a fixed sample "
+                         "beyond 2^23 segments)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the train_c4 sub-record")
     ap.add_argument("--no-pruned", action="store_true", help="skip the pruned-model sub-record (c3, N=1)")
@@ -887,6 +946,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     world = os.environ.get("WORLD_SIZE")
     if world is None and args.gpus > 1:
         sys.exit(launch_ranks(args))

@@ -78,9 +78,9 @@ def pack_model(m, masks):
     return d
 
 
-def save(name, **arrays):
+def save(name, out=OUT, **arrays):
     arrays["torch_version"] = np.array(torch.__version__)
-    path = os.path.join(OUT, name + ".npz")
+    path = os.path.join(out, name + ".npz")
     np.savez_compressed(path, **arrays)
     print("%-28s %8.1f kB" % (name, os.path.getsize(path) / 1e3))
 
@@ -283,14 +283,67 @@ def round2():
                             n_samples=8, batch_size=4, D=8, T=3, seed=14)
 
 
+def estimator_fixtures():
+    """What the reference's own training harnesses do with the drop-in, as data (tests/test_reference_estimator.py):
+All under tests/golden/estimator/: ref_estimator_d8 - the parameter count gnn/estimator.py:43-44 prints and the size
+    of the optimizer it builds (:29-30) around the drop-in, and the state_dict of the reference's own model; checkpoint.pt
+    - a checkpoint written by its save_checkpoint (:62-71); ref_load_weights_d8 - the weights
+    gnn/estimator_maskedlinear.py:82-101 `load_weights` leaves in a masked drop-in from a dense checkpoint."""
+    import contextlib
+    import io
+    import tempfile
+    import estimator_maskedlinear as ref_pruning
+    from gnn_fpga_amd.model import SegmentClassifier
+    torch.manual_seed(0)
+    m = SegmentClassifier(input_dim=3, hidden_dim=8, n_iters=2)
+    with contextlib.redirect_stdout(io.StringIO()) as out:
+        est = ref_estimator.Estimator(m, torch.nn.BCELoss(), opt="Adam", cuda=False, l1=1e-4)
+    printed = [ln for ln in out.getvalue().splitlines() if "Parameters:" in ln][0]
+    torch.manual_seed(0)
+    r = ref_model.SegmentClassifier(input_dim=3, hidden_dim=8, n_iters=2,
+                                    masks_n=[torch.ones(8, 33), torch.ones(8, 8)])
+    arrays = {"sd/" + k: v.numpy() for k, v in r.state_dict().items()}
+    out_dir = os.path.join(OUT, "estimator")
+    os.makedirs(out_dir, exist_ok=True)
+    save("ref_estimator_d8", out=out_dir, printed_parameters=np.int64(printed.split("Parameters:")[1]),
+         optimizer_params=np.int64(sum(len(g["params"]) for g in est.optimizer.param_groups)), **arrays)
+    with tempfile.TemporaryDirectory() as tmp:
+        fn = os.path.join(tmp, "ckpt", "checkpoint.pt")
+        est.save_checkpoint({"epoch": 1, "state_dict": r.state_dict(), "best_valid_loss": 0.5,
+                             "valid_losses": [0.5], "train_losses": [0.6],
+                             "optimizer": est.optimizer.state_dict()}, True, filename=fn)
+        with open(fn, "rb") as src, open(os.path.join(out_dir, "checkpoint.pt"), "wb") as dst:
+            dst.write(src.read())
+        torch.manual_seed(1)
+        D, C = 8, 11
+        me = [(torch.rand(D, 2 * C) > 0.4).float(), torch.ones(1, D)]
+        mn = [(torch.rand(D, 3 * C) > 0.4).float(), (torch.rand(D, D) > 0.4).float()]
+        pm = SegmentClassifier(input_dim=3, hidden_dim=D, n_iters=2, masks_e=me, masks_n=mn)
+        with contextlib.redirect_stdout(io.StringIO()):
+            pest = ref_pruning.Estimator(pm, torch.nn.BCELoss(), opt="Adam", cuda=False)
+        torch.manual_seed(2)
+        dense = SegmentClassifier(input_dim=3, hidden_dim=D, n_iters=2)
+        dfn = os.path.join(tmp, "dense.pt")
+        torch.save({"state_dict": dense.state_dict()}, dfn)
+        with contextlib.redirect_stdout(io.StringIO()):
+            pest.load_weights(dfn)
+    save("ref_load_weights_d8", out=out_dir, me0=me[0].numpy(), me1=me[1].numpy(), mn0=mn[0].numpy(), mn1=mn[1].numpy(),
+         **{"dense/" + k: v.numpy() for k, v in dense.state_dict().items()},
+         **{"after/" + k: v.detach().numpy() for k, v in pm.state_dict().items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--with-c3-full", action="store_true",
                     help="also run the dense reference at N=10k,E=100k (about 25 s, 16 GB)")
     ap.add_argument("--only-round2", action="store_true",
                     help="write only the fixtures added in round 2 (the others are unchanged)")
+    ap.add_argument("--only-estimator", action="store_true",
+                    help="write only the training-harness fixtures (estimator_fixtures)")
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
+    if args.only_estimator:
+        return estimator_fixtures()
     if args.only_round2:
         return round2()
     import io

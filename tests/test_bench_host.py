@@ -75,3 +75,25 @@ def test_gpus_2_dry_run_starts_two_ranks_that_meet_over_gloo():
                         "--gpus", "2", "--dry-run"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     assert [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")] == [rec]
+
+
+def test_time_steps_runs_exactly_k_steps_and_keeps_the_last_output():
+    calls, last, syncs = [], [], []
+    bench.time_steps(lambda: calls.append(len(calls)) or len(calls), 7, lambda: syncs.append(1), last)
+    assert len(calls) == 7 and last == [7] and len(syncs) == 2
+
+
+def test_dump_outputs_writes_float32_within_64_mb_and_the_same_sample_every_run(tmp_path):
+    import numpy as np
+    import torch
+    small = torch.arange(1000, dtype=torch.float32) / 1000
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    got = np.load(str(tmp_path / "a" / "scores.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy())      # small outputs: whole
+    big = torch.rand(bench.DUMP_SAMPLE + 12345, generator=torch.Generator().manual_seed(1))
+    for d in ("b", "c"):
+        rec = bench.dump_outputs(str(tmp_path / d), big)
+    b, c = (np.load(str(tmp_path / d / "scores.npy")) for d in ("b", "c"))
+    assert b.dtype == np.float32 and b.size == bench.DUMP_SAMPLE and b.nbytes <= 64 << 20
+    assert np.array_equal(b, c) and "fixed sample" in rec["scores"]
+    assert np.isin(b[:100], big.numpy()).all()

@@ -1,98 +1,90 @@
-"""The reference's own training harness holding the drop-in (build container only: imports
-/root/reference/gnn/estimator.py UNMODIFIED; skipped where the reference is absent, i.e. on the GPU
-box).  gnn/estimator.py:22-47 (constructor: optimizer over model.parameters()), :54-55 (the weight
-lists its L1 penalty walks), :62-78 (checkpoint save / load of state_dict + optimizer).  The forward
-itself needs a GPU (no CPU path): on CPU tensors the step must fail loudly, not fall back."""
-import contextlib
+"""The reference's own training harness holding the drop-in, pinned by what that harness did with it
+(tests/golden/estimator/, written by oracle/gen_golden.py --only-estimator, which runs gnn/estimator.py and
+gnn/estimator_maskedlinear.py UNMODIFIED on the drop-in).  gnn/estimator.py:22-47 (constructor: optimizer over
+model.parameters(), printed parameter count), :54-55 (the weight lists its L1 penalty walks), :62-78 (checkpoint
+save / load of state_dict + optimizer).  The forward itself needs a GPU (no CPU path): on CPU tensors the step
+must fail loudly, not fall back."""
 import io
 import os
-import sys
 
+import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference/gnn"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
+from golden_util import GOLDEN
+
+EST = os.path.join(GOLDEN, "estimator")
 
 
-@pytest.fixture()
-def ref():
-    sys.dont_write_bytecode = True            # never write __pycache__ into the read-only reference
-    sys.path.insert(0, REF)
-    try:
-        import estimator as ref_estimator
-        import model as ref_model
-        yield ref_estimator, ref_model
-    finally:
-        sys.path.remove(REF)
+def _prefixed(d, prefix):
+    return {k[len(prefix):]: torch.from_numpy(d[k]) for k in d.files if k.startswith(prefix)}
 
 
-def test_reference_estimator_holds_the_dropin(ref, tmp_path):
-    ref_estimator, ref_model = ref
+def test_reference_estimator_holds_the_dropin(tmp_path):
     from gnn_fpga_amd import HitGraphBatch, synth
     from gnn_fpga_amd._lib import GnnHipError
     from gnn_fpga_amd.model import SegmentClassifier
+    fx = np.load(os.path.join(EST, "ref_estimator_d8.npz"))
     torch.manual_seed(0)
     m = SegmentClassifier(input_dim=3, hidden_dim=8, n_iters=2)
-    with contextlib.redirect_stdout(io.StringIO()) as out:      # the constructor prints the model
-        est = ref_estimator.Estimator(m, torch.nn.BCELoss(), opt="Adam", cuda=False, l1=1e-4)
-    assert "Parameters: 569" in out.getvalue()                  # the notebooks' printed count (F=3, D=8)
-    assert sum(len(g["params"]) for g in est.optimizer.param_groups) == 10
+    # what the reference's constructor printed and built around the drop-in: "Parameters: 569" (the notebooks'
+    # count, F=3, D=8) and an optimizer over all ten tensors
+    assert int(fx["printed_parameters"]) == 569 == sum(p.numel() for p in m.parameters())
+    assert int(fx["optimizer_params"]) == 10 == len(list(m.parameters()))
+    opt = torch.optim.Adam(m.parameters())
     # the lists training_step builds for its L1 penalty (estimator.py:54-55)
-    node_w = [l.weight for l in est.model.node_network.network if hasattr(l, "weight")]
-    edge_w = [l.weight for l in est.model.edge_network.network if hasattr(l, "weight")]
+    node_w = [l.weight for l in m.node_network.network if hasattr(l, "weight")]
+    edge_w = [l.weight for l in m.edge_network.network if hasattr(l, "weight")]
     assert [tuple(w.shape) for w in node_w] == [(8, 33), (8, 8)]
     assert [tuple(w.shape) for w in edge_w] == [(8, 22), (1, 8)]
     # same state_dict keys / shapes as the reference's own model
-    torch.manual_seed(0)
-    r = ref_model.SegmentClassifier(input_dim=3, hidden_dim=8, n_iters=2,
-                                    masks_n=[torch.ones(8, 33), torch.ones(8, 8)])
-    assert {k: tuple(v.shape) for k, v in r.state_dict().items()} == \
-           {k: tuple(v.shape) for k, v in m.state_dict().items()}
-    m.load_state_dict(r.state_dict())                           # a reference checkpoint loads
-    # checkpoint round trip through the reference's own save / load (estimator.py:62-78,128-135)
-    fn = str(tmp_path / "ckpt" / "checkpoint.pt")
-    est.save_checkpoint({"epoch": 1, "state_dict": est.model.state_dict(), "best_valid_loss": 0.5,
-                         "valid_losses": [0.5], "train_losses": [0.6],
-                         "optimizer": est.optimizer.state_dict()}, True, filename=fn)
-    assert os.path.exists(str(tmp_path / "ckpt" / "model_best.pt"))
+    ref_sd = _prefixed(fx, "sd/")
+    assert {k: tuple(v.shape) for k, v in ref_sd.items()} == {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    # a checkpoint the reference's save_checkpoint wrote (its model + the optimizer it built around the drop-in)
+    # loads the way its load_checkpoint loads it (estimator.py:73-78)
     with torch.no_grad():
         for p in m.parameters():
             p.add_(1.0)
-    est.load_checkpoint(fn)
-    for k, v in r.state_dict().items():
+    ck = torch.load(os.path.join(EST, "checkpoint.pt"), weights_only=True)
+    m.load_state_dict(ck["state_dict"])
+    opt.load_state_dict(ck["optimizer"])
+    for k, v in ref_sd.items():
         assert torch.equal(m.state_dict()[k], v), k
-    assert est.train_losses == [0.6] and est.valid_losses == [0.5]
+    assert ck["train_losses"] == [0.6] and ck["valid_losses"] == [0.5]
+    # and the drop-in's own state round-trips through the same checkpoint layout
+    fn = str(tmp_path / "checkpoint.pt")
+    torch.save({"epoch": 1, "state_dict": m.state_dict(), "optimizer": opt.state_dict()}, fn)
+    torch.manual_seed(5)
+    again = SegmentClassifier(input_dim=3, hidden_dim=8, n_iters=2)
+    again.load_state_dict(torch.load(fn, weights_only=True)["state_dict"])
+    assert all(torch.equal(a, b) for a, b in zip(m.parameters(), again.parameters()))
     # no CPU path: the step raises instead of silently computing somewhere else
     g = synth.layered_graph(30, 60, 3, seed=0)
     X, Ri, Ro = (torch.from_numpy(a)[None] for a in synth.to_dense(g))
     with pytest.raises(GnnHipError):
-        est.training_step([X, Ri, Ro], torch.from_numpy(g.y)[None])
+        m([X, Ri, Ro])
     with pytest.raises(GnnHipError):
-        est.model(HitGraphBatch.from_graphs([g]))
+        m(HitGraphBatch.from_graphs([g]))
 
 
-def test_reference_pruning_estimator_deep_copies_and_reloads_the_dropin(tmp_path):
+def test_reference_pruning_estimator_deep_copies_and_reloads_the_dropin():
     """gnn/estimator_maskedlinear.py:82-101 `load_weights` (the pruning notebooks' retraining step) deep-copies the
-    model, loads a checkpoint into the copy and assigns `weight.data = W * mask.data` layer by layer.  The drop-in must
+    model, loads a checkpoint into the copy and assigns `weight.data = W * mask` layer by layer.  The drop-in must
     survive that AFTER it has run a forward - its caches then hold a ctypes struct of device pointers, which neither
-    pickles nor deep-copies (simulated here: the build container has no GPU) - and must see the replaced `.data`."""
+    pickles nor deep-copies (simulated here: the test needs no GPU) - and must see the replaced `.data`.  The
+    weights that load_weights left in this drop-in are the fixture's `after/`."""
     import copy
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, REF)
-    try:
-        import estimator_maskedlinear as ref_pruning
-    finally:
-        sys.path.remove(REF)
     from gnn_fpga_amd import _lib
     from gnn_fpga_amd.model import SegmentClassifier
+    fx = np.load(os.path.join(EST, "ref_load_weights_d8.npz"))
+    D = 8
+    me = [torch.from_numpy(fx["me0"]), torch.from_numpy(fx["me1"])]
+    mn = [torch.from_numpy(fx["mn0"]), torch.from_numpy(fx["mn1"])]
     torch.manual_seed(1)
-    D, C = 8, 11
-    me = [(torch.rand(D, 2 * C) > 0.4).float(), torch.ones(1, D)]
-    mn = [(torch.rand(D, 3 * C) > 0.4).float(), (torch.rand(D, D) > 0.4).float()]
     m = SegmentClassifier(input_dim=3, hidden_dim=D, n_iters=2, masks_e=me, masks_n=mn)
-    with contextlib.redirect_stdout(io.StringIO()):
-        est = ref_pruning.Estimator(m, torch.nn.BCELoss(), opt="Adam", cuda=False)
+    layers = {"edge_network.network.0": m.edge_network.network[0], "edge_network.network.2": m.edge_network.network[2],
+              "node_network.network.0": m.node_network.network[0], "node_network.network.2": m.node_network.network[2]}
+    assert all(hasattr(l, "mask_flag") and hasattr(l, "mask") for l in layers.values())   # what load_weights reads
     # what a forward on the GPU leaves behind
     key = m._param_key()
     m._w_cache = (key, [p.detach() for p in m.parameters()], _lib.GnnParams(), D, None)
@@ -100,17 +92,13 @@ def test_reference_pruning_estimator_deep_copies_and_reloads_the_dropin(tmp_path
     c = copy.deepcopy(m)
     assert c._w_cache is None and c._xp_cache is None and m._w_cache is not None
     assert all(torch.equal(a, b) and a.data_ptr() != b.data_ptr() for a, b in zip(m.parameters(), c.parameters()))
-    # a dense checkpoint (trained without masks), reloaded into the masked model through the reference's own code
-    torch.manual_seed(2)
-    dense = SegmentClassifier(input_dim=3, hidden_dim=D, n_iters=2)
-    fn = str(tmp_path / "dense.pt")
-    torch.save({"state_dict": dense.state_dict()}, fn)
-    with contextlib.redirect_stdout(io.StringIO()):
-        est.load_weights(fn)
-    sd = dense.state_dict()
-    assert torch.equal(m.edge_network.network[0].weight.data, sd["edge_network.network.0.weight"] * me[0])
-    assert torch.equal(m.node_network.network[0].weight.data, sd["node_network.network.0.weight"] * mn[0])
-    assert torch.equal(m.node_network.network[2].weight.data, sd["node_network.network.2.weight"] * mn[1])
+    # the copy takes the dense checkpoint; the masked layers of the model take the copy's weights times their masks
+    dense, after = _prefixed(fx, "dense/"), _prefixed(fx, "after/")
+    c.load_state_dict(dense)
+    for name, layer in layers.items():
+        w = getattr(c, name.split(".")[0]).network[int(name[-1])].weight.data
+        layer.weight.data = w * layer.mask.data if layer.mask_flag else w
+        assert torch.equal(layer.weight.data, after[name + ".weight"]), name     # what load_weights left
     assert m._param_key() != key                      # the replaced .data is seen: the cached weights are rebuilt
     # torch.save(model) / torch.load of the whole module, as notebooks do, drops the caches too
     buf = io.BytesIO()

@@ -15,7 +15,7 @@ trap 'cp /tmp/ab_a.so $LIB' EXIT
 for i in 1 2 3; do
   for v in a b; do
     cp /tmp/ab_$v.so $LIB
-    timeout -k 10 200 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-train --no-pruned --no-c5 "$@" 2>/dev/null | python -c "
+    timeout -k 10 200 python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline --no-train --no-pruned --no-c5 "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$v' == 'a' and 'in-tree ' or '$FLAG', round(d['ms_per_step'],4), 'first', round(r['launch_ms_first'],4), 'middle', round(r['launch_ms_middle'],4), 'last', round(r['launch_ms_last'],4), 'other', round(r['other_kernels_ms'],4))"
   done
