@@ -8,12 +8,13 @@ import ctypes
 import functools
 import os
 
+import numpy as np
 import torch  # imported first: its bundled libamdhip64.so.7 is the one HIP runtime of the process
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgnn_hip.so")
 
-GNN_ABI_VERSION = 5
+GNN_ABI_VERSION = 6
 GNN_ERR_UNSUPPORTED = -10001
 GNN_ERR_BADARG = -10002
 GNN_ERR_WORKSPACE = -10003
@@ -61,6 +62,11 @@ class GnnPlanOut(ctypes.Structure):
     _fields_ = [(n, _f) for n in ("X", "x_absmax", "src", "dst", "sd16", "in_off", "in_nbr", "out_off",
                                   "out_nbr", "in_off16", "in_nbr16", "out_off16", "out_nbr16", "tiles",
                                   "chunks", "sched_a", "sched_b", "perm", "src_abs", "dst_abs", "level")]
+
+
+class GnnGraphBuildSizes(ctypes.Structure):
+    _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "n_rows", "n_tasks", "max_graph_hits",
+                                    "max_graph_segments", "status")]
 
 
 # name -> (restype, argtypes); must list every function include/gnn_hip.h declares
@@ -115,6 +121,12 @@ SIGNATURES = {
                                                    _f, _sz, _f, _f]),
     "gnn_plan_build_fill": (ctypes.c_int, [_f, _i32, _f, _f, _i64, _i64, _i32, ctypes.POINTER(GnnPlanSizes),
                                            _f, _sz, ctypes.POINTER(GnnPlanOut), _f]),
+    "gnn_graph_build_workspace_bytes": (_sz, [_i64, _i64, _f, _i32, _i32, _i32]),
+    "gnn_graph_build_sizes": (ctypes.c_int, [_f, _f, _f, _f, _i64, _f, _i64, _f, _i32, _i32, _i32, ctypes.c_float,
+                                             ctypes.c_float, ctypes.c_float, _f, _sz, _f, _f, _f, _f]),
+    "gnn_graph_build_fill": (ctypes.c_int, [_f, _i64, _i64, _f, _i32, _i32, _i32, ctypes.c_float, ctypes.c_float,
+                                            ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                            ctypes.POINTER(GnnGraphBuildSizes), _f, _sz, _f, _f, _f, _f, _f, _f]),
     "gnn_profile_begin": (ctypes.c_int, [_i32]),
     "gnn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p),
                                        ctypes.POINTER(ctypes.c_float), _i32]),
@@ -743,6 +755,52 @@ def plan_build_sizes(src, dst, hit_ptr, n_hits, n_segments, n_graphs, tile_hits,
     out = GnnPlanSizes()
     ctypes.memmove(ctypes.byref(out), host.data_ptr(), ctypes.sizeof(GnnPlanSizes))
     return out
+
+
+def graph_build_sizes(r, phi, z, layer, event_ptr, pairs, n_layers, n_phi_sectors, cuts):
+    """Stage 1 of the graph builder (csrc/graph_build.hip): (workspace, GnnGraphBuildSizes, hit_ptr, seg_ptr) - the
+    sizes struct and both offset arrays come back in ONE read-back.  pairs: host int32 [P, 2]; cuts: (phi_slope_max,
+    phi_slope_outer_max, z0_max)."""
+    dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    pp = pairs.ctypes.data if pairs.size else None
+    G = E * n_phi_sectors
+    need = int(load().gnn_graph_build_workspace_bytes(n, E, pp, pairs.shape[0], n_layers, n_phi_sectors))
+    if need == 0:
+        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    nw = ctypes.sizeof(GnnGraphBuildSizes) // 8
+    out = torch.empty(nw + 2 * (G + 1), dtype=torch.int64, device=dev)
+    with _on(r) as st:
+        _check(load().gnn_graph_build_sizes(
+            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
+            _dev(layer, torch.int32, "layer"), n, _dev(event_ptr, torch.int64, "event_ptr"), E, pp, pairs.shape[0],
+            n_layers, n_phi_sectors, cuts[0], cuts[1], cuts[2], ws.data_ptr(), ws.numel(), out.data_ptr(),
+            out[nw:].data_ptr(), out[nw + G + 1:].data_ptr(), st))
+    host = out.cpu().numpy()
+    sizes = GnnGraphBuildSizes()
+    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnGraphBuildSizes))
+    return ws, sizes, host[nw:nw + G + 1].copy(), host[nw + G + 1:].copy()
+
+
+def graph_build_fill(ws, sizes, particle_id, event_ptr, pairs, n_layers, n_phi_sectors, cuts, feature_scale, n_hits):
+    """Stage 2: (X [N, 3], src, dst [E] int32, y [E] or None, hit_index [N] int64), N and E from `sizes`."""
+    dev = ws.device
+    N, E = int(sizes.n_hits), int(sizes.n_segments)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    X = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    src = torch.empty(E, dtype=torch.int32, device=dev)
+    dst = torch.empty(E, dtype=torch.int32, device=dev)
+    y = None if particle_id is None else torch.empty(E, dtype=torch.float32, device=dev)
+    hit_index = torch.empty(N, dtype=torch.int64, device=dev)
+    with _on(ws) as st:
+        _check(load().gnn_graph_build_fill(
+            None if particle_id is None else _dev(particle_id, torch.int64, "particle_id"), n_hits,
+            int(event_ptr.shape[0]) - 1, pairs.ctypes.data if pairs.size else None, pairs.shape[0], n_layers,
+            n_phi_sectors, cuts[0], cuts[1], cuts[2], feature_scale[0], feature_scale[1], feature_scale[2],
+            ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(), src.data_ptr(), dst.data_ptr(),
+            None if y is None else y.data_ptr(), hit_index.data_ptr(), st))
+    return X, src, dst, y, hit_index
 
 
 def plan_build_fill(X, src, dst, n_hits, n_segments, chunk_segments, sizes, workspace, arrays):

@@ -47,6 +47,12 @@ struct ProfChain {
 
 constexpr int kBlock = 256;   // 4 waves of 64
 
+// csr_build.hip's device-wide scan, shared: exclusive scans of n_arrays (1 or 2) int32 count arrays stored `stride`
+// apart into ptr_a / ptr_b [n + 1] (entry n = the total); `sums` = scan_sums_words(n) int32 of scratch
+int64_t scan_sums_words(int64_t n);
+int scan_counts(const int32_t *cnt, int64_t stride, int n_arrays, int32_t *ptr_a, int32_t *ptr_b, int64_t n,
+                int32_t *sums, hipStream_t s);
+
 // One-time per-DEVICE set-up (hipFuncSetAttribute opt-ins for > 64 KB of dynamic LDS, CU counts):
 // a process may drive several devices, and a function attribute set while device 0 was current
 // says nothing about device 1.  `static DevOnce once; if (once.need()) { ... }`.

@@ -348,6 +348,27 @@ CsrWs carve_csr(char *base, int64_t n_hits, int64_t n_segments)
 }
 
 }  // namespace
+
+// the scan kernels above for other units (graph_build.hip): exclusive scans of n_arrays (1 or 2) int32 count arrays
+// stored `stride` apart into ptr_a / ptr_b [n + 1] (entry n = the total), `sums` = scan_sums_words(n) ints of scratch
+int64_t scan_sums_words(int64_t n) { return 2 * ((n + kScanTile - 1) / kScanTile + 1); }
+
+int scan_counts(const int32_t *cnt, int64_t stride, int n_arrays, int32_t *ptr_a, int32_t *ptr_b, int64_t n,
+                int32_t *sums, hipStream_t s)
+{
+    if (n <= kOneBlockMax) {
+        GNN_LAUNCH("k_csr_scan", k_csr_scan_one, n_arrays, kScanOneThreads, s, cnt, ptr_a, ptr_b, n, stride);
+        return 0;
+    }
+    const int64_t n_blocks = (n + kScanTile - 1) / kScanTile;
+    const dim3 g((unsigned)n_blocks, (unsigned)n_arrays);
+    GNN_LAUNCH("k_csr_scan_sums", k_csr_scan_sums, g, kBlock, s, cnt, n, stride, sums, n_blocks);
+    GNN_LAUNCH("k_csr_scan", k_csr_scan_one, n_arrays, kScanOneThreads, s, sums, sums, sums + (n_blocks + 1), n_blocks,
+               n_blocks + 1);
+    GNN_LAUNCH("k_csr_scan_blocks", k_csr_scan_blocks, g, kBlock, s, cnt, n, stride, sums, n_blocks, ptr_a, ptr_b);
+    return 0;
+}
+
 }  // namespace gnn
 
 using namespace gnn;

@@ -113,3 +113,54 @@ def to_dense(graph, n_hits_pad=None, n_segments_pad=None, dtype=np.float32):
     Ri[graph.dst, j] = 1
     Ro[graph.src, j] = 1
     return X, Ri, Ro
+
+
+# Barrel radii (mm) of the ten layers the reference's TrackML selection keeps (gnn/prepareGraphs.py:56-58: volumes
+# 8, 13, 17), rounded.
+BARREL_RADII = (32.0, 72.0, 116.0, 172.0, 260.0, 360.0, 500.0, 660.0, 820.0, 1020.0)
+
+# Hit columns as the reference's graph construction consumes them (gnn/prepareGraphs.py:71-86): r, phi, z float32,
+# layer int32, particle_id int64; event_ptr int64 [n_events + 1]: event e owns rows [event_ptr[e], event_ptr[e+1]).
+HitColumns = namedtuple("HitColumns", ["r", "phi", "z", "layer", "particle_id", "event_ptr"])
+
+
+def barrel_event(n_tracks, n_noise, n_events=1, seed=0):
+    """Detector hits of `n_events` barrel events for graph_build.build_graphs.
+
+    Every track crosses the ten BARREL_RADII on a helix-like path: phi(r) = phi0 + k r with a small
+    curvature k, z(r) = z0 + r cot(theta) with z smeared by 0.5 mm, r smeared by 0.1 mm.  `n_noise` noise
+    hits per event sit on random layers at random (phi, z) with particle ids -1, -2, ... (every noise hit
+    its own id).  Each event's rows are shuffled (frame order is not layer order).
+    """
+    rng = np.random.default_rng(seed)
+    radii = np.asarray(BARREL_RADII)
+    n_layers = radii.shape[0]
+    cols = {k: [] for k in ("r", "phi", "z", "layer", "particle_id")}
+    event_ptr = np.zeros(n_events + 1, dtype=np.int64)
+    for e in range(n_events):
+        phi0 = rng.uniform(-np.pi, np.pi, size=(n_tracks, 1))
+        k = rng.uniform(-4e-4, 4e-4, size=(n_tracks, 1))
+        z0 = rng.normal(0.0, 40.0, size=(n_tracks, 1))
+        cot = rng.uniform(-1.0, 1.0, size=(n_tracks, 1))
+        r = radii[None, :] + rng.normal(0.0, 0.1, size=(n_tracks, n_layers))
+        phi = phi0 + k * r
+        z = z0 + r * cot + rng.normal(0.0, 0.5, size=(n_tracks, n_layers))
+        layer = np.broadcast_to(np.arange(n_layers), (n_tracks, n_layers))
+        pid = np.broadcast_to(np.arange(1, n_tracks + 1)[:, None] + e * 1_000_000, (n_tracks, n_layers))
+        nl = rng.integers(0, n_layers, size=n_noise)
+        r_n = radii[nl] + rng.normal(0.0, 0.1, size=n_noise)
+        phi_n = rng.uniform(-np.pi, np.pi, size=n_noise)
+        z_n = rng.uniform(-1000.0, 1000.0, size=n_noise)
+        R = np.concatenate([r.ravel(), r_n])
+        P = np.concatenate([phi.ravel(), phi_n])
+        P = np.mod(P + np.pi, 2 * np.pi) - np.pi                  # into [-pi, pi)
+        Z = np.concatenate([z.ravel(), z_n])
+        L = np.concatenate([layer.ravel(), nl])
+        I = np.concatenate([pid.ravel(), -np.arange(1, n_noise + 1)])
+        order = rng.permutation(R.shape[0])
+        for name, v in (("r", R), ("phi", P), ("z", Z), ("layer", L), ("particle_id", I)):
+            cols[name].append(v[order])
+        event_ptr[e + 1] = event_ptr[e] + R.shape[0]
+    return HitColumns(np.concatenate(cols["r"]).astype(np.float32), np.concatenate(cols["phi"]).astype(np.float32),
+                      np.concatenate(cols["z"]).astype(np.float32), np.concatenate(cols["layer"]).astype(np.int32),
+                      np.concatenate(cols["particle_id"]).astype(np.int64), event_ptr)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNN_ABI_VERSION 5
+#define GNN_ABI_VERSION 6
 
 #define GNN_ERR_UNSUPPORTED (-10001) /* (F, D) has no kernel instantiation            */
 #define GNN_ERR_BADARG      (-10002) /* null pointer, negative size, bad stride ...   */
@@ -357,6 +357,47 @@ size_t gnn_csr_build_workspace_bytes(int64_t n_hits, int64_t n_segments);
 int gnn_csr_build(const int32_t *src, const int32_t *dst, int64_t n_hits, int64_t n_segments, int32_t *in_ptr,
                   int32_t *in_eid, int32_t *in_nbr, int32_t *out_ptr, int32_t *out_eid, int32_t *out_nbr,
                   int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- segment graphs from detector hits, built on the GPU (csrc/graph_build.hip; ABI 6) ----------------------------
+ * Replaces the reference's per-event host graph construction: split_phi_sectors (gnn/prepareGraphs.py:87-106) and one
+ * construct_graph per sector (gnn/graph.py:37-142, with construct_segments / select_segments :43-93), as
+ * process_event calls them (gnn/prepareGraphs.py:136-170).  gnn-fpga_amd/graph_build.py is the numpy specification;
+ * the segments selected are the reference's, bit for bit, for float32 hit columns.  Two calls around ONE host
+ * read-back, as the plan builder's:
+ *   gnn_graph_build_sizes  sectors, (graph, layer) grouping in frame order, kept-pair counts -> *sizes_out, hit_ptr,
+ *                          seg_ptr (DEVICE memory, written asynchronously on `stream`)
+ *   gnn_graph_build_fill   X, src, dst, y, hit_index into arrays the caller allocated from a HOST copy of the sizes
+ *                          (the same workspace, not touched in between)
+ * Inputs (DEVICE): r, phi, z float32 [n_hits], layer int32 [n_hits], event_ptr int64 [n_events + 1] (event e owns
+ * rows [event_ptr[e], event_ptr[e+1])), particle_id int64 [n_hits] or NULL (then y is not written).  layer_pairs
+ * is a HOST array [n_pairs][2] of (l1, l2) in [0, n_layers), at most 128 pairs.  Graph g = event * n_phi_sectors +
+ * sector: its hits in frame order, rows hit_ptr[g] .. hit_ptr[g+1] of X [n_hits_out, 3] (r, centred phi, z, each
+ * float32(float64(v) / scale)) and of hit_index (input row, int64); its segments seg_ptr[g] .. seg_ptr[g+1] of src
+ * (start hit), dst (end hit) int32 in batch numbering and y = (particle_id[start] == particle_id[end]), ordered
+ * pair by pair, then by start hit, then by end hit in frame order.  A pair is kept when |phi_slope| <
+ * (l1 < 5 ? phi_slope_max : phi_slope_outer_max) and |z0| < z0_max (float32 thresholds).  sizes.status (0 = fine):
+ * bit 1 a layer outside [0, n_layers), bit 2 more than 2^31 - 1 segments, bit 4 event_ptr not non-decreasing from 0
+ * to n_hits; gnn_graph_build_fill refuses flagged sizes.  GNN_ERR_BADARG: null or negative arguments, a layer_pairs
+ * entry out of range, n_phi_sectors < 1; GNN_ERR_UNSUPPORTED: > 128 pairs or sizes beyond int32 indices.  The
+ * output is the same in every run (no order decided by atomics). */
+typedef struct gnn_graph_build_sizes {
+    int64_t n_graphs, n_hits, n_segments;       /* graphs = n_events * n_phi_sectors; hits kept (in a sector)      */
+    int64_t n_rows, n_tasks;                    /* (start hit, pair) rows and workgroup tasks of the pair kernels   */
+    int64_t max_graph_hits, max_graph_segments, status;
+} gnn_graph_build_sizes_t;
+
+size_t gnn_graph_build_workspace_bytes(int64_t n_hits, int64_t n_events, const int32_t *layer_pairs, int32_t n_pairs,
+                                       int32_t n_layers, int32_t n_phi_sectors);
+int gnn_graph_build_sizes(const float *r, const float *phi, const float *z, const int32_t *layer, int64_t n_hits,
+                          const int64_t *event_ptr, int64_t n_events, const int32_t *layer_pairs, int32_t n_pairs,
+                          int32_t n_layers, int32_t n_phi_sectors, float phi_slope_max, float phi_slope_outer_max,
+                          float z0_max, void *workspace, size_t workspace_bytes, gnn_graph_build_sizes_t *sizes_out,
+                          int64_t *hit_ptr, int64_t *seg_ptr, void *stream);
+int gnn_graph_build_fill(const int64_t *particle_id, int64_t n_hits, int64_t n_events, const int32_t *layer_pairs,
+                         int32_t n_pairs, int32_t n_layers, int32_t n_phi_sectors, float phi_slope_max,
+                         float phi_slope_outer_max, float z0_max, double scale_r, double scale_phi, double scale_z,
+                         const gnn_graph_build_sizes_t *sizes, void *workspace, size_t workspace_bytes, float *X,
+                         int32_t *src, int32_t *dst, float *y, int64_t *hit_index, void *stream);
 
 /* bound_out (device, 1 float) = the left side of the GNN_FLAG_EXP_PRODUCT condition;
  * x_absmax (device, [F]) = per-feature max |X|.  Asynchronous on `stream`. */
