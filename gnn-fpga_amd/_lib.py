@@ -14,7 +14,7 @@ import torch  # imported first: its bundled libamdhip64.so.7 is the one HIP runt
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgnn_hip.so")
 
-GNN_ABI_VERSION = 6
+GNN_ABI_VERSION = 7
 GNN_ERR_UNSUPPORTED = -10001
 GNN_ERR_BADARG = -10002
 GNN_ERR_WORKSPACE = -10003
@@ -127,6 +127,10 @@ SIGNATURES = {
     "gnn_graph_build_fill": (ctypes.c_int, [_f, _i64, _i64, _f, _i32, _i32, _i32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.POINTER(GnnGraphBuildSizes), _f, _sz, _f, _f, _f, _f, _f, _f]),
+    "gnn_metrics_bins": (_i64, [_i32]),
+    "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
+                                                  _f]),
     "gnn_profile_begin": (ctypes.c_int, [_i32]),
     "gnn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p),
                                        ctypes.POINTER(ctypes.c_float), _i32]),
@@ -816,6 +820,30 @@ def plan_build_fill(X, src, dst, n_hits, n_segments, chunk_segments, sizes, work
             _dev(X, torch.float32, "X"), X.shape[1], _dev(src, torch.int32, "src"),
             _dev(dst, torch.int32, "dst"), n_hits, n_segments, chunk_segments, ctypes.byref(sizes),
             workspace.data_ptr(), workspace.numel(), ctypes.byref(out), st))
+
+
+def metrics_bins(key_shift):
+    """Histogram bins per class at this key shift (csrc/metrics.hip); 0 for a shift outside [10, 23]."""
+    return int(load().gnn_metrics_bins(key_shift))
+
+
+def segment_metrics_update(e, y, src, thresholds, key_shift, counts, hist, status, seg_ptr=None, per_graph=None):
+    """One pass of gnn_segment_metrics_update: ADDS into counts [T + 1, 2] and hist [2, n_bins] (int64 views of the
+    caller's counters), ORs status [1] int32, WRITES per_graph [G, T + 1, 2] when seg_ptr [G + 1] int64 is given.
+    thresholds: host sequence of floats.  Asynchronous: nothing is read back."""
+    n = int(e.numel())
+    th = np.ascontiguousarray(thresholds, dtype=np.float32)
+    G = 0 if seg_ptr is None else int(seg_ptr.numel()) - 1
+    need = int(load().gnn_metrics_workspace_bytes(n, th.size, key_shift, G))
+    with _on(e) as st:
+        ws = torch.empty(need, dtype=torch.uint8, device=e.device) if need else None
+        _check(load().gnn_segment_metrics_update(
+            _dev(e, torch.float32, "scores"), _dev(y, torch.float32, "targets"),
+            None if src is None else _dev(src, torch.int32, "src"), n, th.ctypes.data if th.size else None, th.size,
+            key_shift, _dev(counts, torch.int64, "counts"), _dev(hist, torch.int64, "hist"),
+            None if seg_ptr is None else _dev(seg_ptr, torch.int64, "seg_ptr"), G,
+            None if per_graph is None else _dev(per_graph, torch.int64, "per_graph"),
+            _dev(status, torch.int32, "status"), None if ws is None else ws.data_ptr(), need, st))
 
 
 class profile:

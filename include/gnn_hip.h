@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define GNN_ABI_VERSION 6
+#define GNN_ABI_VERSION 7
 
 #define GNN_ERR_UNSUPPORTED (-10001) /* (F, D) has no kernel instantiation            */
 #define GNN_ERR_BADARG      (-10002) /* null pointer, negative size, bad stride ...   */
@@ -398,6 +398,30 @@ int gnn_graph_build_fill(const int64_t *particle_id, int64_t n_hits, int64_t n_e
                          float phi_slope_outer_max, float z0_max, double scale_r, double scale_phi, double scale_z,
                          const gnn_graph_build_sizes_t *sizes, void *workspace, size_t workspace_bytes, float *X,
                          int32_t *src, int32_t *dst, float *y, int64_t *hit_index, void *stream);
+
+/* ---- scoring a classifier: confusion counts, score histograms (csrc/metrics.hip; ABI 7) ----------------------------
+ * Stands in for the evaluation cells of the reference's notebooks (gnn/MPNN_Seg_ACTS*.ipynb, makeROC and the
+ * per-sample cells), which flatten Estimator.predict's scores (gnn/estimator.py:137-146) and call sklearn.metrics
+ * accuracy_score / precision_score / recall_score on `pred > thresh` and roc_curve on the scores, on the host.
+ * gnn-fpga_amd/metrics.py (segment_metrics_numpy) is the specification of every counter.
+ *   gnn_metrics_bins(key_shift): histogram bins per class, (0x3F800000 >> key_shift) + 1, for key_shift in [10, 23]
+ *     (8192 .. 1 bins per octave); 0 otherwise.  A score's bin is its float32 bit pattern (sign cleared) >> key_shift.
+ *   gnn_metrics_workspace_bytes: device scratch the update needs (0 in this version; pass what it returns).
+ *   gnn_segment_metrics_update: ONE pass over e [n] scores, y [n] labels (float32) and, unless NULL, src [n] int32
+ *     (src < 0 = padded segment, skipped).  Class c = 0 for y == 0, 1 for y == 1.  ADDS (int64, device, caller-owned,
+ *     so calls stream over batches) into counts [T + 1][2] (row 0: segments per class, row 1 + k: segments with
+ *     e > thresholds[k]) and hist [2][gnn_metrics_bins(key_shift)].  thresholds: HOST array of T <= 16 floats.
+ *     With seg_ptr [n_graphs + 1] (device int64; graph g = segments [seg_ptr[g], seg_ptr[g+1]), non-decreasing),
+ *     per_graph [n_graphs][T + 1][2] is WRITTEN with the same counts graph by graph; both NULL or both given.
+ *     status [1] (device int32) is ORed with: 1 a score NaN, inf or outside [0, 1]; 2 a label not exactly 0 or 1;
+ *     4 a threshold not finite (such segments are counted nowhere; the caller reads the word and raises).
+ *     Integer atomics only: the counters are the same in every run.  Asynchronous on `stream`, no read-back. */
+int64_t gnn_metrics_bins(int32_t key_shift);
+size_t gnn_metrics_workspace_bytes(int64_t n, int32_t n_thresholds, int32_t key_shift, int64_t n_graphs);
+int gnn_segment_metrics_update(const float *e, const float *y, const int32_t *src, int64_t n, const float *thresholds,
+                               int32_t n_thresholds, int32_t key_shift, int64_t *counts, int64_t *hist,
+                               const int64_t *seg_ptr, int64_t n_graphs, int64_t *per_graph, int32_t *status,
+                               void *workspace, size_t workspace_bytes, void *stream);
 
 /* bound_out (device, 1 float) = the left side of the GNN_FLAG_EXP_PRODUCT condition;
  * x_absmax (device, [F]) = per-feature max |X|.  Asynchronous on `stream`. */
