@@ -98,6 +98,12 @@ SIGNATURES = {
     "gnn_backward_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "gnn_segclf_backward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams),
                                            _i32, _f, _f, _f, _f, ctypes.POINTER(GnnGrads), _f, _sz, _f]),
+    "gnn_nodeclf_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _i32, _f, _f,
+                                           _f, _sz, _f]),
+    "gnn_nodeclf_forward_train": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _i32, _f,
+                                                 _f, _f, _f, _f, _sz, _f]),
+    "gnn_nodeclf_backward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _i32, _f, _f,
+                                            _f, _f, _f, ctypes.POINTER(GnnGrads), _f, _f, _f, _sz, _f]),
     "gnn_bce_loss": (ctypes.c_int, [_f, _f, _i64, ctypes.c_float, _f, _f, _f, _f]),
     "gnn_dense_to_index": (ctypes.c_int, [_f, _f, _i64, _i64, _i64, _f, _f, _f, _f]),
     "gnn_edge_bwd": (ctypes.c_int, [_f, _i32, ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _f,
@@ -497,6 +503,78 @@ def segclf_backward(batch, weights, F, D, n_iters, e_all, H_all, grad_out, into=
                                           _dev(grad_out, torch.float32, "grad_out"),
                                           ctypes.byref(gs), ws.data_ptr(), ws.numel(), st))
     return grads
+
+
+def _head_check(Wo, bo, F, D):
+    if Wo.numel() != F + D or bo.numel() != 1:
+        raise GnnHipError("the output network needs Wo [1, %d] and bo [1], got %s and %s"
+                          % (F + D, tuple(Wo.shape), tuple(bo.shape)))
+
+
+def nodeclf_forward(batch, weights, Wo, bo, F, D, n_iters, workspace=None, trace=False):
+    """NodeClassifier forward (gnn_nodeclf_forward): hit scores y [n_hits] (and, with trace=True,
+    H_trace [(T+1), N, C]).  `weights`: the trunk's ten effective tensors; Wo [1, C], bo [1]."""
+    dev = batch.X.device
+    N, E = batch.n_hits, batch.n_segments
+    if not shape_supported(F, D):
+        raise GnnHipError("no HIP kernel for input_dim=%d hidden_dim=%d" % (F, D))
+    _head_check(Wo, bo, F, D)
+    need = workspace_bytes(N, E, F, D)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    y = torch.empty(N, dtype=torch.float32, device=dev)
+    Ht = torch.empty((n_iters + 1, N, F + D), dtype=torch.float32, device=dev) if trace else None
+    g = graph_struct(batch)
+    p = params_struct(weights, F, D)
+    with _on(batch.X, g, p) as st:
+        _check(load().gnn_nodeclf_forward(ctypes.byref(g), ctypes.byref(p), _dev(Wo, torch.float32, "Wo"),
+                                          _dev(bo, torch.float32, "bo"), n_iters, y.data_ptr(),
+                                          Ht.data_ptr() if trace else None, workspace.data_ptr(), workspace.numel(),
+                                          st))
+    return (y, Ht) if trace else y
+
+
+def nodeclf_forward_train(batch, weights, Wo, bo, F, D, n_iters, keep_q=True):
+    """NodeClassifier training forward: (e_all [T, E], H_all [(T+1), N, ldh], Q_all [T, N, D] or None, y [N])."""
+    dev = batch.X.device
+    E, N = batch.n_segments, batch.n_hits
+    _head_check(Wo, bo, F, D)
+    ldh = h_stride(F, D)
+    e_all = torch.empty((n_iters, E), dtype=torch.float32, device=dev)
+    H_all = torch.empty((n_iters + 1, N, ldh), dtype=torch.float32, device=dev)
+    Q_all = torch.empty((n_iters, N, D), dtype=torch.float32, device=dev) if keep_q else None
+    y = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(workspace_bytes(N, E, F, D), dtype=torch.uint8, device=dev)
+    g = cached_graph_struct(batch)
+    p = params_struct(weights, F, D)
+    with _on(batch.X, g, p) as st:
+        _check(load().gnn_nodeclf_forward_train(ctypes.byref(g), ctypes.byref(p), _dev(Wo, torch.float32, "Wo"),
+                                                _dev(bo, torch.float32, "bo"), n_iters, e_all.data_ptr(),
+                                                H_all.data_ptr(), Q_all.data_ptr() if keep_q else None,
+                                                y.data_ptr(), ws.data_ptr(), ws.numel(), st))
+    return e_all, H_all, Q_all, y
+
+
+def nodeclf_backward(batch, weights, Wo, bo, F, D, n_iters, e_all, H_all, y, grad_y, Q_all=None):
+    """Gradients of the trunk's ten tensors (state_dict order) and of Wo, bo: (grads, gWo, gbo).
+    `Q_all` None: the backward walks the node passes a second time instead of reading the kept layers."""
+    dev = batch.X.device
+    _head_check(Wo, bo, F, D)
+    grads, gs = _grad_views(list(weights) + [Wo, bo], dev)
+    gWo, gbo = grads[10], grads[11]
+    need = int(load().gnn_backward_workspace_bytes(batch.n_hits, batch.n_segments, F, D))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    g = cached_graph_struct(batch)
+    p = params_struct(weights, F, D)
+    with _on(batch.X, g, p) as st:
+        _check(load().gnn_nodeclf_backward(ctypes.byref(g), ctypes.byref(p), _dev(Wo, torch.float32, "Wo"),
+                                           _dev(bo, torch.float32, "bo"), n_iters, _dev(e_all, torch.float32, "e_all"),
+                                           _dev(H_all, torch.float32, "H_all"),
+                                           _dev(Q_all, torch.float32, "Q_all") if Q_all is not None else None,
+                                           _dev(y, torch.float32, "y"), _dev(grad_y, torch.float32, "grad_y"),
+                                           ctypes.byref(gs), gWo.data_ptr(), gbo.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), st))
+    return grads[:10], gWo, gbo
 
 
 def dense_to_index(Ri, Ro):

@@ -148,3 +148,39 @@ class _NodeFn(torch.autograd.Function):
         gH, ge, gw = _lib.node_bwd(Hp, ev, Hn, ctx.batch, _dummy_weights(ctx.F, ctx.D, Hp.device, node=w), ctx.F,
                                    ctx.D, g)
         return (None, None, None, gH[:, :ctx.C].contiguous(), ge) + tuple(gw)
+
+
+# ---- NodeClassifier (gnn/MPNN_HitClassifier.ipynb cell 21): the trunk's training forward with the output network in
+# place of the final edge pass, and the backward seeded from the hit scores' gradient ----------------------------
+class _NodeClf(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, batch, F, D, n_iters, *weights):
+        w = [t.detach().to(torch.float32).contiguous() for t in weights]
+        e_all, H_all, Q_all, y = _lib.nodeclf_forward_train(batch, w[:10], w[10], w[11], F, D, n_iters)
+        ctx.batch, ctx.F, ctx.D, ctx.n_iters = batch, F, D, n_iters
+        ctx.save_for_backward(e_all, H_all, Q_all, y, *w)
+        return y.clone()
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        e_all, H_all, Q_all, y, *w = ctx.saved_tensors
+        gy = grad_y.to(torch.float32).contiguous()
+        grads, gWo, gbo = _lib.nodeclf_backward(ctx.batch, w[:10], w[10], w[11], ctx.F, ctx.D, ctx.n_iters, e_all,
+                                                H_all, y, gy, Q_all=Q_all)
+        return (None, None, None, None) + tuple(grads) + (gWo, gbo)
+
+
+def nodeclf_apply(model, batch):
+    """Differentiable forward of `model` (a gnn_fpga_amd NodeClassifier) on `batch`: hit scores [n_hits]."""
+    F, D = model.input_dim, model.hidden_dim
+    if not batch.X.is_cuda:
+        raise _lib.GnnHipError("NodeClassifier.forward needs tensors on a ROCm device; there is no CPU path")
+    if not _lib.shape_supported(F, D):
+        raise _lib.GnnHipError("no HIP training kernels for input_dim=%d hidden_dim=%d" % (F, D))
+    lin, out = model.input_network[0], model.output_network[0]
+    en, nn_ = model.edge_network.network, model.node_network.network
+    weights = [lin.weight, lin.bias,
+               en[0].effective_weight(), en[0].bias, en[2].effective_weight(), en[2].bias,
+               nn_[0].effective_weight(), nn_[0].bias, nn_[2].effective_weight(), nn_[2].bias,
+               out.weight, out.bias]
+    return _NodeClf.apply(batch, F, D, model.n_iters, *weights)

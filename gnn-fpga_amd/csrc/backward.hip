@@ -1765,10 +1765,81 @@ BwdWs carve_bwd(char *b, int64_t N, int64_t E, int ldh, int C, int D)
     return w;
 }
 
+// ---- NodeClassifier's output network y = sigmoid(Wo [H'_T | X] + bo) (gnn/MPNN_HitClassifier.ipynb cell 21) ----
+// Per hit: dz = gy y (1 - y) (the chain autograd forms through the Sigmoid; the loss stays separate), the seed of
+// the trunk's backward gH_T = [dz Wo[:D] | 0], and the head's gradient terms dz [h | 1].  The workgroup adds its
+// 256 hits' terms in a fixed order (wave butterflies, then the four waves in order) and WRITES them to its own
+// row of `part` (rows of head_stride() floats); k_head_fold1 / 2 add the rows up in row order, as k_grad_fold1 / 2
+// do for the trunk: gWo, gbo are bit-reproducible.
+template <int F, int D>
+constexpr int head_stride() { return (F + D + 1 + 3) & ~3; }
+
+template <int F, int D>
+__global__ __launch_bounds__(kBlock) void k_head_bwd(const float *__restrict__ H, const float *__restrict__ y,
+                                                     const float *__restrict__ gy, const float *__restrict__ Wo,
+                                                     float *__restrict__ gH, float *__restrict__ part, int64_t n_hits)
+{
+    constexpr int C = F + D, LDH = Shape<F, D>::LDH, NP = C + 1, PS = head_stride<F, D>();
+    __shared__ float wsum[kBlock / 64][NP];
+    const int64_t n = xcd_block() * kBlock + threadIdx.x;
+    float v[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) v[k] = 0.0f;
+    if (n < n_hits) {
+        const float yn = y[n], dz = gy[n] * (1.0f - yn) * yn;
+        float h[LDH], g[LDH];
+        load_row4<LDH / 4>(H + n * LDH, h);
+#pragma unroll
+        for (int k = 0; k < LDH; ++k) g[k] = k < D ? dz * Wo[k] : 0.0f;
+        store_row4<LDH / 4>(gH + n * LDH, g);
+#pragma unroll
+        for (int k = 0; k < C; ++k) v[k] = dz * h[k];
+        v[C] = dz;
+    }
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) wsum[wv][k] = v[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < PS) {       // every row is written in full (surplus workgroups write zeros)
+        float acc = 0.0f;
+        if ((int)threadIdx.x < NP)
+            for (int w = 0; w < kBlock / 64; ++w) acc += wsum[w][threadIdx.x];
+        part[(size_t)blockIdx.x * PS + threadIdx.x] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void k_head_fold1(const float *__restrict__ part, int64_t n_rows, int ps,
+                                                       float *__restrict__ tmp)
+{
+    const int i = threadIdx.x;
+    if (i >= ps) return;
+    const int64_t r0 = (int64_t)blockIdx.y * kFoldChunk;
+    const int64_t r1 = r0 + kFoldChunk < n_rows ? r0 + kFoldChunk : n_rows;
+    float sum = 0.0f;
+    for (int64_t r = r0; r < r1; ++r) sum += part[r * ps + i];
+    tmp[(int64_t)blockIdx.y * ps + i] = sum;
+}
+
+__global__ __launch_bounds__(kBlock) void k_head_fold2(const float *__restrict__ tmp, int64_t n_chunks, int ps, int C,
+                                                       float *__restrict__ gWo, float *__restrict__ gbo)
+{
+    const int i = threadIdx.x;
+    if (i > C) return;
+    float sum = 0.0f;
+    for (int64_t c = 0; c < n_chunks; ++c) sum += tmp[c * ps + i];
+    *(i < C ? gWo + i : gbo) += sum;
+}
+
 template <int F, int D>
 int backward_t(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
                const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
-               char *ws, hipStream_t s)
+               char *ws, hipStream_t s, const HeadBwd *head = nullptr)
 {
     constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH;
     const int64_t N = g->n_hits, E = g->n_segments;
@@ -1783,12 +1854,26 @@ int backward_t(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *
     constexpr int RS = GL::stride;
     if (w.rep_end - reinterpret_cast<char *>(rp) < (ptrdiff_t)((size_t)w.rows * RS * sizeof(float)))
         return fail(GNN_ERR_WORKSPACE, "partial-gradient table does not match GradLayout");
-    const float *ge = grad_out;
+    if (head && N > 0) {
+        // seeded start (NodeClassifier): the output network's backward writes gH_T and folds gWo, gbo.  Its
+        // partial rows go to G4 and the chunk sums to tmp - both free until the trunk below (and big enough:
+        // grid_for(N) <= N rows of head_stride <= 4 D floats; at most w.rows rows of GradLayout::stride)
+        static_assert(head_stride<F, D>() <= 4 * D && head_stride<F, D>() <= RS, "head rows fit G4 and tmp");
+        const unsigned hg = grid_for(N);
+        GNN_LAUNCH("k_head_bwd", (k_head_bwd<F, D>), hg, kBlock, s, H_all + (size_t)T * N * LDH, head->y, head->gy,
+                   head->Wo, gH, w.G4, N);
+        const int64_t nc = fold_chunks(hg);
+        GNN_LAUNCH("k_head_fold", k_head_fold1, dim3(1, (unsigned)nc), kBlock, s, w.G4, (int64_t)hg,
+                   head_stride<F, D>(), w.tmp);
+        GNN_LAUNCH("k_head_fold", k_head_fold2, 1, kBlock, s, w.tmp, nc, head_stride<F, D>(), C, head->gWo, head->gbo);
+    }
+    const float *ge = head ? nullptr : grad_out;
     for (int t = T; t >= 0; --t) {
         const float *Ht = H_all + (size_t)t * N * LDH;
         const float *et = e_all + (size_t)t * E;
-        // edge pass t backward: adds into gH (gradient w.r.t. H_t)
-        bool edge_done = false;
+        // edge pass t backward: adds into gH (gradient w.r.t. H_t); a NodeClassifier has no edge pass T - its
+        // backward starts from the seeded gH_T
+        bool edge_done = head && t == T;
         if constexpr (D >= 32) {
             // wide shapes, final pass (the only edge pass this loop still runs for them): the pull-form
             // kernels with the loss gradient as ge - k_hit_bwdW on a zero gradient row builds the records
@@ -2414,8 +2499,8 @@ __global__ __launch_bounds__(64) void k_bce_final(const float *__restrict__ part
 }
 
 #define BWD_FOR_EACH_SHAPE(X_) \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(11, 4) X_(11, 8) \
-    X_(11, 16)
+    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
+    X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
 
 }  // namespace
 
@@ -2473,13 +2558,13 @@ size_t backward_workspace_bytes(int64_t N, int64_t E, int F, int D)
 
 int backward(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
              const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
-             void *ws, size_t ws_bytes, hipStream_t s)
+             void *ws, size_t ws_bytes, hipStream_t s, const HeadBwd *head)
 {
     if (ws_bytes < backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
         return fail(GNN_ERR_WORKSPACE, "backward workspace too small: need %zu bytes",
                     backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return backward_t<F_, D_>(g, p, T, e_all, H_all, Q_all, grad_out, gr, base, s);
+#define X_(F_, D_) if (p->F == F_ && p->D == D_) return backward_t<F_, D_>(g, p, T, e_all, H_all, Q_all, grad_out, gr, base, s, head);
     BWD_FOR_EACH_SHAPE(X_)
 #undef X_
     return fail(GNN_ERR_UNSUPPORTED, "no backward kernel for input_dim=%d hidden_dim=%d", p->F, p->D);

@@ -179,9 +179,16 @@ int backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *
                     const int32_t *seg_ptr, int64_t n_graphs, int cap_h, int cap_s, int T,
                     const float *e_all, const float *H_all, const float *grad_out,
                     const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s);
+// NodeClassifier's output network y = sigmoid(Wo [H'_T | X] + bo) (gnn/MPNN_HitClassifier.ipynb cell 21): with
+// `head` the backward starts from the hit scores' gradient gy instead of the final edge pass (grad_out unused,
+// e_all holds the n_iters edge passes of the trunk) and adds the head's own gradients into gWo [C], gbo [1]
+struct HeadBwd {
+    const float *Wo, *y, *gy;
+    float *gWo, *gbo;
+};
 int backward(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
              const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
-             void *ws, size_t ws_bytes, hipStream_t s);
+             void *ws, size_t ws_bytes, hipStream_t s, const HeadBwd *head = nullptr);
 
 int edge_bwd(const float *H, const gnn_graph_t *g, const gnn_params_t *p, const float *e, const float *ge, float *gH,
              const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s);

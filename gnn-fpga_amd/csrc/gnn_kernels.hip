@@ -139,6 +139,17 @@ __device__ __forceinline__ void store_row4(float *__restrict__ row, const float 
     for (int i = 0; i < N4; ++i) o[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
 }
 
+// NodeClassifier's output network on a finished hit row h = [H'_T | X]: sigmoid(Wo h + bo), Wo [1, C]
+// (gnn/MPNN_HitClassifier.ipynb cell 21), k ascending from the bias in every kernel that runs it
+template <int C>
+__device__ __forceinline__ float head_score(const float *h, const float *__restrict__ Wo, const float *__restrict__ bo)
+{
+    float acc = bo[0];
+#pragma unroll
+    for (int k = 0; k < C; ++k) acc = fmaf(Wo[k], h[k], acc);
+    return sigmoid_f(acc);
+}
+
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
@@ -150,7 +161,10 @@ __global__ __launch_bounds__(kBlock) void k_input(const float *__restrict__ X,
                                                   const float *__restrict__ W1,
                                                   const float *__restrict__ b1,
                                                   float *__restrict__ H, int ldh,
-                                                  float *__restrict__ PQ, int64_t n_hits)
+                                                  float *__restrict__ PQ, int64_t n_hits,
+                                                  const float *__restrict__ Wo = nullptr,
+                                                  const float *__restrict__ bo = nullptr,
+                                                  float *__restrict__ y = nullptr)
 {
     constexpr int LDH = Shape<F, D>::LDH;
     const int64_t n = xcd_block() * kBlock + threadIdx.x;
@@ -169,6 +183,7 @@ __global__ __launch_bounds__(kBlock) void k_input(const float *__restrict__ X,
     }
     store_row4<LDH / 4>(H + n * ldh, h);
     if (PQ) store_pq<F, D>(h, W1, b1, PQ + n * 2 * D);
+    if (y) y[n] = head_score<F + D>(h, Wo, bo);           // n_iters = 0: the output network reads H0
 }
 
 // P/Q from an existing H (stand-alone EdgeNetwork entry point).
@@ -232,7 +247,8 @@ __global__ __launch_bounds__(kBlock) void k_node(
     const int32_t *__restrict__ out_eid, const int32_t *__restrict__ out_nbr,
     const float *__restrict__ W3, const float *__restrict__ b3, const float *__restrict__ W4,
     const float *__restrict__ b4, const float *__restrict__ W1, const float *__restrict__ b1,
-    float *__restrict__ Hn, int ldhn, float *__restrict__ PQ, float *__restrict__ Qkeep, int64_t n_hits)
+    float *__restrict__ Hn, int ldhn, float *__restrict__ PQ, float *__restrict__ Qkeep, int64_t n_hits,
+    const float *__restrict__ Wo, const float *__restrict__ bo, float *__restrict__ y)
 {
     constexpr int C = Shape<F, D>::C;
     constexpr int LDH = Shape<F, D>::LDH;
@@ -296,6 +312,7 @@ __global__ __launch_bounds__(kBlock) void k_node(
     for (int k = D; k < LDH; ++k) hn[k] = M[2 * LDH + k];   // skip concat of X (model.py:154)
     store_row4<LDH / 4>(Hn + n * ldhn, hn);
     if (PQ) store_pq<F, D>(hn, W1, b1, PQ + n * 2 * D);
+    if (y) y[n] = head_score<C>(hn, Wo, bo);             // last node pass of a NodeClassifier: its output network
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -393,7 +410,8 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
     const float *__restrict__ H, int ldh, const float *__restrict__ M, const float *__restrict__ W3,
     const float *__restrict__ b3, const float *__restrict__ W4, const float *__restrict__ b4,
     const float *__restrict__ W1, const float *__restrict__ b1, float *__restrict__ Hn, int ldhn,
-    float *__restrict__ PQ, float *__restrict__ Qkeep, int64_t n_hits)
+    float *__restrict__ PQ, float *__restrict__ Qkeep, int64_t n_hits, const float *__restrict__ Wo,
+    const float *__restrict__ bo, float *__restrict__ y)
 {
     typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH, RS = kBlock + 4;
@@ -497,6 +515,24 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
 #pragma unroll
         for (int v = D / 4; v < LDH / 4; ++v)
             reinterpret_cast<float4 *>(Hn + n * ldhn)[v] = make_float4(hp[4 * v], hp[4 * v + 1], hp[4 * v + 2], hp[4 * v + 3]);
+    }
+    if (y) {                                             // (kernel-uniform) last node pass of a NodeClassifier:
+        // y = sigmoid(Wo [H' | x] + bo) - H' goes through LDS back to the thread that owns the hit
+        __syncthreads();
+#pragma unroll
+        for (int it = 0; it < RT; ++it)
+#pragma unroll
+            for (int ht = 0; ht < 4; ++ht) {
+                float *x = lds + (16 * it + 4 * g4) * RS + hcol + 16 * ht;
+                x[0] = hn[it][ht].x; x[RS] = hn[it][ht].y; x[2 * RS] = hn[it][ht].z; x[3 * RS] = hn[it][ht].w;
+            }
+        __syncthreads();
+        if (active) {
+            float h[C];
+#pragma unroll
+            for (int k = 0; k < C; ++k) h[k] = k < D ? lds[k * RS + threadIdx.x] : hp[k];
+            y[n] = head_score<C>(h, Wo, bo);
+        }
     }
     if (!PQ) return;                                     // (kernel-uniform)
     // ---- P = W1a [H' | x] + b1, Q = W1b [H' | x] for the next edge pass
@@ -977,26 +1013,30 @@ __global__ __launch_bounds__(kBlock) void k_unpad(const float *__restrict__ H, i
 // ---------------------------------------------------------------------------------------------
 // shape dispatch
 // ---------------------------------------------------------------------------------------------
+// (input_dim 4: the hit classifier of gnn/MPNN_HitClassifier.ipynb - r, phi, z and the seed label - and the first
+// shapes whose hit rows [H' | X] have no zero pad column, C == LDH)
 #define GNN_FOR_EACH_SHAPE(X_) \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(11, 4) X_(11, 8) \
-    X_(11, 16)
+    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
+    X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
 
+// (Wo / bo / y: a NodeClassifier without message passing scores its hits from H0 here)
 template <int F, int D>
 int run_input(const float *X, const float *Win, const float *bin, const float *W1,
-              const float *b1, float *H, int ldh, float *PQ, int64_t n, hipStream_t s)
+              const float *b1, float *H, int ldh, float *PQ, int64_t n, hipStream_t s,
+              const float *Wo = nullptr, const float *bo = nullptr, float *y = nullptr)
 {
     if (n <= 0) return 0;
     if constexpr (D >= 32) {
         // wide hidden layers at detector size: the P / Q products on the matrix cores
         if (PQ && n >= kNodeWideMinHits && ldh == Shape<F, D>::LDH && !getenv("GNN_NODE_ONE_LANE")) {
             GNN_LAUNCH("k_input", (k_input<F, D>), grid_for(n), kBlock, s, X, Win, bin, W1, b1, H, ldh,
-                       (float *)nullptr, n);
+                       (float *)nullptr, n, Wo, bo, y);
             GNN_LAUNCH("k_pq_mlpW", (k_pq_mlpW<F, D>), grid_for(n), kBlock, s, H, ldh, W1, b1, PQ, n);
             return 0;
         }
     }
     GNN_LAUNCH("k_input", (k_input<F, D>), grid_for(n), kBlock, s, X, Win, bin, W1, b1, H, ldh,
-               PQ, n);
+               PQ, n, Wo, bo, y);
     return 0;
 }
 
@@ -1021,22 +1061,24 @@ int run_edge(const int32_t *src, const int32_t *dst, const float *PQ, const floa
 template <int F, int D>
 int run_node(const float *H, int ldh, const float *e, const gnn_graph_t *g, const float *W3,
              const float *b3, const float *W4, const float *b4, const float *W1, const float *b1,
-             float *Hn, int ldhn, float *PQ, hipStream_t s, float *Qkeep = nullptr, float *Mbuf = nullptr)
+             float *Hn, int ldhn, float *PQ, hipStream_t s, float *Qkeep = nullptr, float *Mbuf = nullptr,
+             const float *Wo = nullptr, const float *bo = nullptr, float *y = nullptr,
+             int64_t wide_min_hits = kNodeWideMinHits)
 {
     if (g->n_hits <= 0) return 0;
     if constexpr (D >= 32) {
         // wide hidden layers at detector size: 16-lane list walk + matrix-core MLP (Mbuf: [n_hits, 2 ldh] scratch)
-        if (Mbuf && g->n_hits >= kNodeWideMinHits && ldh == Shape<F, D>::LDH && !getenv("GNN_NODE_ONE_LANE")) {
+        if (Mbuf && g->n_hits >= wide_min_hits && ldh == Shape<F, D>::LDH && !getenv("GNN_NODE_ONE_LANE")) {
             GNN_LAUNCH("k_node_walkW", (k_node_walkW<F, D>), grid_walk(g->n_hits), kWalkBlock, s, H, ldh, e, g->in_ptr,
                        g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, Mbuf, g->n_hits);
             GNN_LAUNCH("k_node_mlpW", (k_node_mlpW<F, D>), grid_for(g->n_hits), kBlock, s, H, ldh, Mbuf, W3, b3, W4, b4,
-                       W1, b1, Hn, ldhn, PQ, Qkeep, g->n_hits);
+                       W1, b1, Hn, ldhn, PQ, Qkeep, g->n_hits, Wo, bo, y);
             return 0;
         }
     }
     GNN_LAUNCH("k_node", (k_node<F, D>), grid_for(g->n_hits), kBlock, s, H, ldh, e, g->in_ptr,
                g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, W3, b3, W4, b4, W1, b1,
-               Hn, ldhn, PQ, Qkeep, g->n_hits);
+               Hn, ldhn, PQ, Qkeep, g->n_hits, Wo, bo, y);
     return 0;
 }
 
@@ -1061,10 +1103,19 @@ Workspace carve(void *base, int64_t n_hits, int64_t n_seg, int ldh, int D)
     return w;
 }
 
+// NodeClassifier's output network in place of the final edge pass: y [n_hits] = sigmoid(Wo [H'_T | X] + bo)
+struct Head {
+    const float *Wo, *bo;
+    float *y;
+};
+
+// head == NULL: SegmentClassifier (n_iters x (edge pass, node pass), final edge pass -> e_out).  head != NULL:
+// NodeClassifier - the loop ends after the last node pass, whose kernel scores the hits (k_input's for
+// n_iters = 0): no final edge pass and no P / Q for it; e_trace then has n_iters rows.
 template <int F, int D>
 int forward_impl(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, float *e_out,
                  float *e_trace, float *H_trace, void *ws, hipStream_t s, float *H_all = nullptr,
-                 float *Q_all = nullptr)
+                 float *Q_all = nullptr, const Head *head = nullptr)
 {
     constexpr int C = Shape<F, D>::C;
     constexpr int LDH = Shape<F, D>::LDH;
@@ -1072,13 +1123,17 @@ int forward_impl(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, float
     Workspace w = carve(ws, N, E, LDH, D);
     // training forward: every iteration's H is kept (H_all), no ping-pong
     float *H = H_all ? H_all : w.Ha, *Hn = H_all ? H_all + (size_t)N * LDH : w.Hb;
-    int rc = run_input<F, D>(g->X, p->Win, p->bin, p->W1, p->b1, H, LDH, w.PQ, N, s);
+    const bool head0 = head && n_iters == 0;
+    int rc = run_input<F, D>(g->X, p->Win, p->bin, p->W1, p->b1, H, LDH, head0 ? nullptr : w.PQ, N, s,
+                             head0 ? head->Wo : nullptr, head0 ? head->bo : nullptr, head0 ? head->y : nullptr);
     if (rc) return rc;
     for (int t = 0; t <= n_iters; ++t) {
         if (H_trace && N > 0)
             GNN_LAUNCH("k_unpad", k_unpad, grid_for(N * C), kBlock, s, H, LDH, C,
                        H_trace + (size_t)t * N * C, N * C);
         const bool last = (t == n_iters);
+        if (last && head) break;
+        const Head *tail = (head && t == n_iters - 1) ? head : nullptr;      // the node pass that feeds the head
         float *e_t = e_trace ? e_trace + (size_t)t * E : (last ? e_out : w.e);
         rc = run_edge<D>(g->src, g->dst, w.PQ, p->b1, p->W2, p->b2, e_t, E, s);
         if (rc) return rc;
@@ -1091,7 +1146,12 @@ int forward_impl(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, float
             break;
         }
         rc = run_node<F, D>(H, LDH, e_t, g, p->W3, p->b3, p->W4, p->b4, p->W1, p->b1, Hn, LDH,
-                            w.PQ, s, Q_all ? Q_all + (size_t)t * N * D : nullptr, w.M);
+                            tail ? nullptr : w.PQ, s, Q_all ? Q_all + (size_t)t * N * D : nullptr, w.M,
+                            tail ? tail->Wo : nullptr, tail ? tail->bo : nullptr, tail ? tail->y : nullptr,
+                            // a NodeClassifier takes the wide kernels at every size: at the notebook's 32 x 50 hits
+                            // the one-lane k_node<4, 64> spills (0.21 ms a pass against 0.075 ms for k_node_walkW +
+                            // k_node_mlpW, profiles/nodeclf_kernel_trace.txt); SegmentClassifier keeps its routes
+                            head ? 0 : kNodeWideMinHits);
         if (rc) return rc;
         if (H_all) {
             H = Hn;
@@ -1284,6 +1344,79 @@ int gnn_segclf_backward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_i
         return fail(GNN_ERR_BADARG, "gnn_segclf_backward: gradient pointer missing");
     return backward(g, p, n_iters, e_all, H_all, Q_all, grad_out, gr, workspace, workspace_bytes,
                     static_cast<hipStream_t>(stream));
+}
+
+// ---- NodeClassifier (gnn/MPNN_HitClassifier.ipynb cells 20-21): the trunk above, the output network in place
+// of the final edge pass ------------------------------------------------------------------------------------
+static int nodeclf_check(const char *who, const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
+                         int32_t n_iters, const float *y, void *workspace, size_t workspace_bytes)
+{
+    if (!g || !p || !Wo || !bo || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0)
+        return fail(GNN_ERR_BADARG, "%s: bad argument", who);
+    if (g->n_hits > 0 && (!y || !g->X || !g->in_ptr || !g->out_ptr))
+        return fail(GNN_ERR_BADARG, "%s: hit arrays missing", who);
+    if (n_iters > 0 && g->n_segments > 0 && (!g->src || !g->dst))
+        return fail(GNN_ERR_BADARG, "%s: segment arrays missing", who);
+    if (!p->Win || !p->bin || !p->W1 || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4)
+        return fail(GNN_ERR_BADARG, "%s: weight pointer missing", who);
+    if (!gnn_shape_supported(p->F, p->D))
+        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    if (!workspace || workspace_bytes < gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
+        return fail(GNN_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes", who,
+                    gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
+    return 0;
+}
+
+int gnn_nodeclf_forward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo, int32_t n_iters,
+                        float *y_out, float *H_trace, void *workspace, size_t workspace_bytes, void *stream)
+{
+    gnn::ProfChain chain_;
+    int rc = nodeclf_check("gnn_nodeclf_forward", g, p, Wo, bo, n_iters, y_out, workspace, workspace_bytes);
+    if (rc) return rc;
+    void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Head head = {Wo, bo, y_out};
+#define X_(F_, D_) if (p->F == F_ && p->D == D_) return forward_impl<F_, D_>(g, p, n_iters, nullptr, nullptr, H_trace, ws, s, nullptr, nullptr, &head);
+    GNN_FOR_EACH_SHAPE(X_)
+#undef X_
+    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+}
+
+int gnn_nodeclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
+                              int32_t n_iters, float *e_all, float *H_all, float *Q_all, float *y_out, void *workspace,
+                              size_t workspace_bytes, void *stream)
+{
+    gnn::ProfChain chain_;
+    int rc = nodeclf_check("gnn_nodeclf_forward_train", g, p, Wo, bo, n_iters, y_out, workspace, workspace_bytes);
+    if (rc) return rc;
+    if ((n_iters > 0 && g->n_segments > 0 && !e_all) || (g->n_hits > 0 && !H_all))
+        return fail(GNN_ERR_BADARG, "gnn_nodeclf_forward_train: array missing");
+    void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Head head = {Wo, bo, y_out};
+#define X_(F_, D_) if (p->F == F_ && p->D == D_) return forward_impl<F_, D_>(g, p, n_iters, nullptr, e_all, nullptr, ws, s, H_all, Q_all, &head);
+    GNN_FOR_EACH_SHAPE(X_)
+#undef X_
+    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+}
+
+int gnn_nodeclf_backward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo, int32_t n_iters,
+                         const float *e_all, const float *H_all, const float *Q_all, const float *y, const float *grad_y,
+                         const gnn_grads_t *gr, float *gWo, float *gbo, void *workspace, size_t workspace_bytes,
+                         void *stream)
+{
+    gnn::ProfChain chain_;
+    if (!g || !p || !gr || !Wo || !bo || !gWo || !gbo || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0 || !workspace)
+        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: bad argument");
+    if ((n_iters > 0 && g->n_segments > 0 && !e_all) || (g->n_hits > 0 && (!H_all || !y || !grad_y)))
+        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: saved tensors missing");
+    if (!gr->Win || !gr->bin || !gr->W1 || !gr->b1 || !gr->W2 || !gr->b2 || !gr->W3 || !gr->b3 || !gr->W4 || !gr->b4)
+        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: gradient pointer missing");
+    if (!gnn_shape_supported(p->F, p->D))
+        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const HeadBwd head = {Wo, y, grad_y, gWo, gbo};
+    return backward(g, p, n_iters, e_all, H_all, Q_all, nullptr, gr, workspace, workspace_bytes,
+                    static_cast<hipStream_t>(stream), &head);
 }
 
 // dense one-hot incidence matrices -> index form, where the matrices live (the reference's input

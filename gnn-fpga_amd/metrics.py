@@ -305,5 +305,10 @@ def evaluate(model, generator, n_batches, thresholds=(0.5,), **kw):
             batch, target = next(generator)
             if target is None:
                 raise ValueError("the generator gave a batch without targets")
-            m.update(model(batch), target, batch=batch, include_padding=kw.get("include_padding", False))
+            if getattr(model, "scores_hits", False):
+                # a NodeClassifier scores hits: every hit counts, as in the notebook's sklearn calls on the flattened
+                # labels (gnn/MPNN_HitClassifier.ipynb cell 35)
+                m.update(model(batch), target)
+            else:
+                m.update(model(batch), target, batch=batch, include_padding=kw.get("include_padding", False))
     return m

@@ -407,3 +407,72 @@ class SegmentClassifier(nn.Module):
         if batch.dense_shape:
             e = e.view(batch.dense_shape[0], batch.dense_shape[2])
         return (e, res[1], res[2]) if trace else e
+
+
+class NodeClassifier(nn.Module):
+    """Hit classification GNN (reference gnn/MPNN_HitClassifier.ipynb cells 20-21), HIP forward.
+
+    Same constructor, module tree and twelve state_dict keys as the notebook's class: the segment
+    classifier's trunk (input network, n_iters x (edge pass, node pass)) followed by
+    `output_network = Sequential(Linear(C, 1), Sigmoid())` on every hit's [H'_T | X].  The output
+    network runs inside the last node pass's kernel (gnn_nodeclf_forward); there is no final edge pass.
+    `forward([X, Ri, Ro])` with dense inputs returns [B, N] (every hit, zero-padded ones included, as in
+    the reference); with a HitGraphBatch it returns [n_hits].  Always the per-module kernels."""
+
+    scores_hits = True          # metrics.evaluate counts hits, not segments
+
+    def __init__(self, input_dim=4, hidden_dim=8, n_iters=1, hidden_activation=nn.Tanh):
+        super(NodeClassifier, self).__init__()
+        self.n_iters = n_iters
+        self.input_dim, self.hidden_dim = input_dim, hidden_dim
+        _require_tanh(hidden_activation)
+        self.input_network = nn.Sequential(
+            nn.Linear(input_dim, hidden_dim),
+            hidden_activation())
+        self.edge_network = EdgeNetwork(input_dim + hidden_dim, hidden_dim, hidden_activation)
+        self.node_network = NodeNetwork(input_dim + hidden_dim, hidden_dim, hidden_activation)
+        self.output_network = nn.Sequential(
+            nn.Linear(input_dim + hidden_dim, 1),
+            nn.Sigmoid())
+        self._workspace = None
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st["_workspace"] = None
+        return st
+
+    def effective_weights(self):
+        """The trunk's ten tensors the kernels consume, in state_dict order, masks applied."""
+        lin = self.input_network[0]
+        return ([_f32c(lin.weight), _f32c(lin.bias)] + self.edge_network.weights() +
+                self.node_network.weights())
+
+    def forward(self, inputs, trace=False):
+        """inputs = [X, Ri, Ro] or a HitGraphBatch -> hit scores ([B, N] or [n_hits]); trace=True also
+        returns the hit features of every iteration [(T+1), n_hits, C]."""
+        if isinstance(inputs, HitGraphBatch):
+            batch = inputs
+        else:
+            X, Ri, Ro = inputs
+            batch = _as_batch(X, Ri, Ro)
+        F, D = self.input_dim, self.hidden_dim
+        if not batch.X.is_cuda:
+            raise _lib.GnnHipError("NodeClassifier.forward needs tensors on a ROCm device; "
+                                   "there is no CPU path")
+        if not _lib.shape_supported(F, D):
+            raise _lib.GnnHipError("no HIP kernel for input_dim=%d hidden_dim=%d" % (F, D))
+        if not trace and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            from .autograd import nodeclf_apply   # backward kernels live there
+            y = nodeclf_apply(self, batch)
+        else:
+            out = self.output_network[0]
+            need = _lib.workspace_bytes(batch.n_hits, batch.n_segments, F, D)
+            if (self._workspace is None or self._workspace.numel() < need or
+                    self._workspace.device != batch.X.device):
+                self._workspace = torch.empty(need, dtype=torch.uint8, device=batch.X.device)
+            res = _lib.nodeclf_forward(batch, self.effective_weights(), _f32c(out.weight), _f32c(out.bias), F, D,
+                                       self.n_iters, workspace=self._workspace, trace=trace)
+            y = res[0] if trace else res
+        if batch.dense_shape:
+            y = y.view(batch.dense_shape[0], batch.dense_shape[1])
+        return (y, res[1]) if trace else y

@@ -164,3 +164,54 @@ def barrel_event(n_tracks, n_noise, n_events=1, seed=0):
     return HitColumns(np.concatenate(cols["r"]).astype(np.float32), np.concatenate(cols["phi"]).astype(np.float32),
                       np.concatenate(cols["z"]).astype(np.float32), np.concatenate(cols["layer"]).astype(np.int32),
                       np.concatenate(cols["particle_id"]).astype(np.int64), event_ptr)
+
+
+# gnn/MPNN_HitClassifier.ipynb cells 12-15: 10 detector layers x 5 candidate hits per sample (layer-major), the
+# segments of every adjacent-layer pair in np.where order, X = [r, phi, z, seed] / (1000, pi, 1000, 1)
+HitSamples = namedtuple("HitSamples", ["X", "Ri", "Ro", "y", "src", "dst"])
+
+
+def hit_classifier_samples(n, seed=0, n_det_layers=10, n_layer_hits=5, n_seed_layers=3):
+    """Seeded stand-ins for the notebook's track samples (its ACTS preparation, cells 5-15, needs pandas and the
+    dataset).  Per sample one straight-in-(r, z), curving-in-phi track crosses the 10 layers; each layer keeps
+    its true hit and the 4 nearest noise hits in (eta, phi), sorted by that distance (the true hit first, as
+    cell 15's sort puts it); phi is centred on the first true hit; the last feature is the label on the first
+    3 layers (the seed), 0 elsewhere.  Returns HitSamples: X float32 [n, 50, 4], Ri / Ro uint8 [n, 50, 225]
+    (Ro = inner hit, Ri = outer hit), y uint8 [n, 50] (hit labels), src / dst int32 [225] (the same segments for
+    every sample: the candidate layout is fixed)."""
+    rng = np.random.default_rng(seed)
+    n_hits = n_det_layers * n_layer_hits
+    n_edges = n_layer_hits ** 2 * (n_det_layers - 1)
+    layers = np.repeat(np.arange(n_det_layers), n_layer_hits)
+    adj = np.stack(np.where((layers[None, :] - layers[:, None]) == 1), axis=1)     # cell 15's adj_idx
+    src, dst = adj[:, 0].astype(np.int32), adj[:, 1].astype(np.int32)
+    assert src.shape[0] == n_edges
+    radii = 32.0 + 72.0 * np.arange(n_det_layers)                                  # mm
+    X = np.zeros((n, n_hits, 4), dtype=np.float32)
+    y = np.zeros((n, n_hits), dtype=np.uint8)
+    for i in range(n):
+        eta, phi0, z0 = rng.uniform(-1.5, 1.5), rng.uniform(-np.pi, np.pi), rng.normal(0.0, 50.0)
+        curv = rng.uniform(-1e-3, 1e-3)                                            # rad / mm
+        phi_ref = phi0 + curv * radii[0]                                           # the first true hit
+        for l, r in enumerate(radii):
+            z_t = z0 + r * np.sinh(eta)
+            phi_t = phi0 + curv * r
+            d_eta = rng.normal(0.0, 0.05, size=n_layer_hits - 1)
+            d_phi = rng.normal(0.0, 0.05, size=n_layer_hits - 1)
+            order = np.argsort(np.hypot(d_eta, d_phi))
+            z = np.concatenate([[z_t], r * np.sinh(eta + d_eta[order]) + z0])
+            phi = np.concatenate([[phi_t], phi_t + d_phi[order]])
+            s = slice(l * n_layer_hits, (l + 1) * n_layer_hits)
+            dphi = np.mod(phi - phi_ref + np.pi, 2 * np.pi) - np.pi               # centred on the first true hit
+            X[i, s, 0] = r / 1000.0
+            X[i, s, 1] = dphi / np.pi
+            X[i, s, 2] = z / 1000.0
+            y[i, l * n_layer_hits] = 1
+        seed_hits = layers < n_seed_layers
+        X[i, seed_hits, 3] = y[i, seed_hits]
+    edge_idx = np.arange(n_edges)
+    Ri = np.zeros((n, n_hits, n_edges), dtype=np.uint8)
+    Ro = np.zeros((n, n_hits, n_edges), dtype=np.uint8)
+    Ri[:, dst, edge_idx] = 1
+    Ro[:, src, edge_idx] = 1
+    return HitSamples(X, Ri, Ro, y, src, dst)

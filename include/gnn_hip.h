@@ -209,6 +209,33 @@ int gnn_segclf_backward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_i
                         const float *grad_out, const gnn_grads_t *grads, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* NodeClassifier (gnn/MPNN_HitClassifier.ipynb cells 20-21, the reference's hit classifier): the trunk of
+ * gnn_segclf_forward - input network, n_iters x (edge pass, node pass) - then the output network
+ *   y[n] = sigmoid(Wo [H'_T[n] | X[n]] + bo),   Wo [1, C] (H' columns first, then X), bo [1]
+ * in place of the final edge pass (the last node pass's kernel scores its hits; with n_iters = 0 the
+ * input network's does).  Wo, bo, gWo, gbo are separate device pointers: gnn_params_t / gnn_grads_t
+ * are the trunk's ten tensors.  Workspace: gnn_forward_workspace_bytes for both forwards,
+ * gnn_backward_workspace_bytes for the backward.
+ * gnn_nodeclf_forward replaces NodeClassifier.forward (cell 21): y_out [n_hits]; H_trace (NULL to
+ * skip) [(n_iters+1), n_hits, C] as in gnn_segclf_forward. */
+int gnn_nodeclf_forward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
+                        int32_t n_iters, float *y_out, float *H_trace, void *workspace,
+                        size_t workspace_bytes, void *stream);
+/* Training forward of cell 21 (as run by gnn/estimator.py's training_step, cell 30): like
+ * gnn_segclf_forward_train, with the n_iters trunk edge passes in e_all [n_iters, n_segments],
+ * H_all [(n_iters+1), n_hits, ldh], Q_all [n_iters, n_hits, hidden_dim] (or NULL), y_out [n_hits]. */
+int gnn_nodeclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
+                              int32_t n_iters, float *e_all, float *H_all, float *Q_all, float *y_out,
+                              void *workspace, size_t workspace_bytes, void *stream);
+/* Backward of cell 21 for loss.backward() in gnn/estimator.py (cell 30): given grad_y [n_hits] =
+ * dLoss/dy and the tensors saved by gnn_nodeclf_forward_train (y = its y_out), ADDS the gradients of
+ * the ten trunk tensors into `grads` and of the output network into gWo [C], gbo [1] (zero them first).
+ * dz = grad_y y (1 - y) seeds gH_T = dz Wo[:D]; every sum runs in a fixed order (bit-reproducible). */
+int gnn_nodeclf_backward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
+                         int32_t n_iters, const float *e_all, const float *H_all, const float *Q_all /* or NULL */,
+                         const float *y, const float *grad_y, const gnn_grads_t *grads, float *gWo, float *gbo,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* The same gradients for a batch of SMALL graphs (gnn/prepareMuonGraphs.py sizes) in ONE launch:
  * one workgroup per graph keeps the graph's saved rows and every intermediate in LDS (counterpart
  * of gnn_segclf_forward_events; same layout contract for hit_ptr / seg_ptr).  Workspace:
