@@ -69,6 +69,10 @@ class GnnGraphBuildSizes(ctypes.Structure):
                                     "max_graph_segments", "status")]
 
 
+class GnnHitSamplesSizes(ctypes.Structure):
+    _fields_ = [(n, _i64) for n in ("n_samples", "n_hits", "n_segments", "n_kept", "n_groups", "n_tasks", "status")]
+
+
 # name -> (restype, argtypes); must list every function include/gnn_hip.h declares
 SIGNATURES = {
     "gnn_abi_version": (ctypes.c_int, []),
@@ -133,6 +137,11 @@ SIGNATURES = {
     "gnn_graph_build_fill": (ctypes.c_int, [_f, _i64, _i64, _f, _i32, _i32, _i32, ctypes.c_float, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.POINTER(GnnGraphBuildSizes), _f, _sz, _f, _f, _f, _f, _f, _f]),
+    "gnn_hit_samples_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "gnn_hit_samples_sizes": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _f, _i64, _i32, _i32, _f, _sz, _f, _f]),
+    "gnn_hit_samples_fill": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, _i32, _i32, _i32, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_double, ctypes.POINTER(GnnHitSamplesSizes), _f,
+                                            _sz, _f, _f, _f, _f, _f, _f, _f]),
     "gnn_metrics_bins": (_i64, [_i32]),
     "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
@@ -883,6 +892,49 @@ def graph_build_fill(ws, sizes, particle_id, event_ptr, pairs, n_layers, n_phi_s
             ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(), src.data_ptr(), dst.data_ptr(),
             None if y is None else y.data_ptr(), hit_index.data_ptr(), st))
     return X, src, dst, y, hit_index
+
+
+def hit_samples_sizes(r, phi, z, layer, particle_id, event_ptr, n_det_layers, n_layer_hits):
+    """Stage 1 of the hit-sample builder (csrc/hit_samples.hip): (workspace, GnnHitSamplesSizes) - the sizes come
+    back in ONE read-back."""
+    dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
+    need = int(load().gnn_hit_samples_workspace_bytes(n, E, n_det_layers, n_layer_hits))
+    if need == 0:
+        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(ctypes.sizeof(GnnHitSamplesSizes) // 8, dtype=torch.int64, device=dev)
+    with _on(r) as st:
+        _check(load().gnn_hit_samples_sizes(
+            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
+            _dev(layer, torch.int32, "layer"), _dev(particle_id, torch.int64, "particle_id"), n,
+            _dev(event_ptr, torch.int64, "event_ptr"), E, n_det_layers, n_layer_hits, ws.data_ptr(), ws.numel(),
+            out.data_ptr(), st))
+    host = out.cpu().numpy()
+    sizes = GnnHitSamplesSizes()
+    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnHitSamplesSizes))
+    return ws, sizes
+
+
+def hit_samples_fill(ws, sizes, r, phi, z, particle_id, n_events, n_det_layers, n_layer_hits, n_seed_layers,
+                     feature_scale):
+    """Stage 2: (X [N, 4], y [N], hit_index [N] int64, src, dst [E] int32, keys [S, 2] int64), S, N and E from
+    `sizes`."""
+    dev = ws.device
+    S, N, E = int(sizes.n_samples), int(sizes.n_hits), int(sizes.n_segments)
+    X = torch.empty((N, 4), dtype=torch.float32, device=dev)
+    y = torch.empty(N, dtype=torch.float32, device=dev)
+    hit_index = torch.empty(N, dtype=torch.int64, device=dev)
+    src = torch.empty(E, dtype=torch.int32, device=dev)
+    dst = torch.empty(E, dtype=torch.int32, device=dev)
+    keys = torch.empty((S, 2), dtype=torch.int64, device=dev)
+    with _on(ws) as st:
+        _check(load().gnn_hit_samples_fill(
+            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
+            _dev(particle_id, torch.int64, "particle_id"), int(r.shape[0]), n_events, n_det_layers, n_layer_hits,
+            n_seed_layers, feature_scale[0], feature_scale[1], feature_scale[2], ctypes.byref(sizes), ws.data_ptr(),
+            ws.numel(), X.data_ptr(), y.data_ptr(), hit_index.data_ptr(), src.data_ptr(), dst.data_ptr(),
+            keys.data_ptr(), st))
+    return X, y, hit_index, src, dst, keys
 
 
 def plan_build_fill(X, src, dst, n_hits, n_segments, chunk_segments, sizes, workspace, arrays):

@@ -1,0 +1,652 @@
+// hit_samples.hip - the hit classifier's track samples from detector hits on the GPU.
+//
+// The reference builds them on the host in pandas (gnn/MPNN_HitClassifier.ipynb cells 5 and 9-15): deduplicate the
+// hits per (event, particle, layer), keep the events with more than n_layer_hits hits on every present layer and the
+// (event, particle) pairs whose hits cover all n_det_layers layers, and for each of them and each layer take the
+// n_layer_hits hits nearest the track's own hit in (eta, phi).  gnn-fpga_amd/hit_samples.py is the numpy
+// specification of what is computed here; the distance is the reference's float32 arithmetic in its order of
+// operations, with contraction to FMA off (the pragma) and a correctly rounded sqrt.
+//
+//   gnn_hit_samples_sizes
+//     k_hs_key       one lane per hit: its event (binary search of event_ptr), checks; sort keys pid (biased)
+//     radix sort A   (pid, row)                                   } stable: (event, pid, row) order, then
+//     k_hs_evkey     event of each sorted hit                     } (event, pid) groups numbered by a scan of
+//     radix sort B   (event, row of A)                            } the group starts
+//     k_hs_gflag     1 where a new (event, pid) group starts; scan -> group of every position
+//     k_hs_layerkey  (group << 6 | layer) by input row
+//     radix sort C   -> every group's hits layer by layer, in frame order on each layer
+//     k_hs_gstart    each group's first position
+//     k_hs_walk      one lane per group: per layer the hit of smallest r (the first on ties) is kept; counts
+//                    kept hits per (event, layer) (atomics: counts only) and the group's distinct layers
+//     k_hs_event     one lane per event: does every present layer have more than n_layer_hits kept hits?
+//     k_hs_sflag     one lane per group: a sample when its event passed and it covers all layers; scan -> sample
+//                    numbers in (event, pid) order; samples per event -> sample and task offsets (scan)
+//     k_hs_track     one lane per sample: its kept hit on each layer and that hit's float64-chain eta
+//     k_hs_bucketkey (event * L + layer) of every kept hit; radix sort D -> each (event, layer) in frame order
+//     k_hs_stage     float32-chain eta and phi of every kept hit, SoA in that order
+//     k_hs_final     the sizes and the status word
+//   gnn_hit_samples_fill
+//     k_hs_fill<K>   one workgroup per (event, block of 64 of its samples, layer), one lane per sample: the layer's
+//                    hits through LDS (every lane reads the same word: a broadcast), a top-K list in registers;
+//                    writes X, y, hit_index of the sample's K candidates on that layer
+//     k_hs_segments  the fixed adjacent-layer pattern offset by L * K per sample; k_hs_keys (event, particle)
+// Nothing is ordered by atomics: two builds of one input give the same bits.
+#include <cstring>
+
+#include <rocprim/rocprim.hpp>
+
+#include "common.h"
+
+#include <cmath>
+
+#pragma clang fp contract(off)
+
+namespace gnn {
+namespace {
+
+constexpr int kMaxK = 16, kMaxL = 64;                  // n_layer_hits, n_det_layers (the layer is 6 bits of a key)
+constexpr int kFB = 64;                                // samples per fill workgroup, one lane each
+constexpr int kTile = 1024;                            // layer hits per LDS tile
+constexpr int kFillWgPerCu = 16;
+constexpr float kPiF = (float)M_PI;                    // numpy compares float32 data with float32(np.pi)
+constexpr float kTwoPiF = (float)(2.0 * M_PI);
+constexpr int kStatusLayer = 1, kStatusInt32 = 2, kStatusEvents = 4, kStatusFinite = 8;
+constexpr uint32_t kNanKey = 0x7FC00000u, kNoKey = 0xFFFFFFFFu;
+
+typedef unsigned long long u64;
+
+// gnn/MPNN_HitClassifier.ipynb cell 9 calc_eta on float32 columns: numpy's float32 ufuncs
+__device__ __forceinline__ float eta32(float r, float z) { return -1.0f * logf(tanf(atan2f(r, z) / 2.0f)); }
+// ... and on the track hit, an iloc row of a mixed-dtype frame: float64
+__device__ __forceinline__ double eta64(float r, float z) { return -1.0 * log(tan(atan2((double)r, (double)z) / 2.0)); }
+
+// cell 9 calc_dphi, float32
+__device__ __forceinline__ float wrap_dphi(float d)
+{
+    if (d > kPiF) d = d - kTwoPiF;
+    if (d < -kPiF) d = d + kTwoPiF;
+    return d;
+}
+
+// an order-preserving key of a non-negative float (a sum of squares or its sqrt); every NaN is one key above +inf
+__device__ __forceinline__ uint32_t dkey(float v) { return v != v ? kNanKey : __float_as_uint(v); }
+
+int bits_for(int64_t v)                                // bits to hold 0 .. v
+{
+    int b = 1;
+    while (b < 63 && (v >> b) != 0) ++b;
+    return b;
+}
+
+struct HsWs {
+    int32_t *status;                                   // head: [status | pad] [cnt E*L] [gpc 2 * stride]
+    int32_t *cnt, *gpc;
+    int32_t *evt, *kept, *gf, *gx, *sf, *sx, *gst, *gnl, *gev, *ok, *sptr, *tbase, *trk, *sev, *boff;
+    u64 *ka, *kb;
+    int32_t *va, *vb;
+    float *leta, *lphi, *teta;
+    int32_t *sums;
+    void *temp;
+    size_t temp_bytes;
+    int64_t EL, stride, head_bytes;
+    size_t bytes;
+};
+
+size_t sort_temp_bytes(int64_t n)
+{
+    size_t t = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, t, (const u64 *)nullptr, (u64 *)nullptr, (const int32_t *)nullptr,
+                                    (int32_t *)nullptr, (size_t)n, 0u, 64u, (hipStream_t)0, false);
+    return t + 256;
+}
+
+HsWs carve_hs(char *base, int64_t n, int64_t E, int L)
+{
+    HsWs w;
+    w.EL = E * L;
+    w.stride = (E + 64) & ~(int64_t)63;
+    size_t off = 0;
+    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += align256(b); return p; };
+    w.head_bytes = 256 + (w.EL + 2 * w.stride) * (int64_t)sizeof(int32_t);
+    char *head = take((size_t)w.head_bytes);
+    w.status = reinterpret_cast<int32_t *>(head);
+    w.cnt = head ? reinterpret_cast<int32_t *>(head + 256) : nullptr;
+    w.gpc = w.cnt ? w.cnt + w.EL : nullptr;
+    auto i32 = [&](int64_t k) { return reinterpret_cast<int32_t *>(take((size_t)k * 4)); };
+    w.evt = i32(n);
+    w.kept = i32(n);
+    w.gf = i32(n);
+    w.gx = i32(n + 1);
+    w.sf = i32(n);
+    w.sx = i32(n + 1);
+    w.gst = i32(n + 1);
+    w.gnl = i32(n);
+    w.gev = i32(n);
+    w.ok = i32(E);
+    w.sptr = i32(E + 1);
+    w.tbase = i32(E + 1);
+    w.trk = i32(n);
+    w.sev = i32(n);
+    w.boff = i32(w.EL + 1);
+    w.ka = reinterpret_cast<u64 *>(take((size_t)n * 8));
+    w.kb = reinterpret_cast<u64 *>(take((size_t)n * 8));
+    w.va = i32(n);
+    w.vb = i32(n);
+    w.leta = reinterpret_cast<float *>(take((size_t)n * 4));
+    w.lphi = reinterpret_cast<float *>(take((size_t)n * 4));
+    w.teta = reinterpret_cast<float *>(take((size_t)n * 4));
+    w.sums = i32(scan_sums_words(max(max(n, w.EL), E)));
+    w.temp_bytes = n > 0 ? sort_temp_bytes(n) : 0;
+    w.temp = take(w.temp_bytes);
+    w.bytes = off + 256;
+    return w;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_key(const float *__restrict__ r, const float *__restrict__ phi,
+                                                   const float *__restrict__ z, const int32_t *__restrict__ layer,
+                                                   const int64_t *__restrict__ pid, int64_t n,
+                                                   const int64_t *__restrict__ ep, int64_t E, int L,
+                                                   int32_t *__restrict__ evt, int32_t *__restrict__ kept,
+                                                   u64 *__restrict__ ka, int32_t *__restrict__ va,
+                                                   int32_t *__restrict__ status)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < E && (ep[i] > ep[i + 1] || (i == 0 && (ep[0] != 0 || ep[E] != n)))) atomicOr(status, kStatusEvents);
+    if (i >= n) return;
+    int64_t lo = 0, hi = E;                            // the event: the largest e with ep[e] <= i
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ep[mid] <= i) lo = mid; else hi = mid;
+    }
+    const int l = layer[i];
+    int e = (int)lo;
+    if (l < 0 || l >= L) {
+        atomicOr(status, kStatusLayer);
+        e = (int)E;                                    // in no event: never kept, never a sample
+    } else if (!(isfinite(r[i]) && isfinite(phi[i]) && isfinite(z[i]))) {
+        atomicOr(status, kStatusFinite);
+        e = (int)E;
+    } else if (!(ep[lo] <= i && i < ep[lo + 1])) {
+        e = (int)E;                                    // (flagged above: event_ptr is malformed)
+    }
+    evt[i] = e;
+    kept[i] = 0;
+    ka[i] = (u64)pid[i] ^ 0x8000000000000000ull;       // signed order
+    va[i] = (int)i;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_evkey(int64_t n, const int32_t *__restrict__ evt,
+                                                     const int32_t *__restrict__ rows, u64 *__restrict__ key)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) key[i] = (u64)evt[rows[i]];
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_gflag(int64_t n, const int32_t *__restrict__ evt,
+                                                     const int64_t *__restrict__ pid, const int32_t *__restrict__ rows,
+                                                     int32_t *__restrict__ gf)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int a = rows[i];
+    int f = 1;
+    if (i > 0) {
+        const int b = rows[i - 1];
+        f = evt[a] != evt[b] || pid[a] != pid[b];
+    }
+    gf[i] = f;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_layerkey(int64_t n, int L, const int32_t *__restrict__ layer,
+                                                        const int32_t *__restrict__ rows, const int32_t *__restrict__ gx,
+                                                        u64 *__restrict__ key, int32_t *__restrict__ val)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int row = rows[i];
+    const int l = layer[row];
+    key[row] = ((u64)(gx[i + 1] - 1) << 6) | (u64)(l >= 0 && l < L ? l : 0);
+    val[row] = row;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_gstart(int64_t n, const u64 *__restrict__ key, int32_t *__restrict__ gst)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = (int64_t)(key[i] >> 6);
+    if (i == 0 || (int64_t)(key[i - 1] >> 6) != g) gst[g] = (int)i;
+    if (i == n - 1) gst[g + 1] = (int)n;
+}
+
+// one lane per (event, pid) group: its hits are stored layer by layer, each layer's in frame order
+__global__ __launch_bounds__(kBlock) void k_hs_walk(int64_t n, int64_t E, int L, const int32_t *__restrict__ gx,
+                                                    const int32_t *__restrict__ gst, const u64 *__restrict__ key,
+                                                    const int32_t *__restrict__ rows, const int32_t *__restrict__ evt,
+                                                    const float *__restrict__ r, int32_t *__restrict__ kept,
+                                                    int32_t *__restrict__ cnt, int32_t *__restrict__ gnl,
+                                                    int32_t *__restrict__ gev)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= gx[n]) return;
+    const int p0 = gst[g], p1 = gst[g + 1];
+    const int e = evt[rows[p0]];
+    int runs = 0;
+    if (e < E) {
+        int best = -1, lay = -1;
+        float rb = 0.f;
+        for (int p = p0; p <= p1; ++p) {
+            const int l = p < p1 ? (int)(key[p] & 63) : -1;
+            if (l != lay) {                            // a layer's run ends: its hit of smallest r is kept
+                if (best >= 0) {
+                    kept[best] = 1;
+                    atomicAdd(cnt + (int64_t)e * L + lay, 1);
+                    ++runs;
+                }
+                if (p == p1) break;
+                lay = l;
+                best = rows[p];
+                rb = r[best];
+            } else {
+                const int row = rows[p];
+                if (r[row] < rb) {                     // idxmin: the first in frame order on ties
+                    best = row;
+                    rb = r[row];
+                }
+            }
+        }
+    }
+    gnl[g] = runs;
+    gev[g] = e;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_event(int64_t E, int L, int K, const int32_t *__restrict__ cnt,
+                                                     int32_t *__restrict__ ok)
+{
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e >= E) return;
+    int good = 1;
+    for (int l = 0; l < L; ++l) {
+        const int c = cnt[e * L + l];
+        good &= c == 0 || c > K;                       // cell 5: a present layer needs more than K hits
+    }
+    ok[e] = good;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_sflag(int64_t n, int64_t E, int L, const int32_t *__restrict__ gx,
+                                                     const int32_t *__restrict__ gnl, const int32_t *__restrict__ gev,
+                                                     const int32_t *__restrict__ ok, int32_t *__restrict__ sf,
+                                                     int32_t *__restrict__ ecnt)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= n) return;
+    int f = 0;
+    if (g < gx[n]) {
+        const int e = gev[g];
+        f = e < E && gnl[g] == L && ok[e];
+        if (f) atomicAdd(ecnt + e, 1);
+    }
+    sf[g] = f;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_etask(int64_t E, int64_t stride, int32_t *__restrict__ gpc)
+{
+    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (e < E) gpc[stride + e] = (gpc[e] + kFB - 1) / kFB;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_track(int64_t n, int L, const int32_t *__restrict__ gx,
+                                                     const int32_t *__restrict__ sf, const int32_t *__restrict__ sx,
+                                                     const int32_t *__restrict__ gst, const u64 *__restrict__ key,
+                                                     const int32_t *__restrict__ rows, const float *__restrict__ r,
+                                                     const float *__restrict__ z, const int32_t *__restrict__ gev,
+                                                     int32_t *__restrict__ trk, float *__restrict__ teta,
+                                                     int32_t *__restrict__ sev)
+{
+    const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= gx[n] || !sf[g]) return;
+    const int64_t s = sx[g];
+    const int p0 = gst[g], p1 = gst[g + 1];
+    int best = -1, lay = -1;
+    float rb = 0.f;
+    for (int p = p0; p <= p1; ++p) {                   // the walk of k_hs_walk again: the kept hit of every layer
+        const int l = p < p1 ? (int)(key[p] & 63) : -1;
+        if (l != lay) {
+            if (best >= 0) {
+                trk[s * L + lay] = best;
+                teta[s * L + lay] = (float)eta64(r[best], z[best]);   // pandas: float32(lay_eta) - float32(trk_eta)
+            }
+            if (p == p1) break;
+            lay = l;
+            best = rows[p];
+            rb = r[best];
+        } else if (r[rows[p]] < rb) {
+            best = rows[p];
+            rb = r[best];
+        }
+    }
+    sev[s] = gev[g];
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_bucketkey(int64_t n, int64_t E, int L, const int32_t *__restrict__ evt,
+                                                         const int32_t *__restrict__ layer,
+                                                         const int32_t *__restrict__ kept, u64 *__restrict__ key,
+                                                         int32_t *__restrict__ val)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int e = evt[i];
+    key[i] = (kept[i] && e < E) ? (u64)e * L + layer[i] : (u64)E * L;
+    val[i] = (int)i;
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_stage(int64_t EL, const int32_t *__restrict__ boff,
+                                                     const int32_t *__restrict__ rows, const float *__restrict__ r,
+                                                     const float *__restrict__ phi, const float *__restrict__ z,
+                                                     float *__restrict__ leta, float *__restrict__ lphi)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= boff[EL]) return;
+    const int row = rows[p];
+    leta[p] = eta32(r[row], z[row]);
+    lphi[p] = phi[row];
+}
+
+__global__ void k_hs_final(int64_t n, int64_t E, int L, int K, const int32_t *__restrict__ gx,
+                           const int32_t *__restrict__ sx, const int32_t *__restrict__ boff,
+                           const int32_t *__restrict__ tbase, const int32_t *__restrict__ status,
+                           gnn_hit_samples_sizes_t *sizes)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int64_t S = n > 0 ? sx[n] : 0;
+    const int64_t hits = S * L * K, segs = S * K * K * (L - 1);
+    sizes->n_samples = S;
+    sizes->n_hits = hits;
+    sizes->n_segments = segs;
+    sizes->n_kept = n > 0 ? boff[E * L] : 0;
+    sizes->n_groups = n > 0 ? gx[n] : 0;
+    sizes->n_tasks = (int64_t)tbase[E] * L;
+    sizes->status = *status | (hits >= ((int64_t)1 << 31) || segs >= ((int64_t)1 << 31) ? kStatusInt32 : 0);
+}
+
+// cells 9 and 15 for one (event, block of samples, layer) per task: d = sqrt(deta^2 + dphi^2) in float32, the K
+// smallest in ascending d (the first in frame order on equal d), then the features of each
+template <int K>
+__global__ __launch_bounds__(kFB) void k_hs_fill(int64_t n_tasks, int L, int n_seed, int64_t E,
+                                                 const int32_t *__restrict__ tbase, const int32_t *__restrict__ sptr,
+                                                 const int32_t *__restrict__ trk, const float *__restrict__ tet,
+                                                 const int32_t *__restrict__ boff,
+                                                 const int32_t *__restrict__ lrow, const float *__restrict__ leta,
+                                                 const float *__restrict__ lphi, const float *__restrict__ r,
+                                                 const float *__restrict__ phi, const float *__restrict__ z,
+                                                 const int64_t *__restrict__ pid, double sc_r, double sc_phi,
+                                                 double sc_z, float *__restrict__ X, float *__restrict__ y,
+                                                 int64_t *__restrict__ hit_index)
+{
+    __shared__ float se[kTile], sp[kTile];
+    for (int64_t t = blockIdx.x; t < n_tasks; t += gridDim.x) {
+        const int64_t tb = t / L;
+        const int l = (int)(t - tb * L);
+        int64_t lo = 0, hi = E;                        // the event: the largest e with tbase[e] <= tb
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (tbase[mid] <= tb) lo = mid; else hi = mid;
+        }
+        const int64_t e = lo;
+        const int64_t s = sptr[e] + (tb - tbase[e]) * kFB + threadIdx.x;
+        const bool valid = s < sptr[e + 1];
+        float teta = 0.f, tphi = 0.f;
+        int trow = 0;
+        if (valid) {
+            trow = trk[s * L + l];
+            teta = tet[s * L + l];
+            tphi = phi[trow];
+        }
+        uint32_t dk[K], sk[K];
+        int pk[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            dk[k] = kNoKey;
+            sk[k] = kNoKey;
+            pk[k] = -1;
+        }
+        const int64_t b = e * L + l;
+        const int b0 = boff[b], m = boff[b + 1] - b0;
+        for (int t0 = 0; t0 < m; t0 += kTile) {
+            const int mt = min(kTile, m - t0);
+            __syncthreads();                           // the previous tile has been read
+            for (int k = threadIdx.x; k < mt; k += kFB) {
+                se[k] = leta[b0 + t0 + k];
+                sp[k] = lphi[b0 + t0 + k];
+            }
+            __syncthreads();
+            if (valid) {
+                for (int k = 0; k < mt; ++k) {
+                    const float deta = se[k] - teta;
+                    const float dphi = wrap_dphi(sp[k] - tphi);
+                    const float s2 = deta * deta + dphi * dphi;
+                    const uint32_t ks = dkey(s2);
+                    if (ks >= sk[K - 1]) continue;     // sqrt is monotone: d >= the last d, which came earlier
+                    const uint32_t kd = dkey(sqrtf(s2));
+                    if (kd >= dk[K - 1]) continue;     // an equal d later in frame order loses
+                    dk[K - 1] = kd;
+                    sk[K - 1] = ks;
+                    pk[K - 1] = t0 + k;
+#pragma unroll
+                    for (int j = K - 1; j > 0; --j) {
+                        if (dk[j] < dk[j - 1]) {
+                            const uint32_t a = dk[j], c = sk[j];
+                            const int q = pk[j];
+                            dk[j] = dk[j - 1]; sk[j] = sk[j - 1]; pk[j] = pk[j - 1];
+                            dk[j - 1] = a; sk[j - 1] = c; pk[j - 1] = q;
+                        }
+                    }
+                }
+            }
+        }
+        if (!valid) continue;
+        const int64_t spid = pid[trow];
+        const float phi0 = phi[trk[s * L]];            // cell 15: phi centred on the track's first hit
+        const bool seed = l < n_seed;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (pk[k] < 0) continue;                   // (a present layer has more than K hits: never)
+            const int row = lrow[b0 + pk[k]];
+            const int64_t o = (s * L + l) * K + k;
+            const float lab = pid[row] == spid ? 1.0f : 0.0f;
+            const float pc = wrap_dphi(phi[row] - phi0);
+            float4 v;
+            v.x = (float)((double)r[row] / sc_r);      // cell 15: the DataFrame / float64 array, then float32
+            v.y = (float)((double)pc / sc_phi);
+            v.z = (float)((double)z[row] / sc_z);
+            v.w = seed ? lab : 0.0f;
+            reinterpret_cast<float4 *>(X)[o] = v;
+            y[o] = lab;
+            hit_index[o] = row;
+        }
+    }
+}
+
+// cell 15's adj_idx: np.where over (a, b) with layer[b] - layer[a] == 1 in row-major order; Ro = a, Ri = b
+__global__ __launch_bounds__(kBlock) void k_hs_segments(int64_t n_seg, int L, int K, int32_t *__restrict__ src,
+                                                        int32_t *__restrict__ dst)
+{
+    const int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= n_seg) return;
+    const int64_t per = (int64_t)K * K * (L - 1);
+    const int64_t s = q / per;
+    const int e = (int)(q - s * per);
+    const int l = e / (K * K), i = (e / K) % K, j = e % K;
+    const int64_t base = s * L * K;
+    src[q] = (int32_t)(base + l * K + i);
+    dst[q] = (int32_t)(base + (l + 1) * K + j);
+}
+
+__global__ __launch_bounds__(kBlock) void k_hs_keys(int64_t S, int L, const int32_t *__restrict__ trk,
+                                                    const int32_t *__restrict__ sev, const int64_t *__restrict__ pid,
+                                                    int64_t *__restrict__ keys)
+{
+    const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (s >= S) return;
+    keys[2 * s] = sev[s];
+    keys[2 * s + 1] = pid[trk[s * L]];
+}
+
+int check_args(const char *who, int64_t n_hits, int64_t n_events, int32_t L, int32_t K)
+{
+    if (n_hits < 0 || n_events < 1 || L < 1 || K < 1)
+        return fail(GNN_ERR_BADARG, "%s: bad argument (n_hits %lld, n_events %lld, n_det_layers %d, n_layer_hits %d)",
+                    who, (long long)n_hits, (long long)n_events, L, K);
+    if (L > kMaxL || K > kMaxK)
+        return fail(GNN_ERR_BADARG, "%s: n_det_layers %d > %d or n_layer_hits %d > %d", who, L, kMaxL, K, kMaxK);
+    if (n_hits >= ((int64_t)1 << 31) - 1 || n_events * L >= ((int64_t)1 << 31) - 1)
+        return fail(GNN_ERR_UNSUPPORTED, "%s: sizes outside the int32 index range", who);
+    return 0;
+}
+
+char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
+
+template <int K>
+int launch_fill(unsigned grid, hipStream_t s, int64_t n_tasks, int L, int n_seed, int64_t E, const HsWs &w,
+                const float *r, const float *phi, const float *z, const int64_t *pid, double sc_r, double sc_phi,
+                double sc_z, float *X, float *y, int64_t *hit_index)
+{
+    GNN_LAUNCH("k_hs_fill", k_hs_fill<K>, grid, kFB, s, n_tasks, L, n_seed, E, w.tbase, w.sptr, w.trk, w.teta, w.boff, w.va,
+               w.leta, w.lphi, r, phi, z, pid, sc_r, sc_phi, sc_z, X, y, hit_index);
+    return 0;
+}
+
+int fill_any(int K, unsigned grid, hipStream_t s, int64_t n_tasks, int L, int n_seed, int64_t E, const HsWs &w,
+             const float *r, const float *phi, const float *z, const int64_t *pid, double sc_r, double sc_phi,
+             double sc_z, float *X, float *y, int64_t *hit_index)
+{
+    switch (K) {                                       // the top-K list is unrolled at compile time
+#define HS_K(k) \
+    case k: return launch_fill<k>(grid, s, n_tasks, L, n_seed, E, w, r, phi, z, pid, sc_r, sc_phi, sc_z, X, y, hit_index);
+        HS_K(1) HS_K(2) HS_K(3) HS_K(4) HS_K(5) HS_K(6) HS_K(7) HS_K(8)
+        HS_K(9) HS_K(10) HS_K(11) HS_K(12) HS_K(13) HS_K(14) HS_K(15) HS_K(16)
+#undef HS_K
+    }
+    return fail(GNN_ERR_BADARG, "n_layer_hits %d outside [1, %d]", K, kMaxK);
+}
+
+#define HS_SORT(WHAT, KIN, KOUT, VIN, VOUT, BITS)                                                                     \
+    do {                                                                                                              \
+        size_t tb_ = 0;                                                                                               \
+        hipError_t e_ = rocprim::radix_sort_pairs(nullptr, tb_, (const u64 *)(KIN), (KOUT), (const int32_t *)(VIN),   \
+                                                  (VOUT), (size_t)n, 0u, (unsigned)(BITS), s, false);                 \
+        if (e_ == hipSuccess && tb_ > w.temp_bytes) e_ = hipErrorInvalidValue;                                        \
+        tb_ = w.temp_bytes;                                                                                           \
+        if (e_ == hipSuccess) e_ = rocprim::radix_sort_pairs(w.temp, tb_, (const u64 *)(KIN), (KOUT), (const int32_t *)(VIN),   \
+                                                  (VOUT), (size_t)n, 0u, (unsigned)(BITS), s, false);                 \
+        if (e_ != hipSuccess) return fail(-(int)e_, "gnn_hit_samples_sizes: radix sort %s: %s", WHAT,                \
+                                          hipGetErrorString(e_));                                                     \
+    } while (0)
+
+}  // namespace
+}  // namespace gnn
+
+using namespace gnn;
+
+extern "C" {
+
+size_t gnn_hit_samples_workspace_bytes(int64_t n_hits, int64_t n_events, int32_t n_det_layers, int32_t n_layer_hits)
+{
+    if (check_args("gnn_hit_samples_workspace_bytes", n_hits, n_events, n_det_layers, n_layer_hits)) return 0;
+    return carve_hs(nullptr, n_hits, n_events, n_det_layers).bytes;
+}
+
+int gnn_hit_samples_sizes(const float *r, const float *phi, const float *z, const int32_t *layer,
+                          const int64_t *particle_id, int64_t n_hits, const int64_t *event_ptr, int64_t n_events,
+                          int32_t n_det_layers, int32_t n_layer_hits, void *workspace, size_t workspace_bytes,
+                          gnn_hit_samples_sizes_t *sizes_out, void *stream)
+{
+    ProfChain chain_;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = check_args("gnn_hit_samples_sizes", n_hits, n_events, n_det_layers, n_layer_hits)) return rc;
+    if ((n_hits > 0 && (!r || !phi || !z || !layer || !particle_id)) || !event_ptr || !sizes_out)
+        return fail(GNN_ERR_BADARG, "gnn_hit_samples_sizes: pointer missing");
+    const int64_t n = n_hits, E = n_events;
+    const int L = n_det_layers, K = n_layer_hits;
+    const size_t need = carve_hs(nullptr, n, E, L).bytes;
+    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    HsWs w = carve_hs(align_ws(workspace), n, E, L);
+    hipError_t err = hipMemsetAsync(w.status, 0, (size_t)w.head_bytes, s);
+    if (err == hipSuccess) err = hipMemsetAsync(sizes_out, 0, sizeof(gnn_hit_samples_sizes_t), s);
+    if (err != hipSuccess) return fail(-(int)err, "gnn_hit_samples_sizes: memset failed: %s", hipGetErrorString(err));
+    GNN_LAUNCH("k_hs_key", k_hs_key, max(grid_for(max(n, E)), 1u), kBlock, s, r, phi, z, layer, particle_id, n,
+               event_ptr, E, L, w.evt, w.kept, w.ka, w.va, w.status);
+    if (n > 0) {
+        // (event, pid, row) order: pid first, then a stable sort by event
+        HS_SORT("by particle", w.ka, w.kb, w.va, w.vb, 64);
+        GNN_LAUNCH("k_hs_evkey", k_hs_evkey, grid_for(n), kBlock, s, n, w.evt, w.vb, w.ka);
+        HS_SORT("by event", w.ka, w.kb, w.vb, w.va, bits_for(E));
+        GNN_LAUNCH("k_hs_gflag", k_hs_gflag, grid_for(n), kBlock, s, n, w.evt, particle_id, w.va, w.gf);
+        if (int rc = scan_counts(w.gf, 0, 1, w.gx, nullptr, n, w.sums, s)) return rc;
+        // each group layer by layer, frame order within a layer
+        GNN_LAUNCH("k_hs_layerkey", k_hs_layerkey, grid_for(n), kBlock, s, n, L, layer, w.va, w.gx, w.ka, w.vb);
+        HS_SORT("by group and layer", w.ka, w.kb, w.vb, w.va, 6 + bits_for(n));
+        GNN_LAUNCH("k_hs_gstart", k_hs_gstart, grid_for(n), kBlock, s, n, w.kb, w.gst);
+        GNN_LAUNCH("k_hs_walk", k_hs_walk, grid_for(n), kBlock, s, n, E, L, w.gx, w.gst, w.kb, w.va, w.evt, r, w.kept,
+                   w.cnt, w.gnl, w.gev);
+    }
+    GNN_LAUNCH("k_hs_event", k_hs_event, grid_for(E), kBlock, s, E, L, K, w.cnt, w.ok);
+    if (n > 0) {
+        GNN_LAUNCH("k_hs_sflag", k_hs_sflag, grid_for(n), kBlock, s, n, E, L, w.gx, w.gnl, w.gev, w.ok, w.sf, w.gpc);
+        if (int rc = scan_counts(w.sf, 0, 1, w.sx, nullptr, n, w.sums, s)) return rc;
+    }
+    GNN_LAUNCH("k_hs_etask", k_hs_etask, grid_for(E), kBlock, s, E, w.stride, w.gpc);
+    if (int rc = scan_counts(w.gpc, w.stride, 2, w.sptr, w.tbase, E, w.sums, s)) return rc;
+    if (n > 0) {
+        GNN_LAUNCH("k_hs_track", k_hs_track, grid_for(n), kBlock, s, n, L, w.gx, w.sf, w.sx, w.gst, w.kb, w.va, r,
+                   z, w.gev, w.trk, w.teta, w.sev);
+        // the kept hits of every (event, layer) in frame order
+        GNN_LAUNCH("k_hs_bucketkey", k_hs_bucketkey, grid_for(n), kBlock, s, n, E, L, w.evt, layer, w.kept, w.ka,
+                   w.vb);
+        HS_SORT("by event and layer", w.ka, w.kb, w.vb, w.va, bits_for(w.EL));
+    }
+    if (int rc = scan_counts(w.cnt, 0, 1, w.boff, nullptr, w.EL, w.sums, s)) return rc;
+    if (n > 0)
+        GNN_LAUNCH("k_hs_stage", k_hs_stage, grid_for(n), kBlock, s, w.EL, w.boff, w.va, r, phi, z, w.leta, w.lphi);
+    GNN_LAUNCH("k_hs_final", k_hs_final, 1, 64, s, n, E, L, K, w.gx, w.sx, w.boff, w.tbase, w.status, sizes_out);
+    return 0;
+}
+
+int gnn_hit_samples_fill(const float *r, const float *phi, const float *z, const int64_t *particle_id, int64_t n_hits,
+                         int64_t n_events, int32_t n_det_layers, int32_t n_layer_hits, int32_t n_seed_layers,
+                         double scale_r, double scale_phi, double scale_z, const gnn_hit_samples_sizes_t *sizes,
+                         void *workspace, size_t workspace_bytes, float *X, float *y, int64_t *hit_index,
+                         int32_t *src, int32_t *dst, int64_t *keys, void *stream)
+{
+    ProfChain chain_;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = check_args("gnn_hit_samples_fill", n_hits, n_events, n_det_layers, n_layer_hits)) return rc;
+    const int64_t n = n_hits, E = n_events;
+    const int L = n_det_layers, K = n_layer_hits;
+    if (!sizes || sizes->status != 0 || sizes->n_samples < 0 || sizes->n_samples * L > n ||
+        sizes->n_hits != sizes->n_samples * L * K || sizes->n_segments != sizes->n_samples * K * K * (L - 1) ||
+        sizes->n_hits >= ((int64_t)1 << 31) || sizes->n_segments >= ((int64_t)1 << 31) || sizes->n_tasks < 0 ||
+        sizes->n_tasks > ((sizes->n_samples + kFB - 1) / kFB + E) * L)
+        return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: sizes missing, flagged or not from this input");
+    if (n_seed_layers < 0) return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: n_seed_layers < 0");
+    const int64_t S = sizes->n_samples;
+    if (S == 0) return 0;
+    if (!r || !phi || !z || !particle_id || !X || !y || !hit_index || !keys || (sizes->n_segments > 0 && (!src || !dst)))
+        return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: pointer missing");
+    if (!(scale_r != 0.0 && scale_phi != 0.0 && scale_z != 0.0))
+        return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: a feature scale is zero or NaN");
+    const size_t need = carve_hs(nullptr, n, E, L).bytes;
+    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    HsWs w = carve_hs(align_ws(workspace), n, E, L);
+    const unsigned grid = (unsigned)min(sizes->n_tasks, (int64_t)device_cus() * kFillWgPerCu);
+    if (grid > 0)
+        if (int rc = fill_any(K, grid, s, sizes->n_tasks, L, n_seed_layers, E, w, r, phi, z, particle_id, scale_r,
+                              scale_phi, scale_z, X, y, hit_index))
+            return rc;
+    if (sizes->n_segments > 0)
+        GNN_LAUNCH("k_hs_segments", k_hs_segments, grid_for(sizes->n_segments), kBlock, s, sizes->n_segments, L, K,
+                   src, dst);
+    GNN_LAUNCH("k_hs_keys", k_hs_keys, grid_for(S), kBlock, s, S, L, w.trk, w.sev, particle_id, keys);
+    return 0;
+}
+
+}  // extern "C"

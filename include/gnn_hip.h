@@ -426,6 +426,45 @@ int gnn_graph_build_fill(const int64_t *particle_id, int64_t n_hits, int64_t n_e
                          const gnn_graph_build_sizes_t *sizes, void *workspace, size_t workspace_bytes, float *X,
                          int32_t *src, int32_t *dst, float *y, int64_t *hit_index, void *stream);
 
+/* ---- the hit classifier's track samples from detector hits, built on the GPU (csrc/hit_samples.hip; ABI 7) ---------
+ * Replaces the sample preparation of gnn/MPNN_HitClassifier.ipynb on the host in pandas: the deduplication of
+ * select_hits (cell 5), select_signal_hits (cells 5 and 10), the signal keys (cell 11), the constants and arrays of
+ * cells 12 and 14 and the per-sample loop of cell 15 with calc_eta / calc_dphi / calc_eta_phi_distance (cell 9).
+ * gnn-fpga_amd/hit_samples.py is the numpy specification.  Two calls around ONE host read-back of the sizes:
+ *   gnn_hit_samples_sizes  deduplication, event and track selection, sample numbering, kept hits grouped per
+ *                          (event, layer) in frame order -> *sizes_out (DEVICE memory, written asynchronously)
+ *   gnn_hit_samples_fill   X, y, hit_index, src, dst, keys into arrays the caller allocated from a HOST copy of the
+ *                          sizes (the same workspace, not touched in between)
+ * Inputs (DEVICE): r, phi, z float32 [n_hits], layer int32 [n_hits] (barrel layers already renumbered),
+ * particle_id int64 [n_hits], event_ptr int64 [n_events + 1] (event e owns rows [event_ptr[e], event_ptr[e+1])).
+ * L = n_det_layers <= 64, K = n_layer_hits <= 16 (GNN_ERR_BADARG otherwise).  Per (event, particle, layer) the hit of
+ * smallest r is kept (the first row on ties); an event is dropped when a layer present in it has <= K kept hits; a
+ * sample is an (event, particle) whose kept hits cover all L layers, numbered in ascending (event, particle_id).
+ * Sample s owns hits [s L K, (s + 1) L K) of X [., 4] (r, phi - phi of its layer-0 hit wrapped to [-pi, pi], z, each
+ * float32(float64(v) / scale), then the label on layers < n_seed_layers, 0 elsewhere), y (float32 label: the
+ * candidate's particle is the sample's) and hit_index (input row, int64), layer-major, on each layer the K hits
+ * nearest its own hit by d = sqrt(deta^2 + dphi^2) (float32, the track hit's eta in float64) in ascending d, the
+ * first in frame order on equal d; segments [s K^2 (L-1), ...) of src (inner hit) and dst (outer hit) int32 in batch
+ * numbering, every adjacent-layer pair in np.where order; keys [n_samples][2] int64 (event, particle_id).
+ * sizes.status (0 = fine): bit 1 a layer outside [0, L), bit 2 more than 2^31 - 1 sample hits or segments, bit 4
+ * event_ptr not non-decreasing from 0 to n_hits, bit 8 a non-finite r, phi or z; gnn_hit_samples_fill refuses
+ * flagged sizes.  The output is the same in every run (no order decided by atomics). */
+typedef struct gnn_hit_samples_sizes {
+    int64_t n_samples, n_hits, n_segments;      /* samples; sample hits n_samples L K; segments n_samples K^2 (L-1) */
+    int64_t n_kept, n_groups, n_tasks, status;  /* kept hits; (event, particle) pairs; fill work items             */
+} gnn_hit_samples_sizes_t;
+
+size_t gnn_hit_samples_workspace_bytes(int64_t n_hits, int64_t n_events, int32_t n_det_layers, int32_t n_layer_hits);
+int gnn_hit_samples_sizes(const float *r, const float *phi, const float *z, const int32_t *layer,
+                          const int64_t *particle_id, int64_t n_hits, const int64_t *event_ptr, int64_t n_events,
+                          int32_t n_det_layers, int32_t n_layer_hits, void *workspace, size_t workspace_bytes,
+                          gnn_hit_samples_sizes_t *sizes_out, void *stream);
+int gnn_hit_samples_fill(const float *r, const float *phi, const float *z, const int64_t *particle_id, int64_t n_hits,
+                         int64_t n_events, int32_t n_det_layers, int32_t n_layer_hits, int32_t n_seed_layers,
+                         double scale_r, double scale_phi, double scale_z, const gnn_hit_samples_sizes_t *sizes,
+                         void *workspace, size_t workspace_bytes, float *X, float *y, int64_t *hit_index,
+                         int32_t *src, int32_t *dst, int64_t *keys, void *stream);
+
 /* ---- scoring a classifier: confusion counts, score histograms (csrc/metrics.hip; ABI 7) ----------------------------
  * Stands in for the evaluation cells of the reference's notebooks (gnn/MPNN_Seg_ACTS*.ipynb, makeROC and the
  * per-sample cells), which flatten Estimator.predict's scores (gnn/estimator.py:137-146) and call sklearn.metrics
