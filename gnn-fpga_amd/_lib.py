@@ -73,6 +73,21 @@ class GnnHitSamplesSizes(ctypes.Structure):
     _fields_ = [(n, _i64) for n in ("n_samples", "n_hits", "n_segments", "n_kept", "n_groups", "n_tasks", "status")]
 
 
+class GnnEmtfHits(ctypes.Structure):
+    _fields_ = [(n, _f) for n in ("z", "theta", "phi", "r", "bend", "tp1", "tp2", "station", "ring", "type",
+                                  "event_ptr")] + [("n_rows", _i64)]
+
+
+class GnnMuonGraphSizes(ctypes.Structure):
+    _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "max_graph_hits", "max_graph_segments",
+                                    "status")]
+
+
+class GnnMuonGraphOut(ctypes.Structure):
+    _fields_ = [(n, _f) for n in ("X", "src", "dst", "y", "hit_source", "hit_row", "entry", "pt", "eta", "flags",
+                                  "graph_hits", "graph_segments")]
+
+
 # name -> (restype, argtypes); must list every function include/gnn_hip.h declares
 SIGNATURES = {
     "gnn_abi_version": (ctypes.c_int, []),
@@ -142,6 +157,14 @@ SIGNATURES = {
     "gnn_hit_samples_fill": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, _i32, _i32, _i32, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_double, ctypes.POINTER(GnnHitSamplesSizes), _f,
                                             _sz, _f, _f, _f, _f, _f, _f, _f]),
+    "gnn_muon_graph_workspace_bytes": (_sz, [_i64]),
+    "gnn_muon_graph_sizes": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f,
+                                            _sz, _f, _f, _f, _f]),
+    "gnn_muon_graph_fill": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f, _f,
+                                           _i64, _i64, ctypes.POINTER(GnnMuonGraphSizes), _f, _sz,
+                                           ctypes.POINTER(GnnMuonGraphOut), _f]),
+    "gnn_muon_graph_padded": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f,
+                                             _f, _i64, _i64, _f, _sz, ctypes.POINTER(GnnMuonGraphOut), _f, _f]),
     "gnn_metrics_bins": (_i64, [_i32]),
     "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
@@ -935,6 +958,107 @@ def hit_samples_fill(ws, sizes, r, phi, z, particle_id, n_events, n_det_layers, 
             ws.numel(), X.data_ptr(), y.data_ptr(), hit_index.data_ptr(), src.data_ptr(), dst.data_ptr(),
             keys.data_ptr(), st))
     return X, y, hit_index, src, dst, keys
+
+
+def _emtf_hits(cols, n_rows):
+    """GnnEmtfHits of one source's validated device columns (muon_graph._columns)."""
+    h = GnnEmtfHits()
+    for field, name in (("z", "vh_sim_z"), ("theta", "vh_sim_theta"), ("phi", "vh_sim_phi"), ("r", "vh_sim_r")):
+        setattr(h, field, _dev(cols[name], torch.float32, name))
+    for field, name in (("bend", "vh_bend"), ("tp1", "vh_sim_tp1"), ("tp2", "vh_sim_tp2"), ("station", "vh_station"),
+                        ("ring", "vh_ring"), ("type", "vh_type")):
+        setattr(h, field, _dev(cols[name], torch.int32, name))
+    h.event_ptr = _dev(cols["event_ptr"], torch.int64, "event_ptr")
+    h.n_rows = n_rows
+    return h
+
+
+def _muon_graph_out(dev, n_hits, n_segments, n_graphs):
+    """Device arrays of one muon graph build and the GnnMuonGraphOut pointing at them."""
+    t = {"X": torch.empty((n_hits, 11), dtype=torch.float32, device=dev),
+         "src": torch.empty(n_segments, dtype=torch.int32, device=dev),
+         "dst": torch.empty(n_segments, dtype=torch.int32, device=dev),
+         "y": torch.empty(n_segments, dtype=torch.float32, device=dev),
+         "hit_source": torch.empty(n_hits, dtype=torch.int32, device=dev),
+         "hit_row": torch.empty(n_hits, dtype=torch.int64, device=dev),
+         "entry": torch.empty(n_graphs, dtype=torch.int64, device=dev),
+         "pt": torch.empty(n_graphs, dtype=torch.float32, device=dev),
+         "eta": torch.empty(n_graphs, dtype=torch.float32, device=dev),
+         "flags": torch.empty(n_graphs, dtype=torch.int32, device=dev),
+         "graph_hits": torch.empty(n_graphs, dtype=torch.int32, device=dev),
+         "graph_segments": torch.empty(n_graphs, dtype=torch.int32, device=dev)}
+    o = GnnMuonGraphOut()
+    for k, v in t.items():
+        setattr(o, k, v.data_ptr() if v.numel() else None)
+    return t, o
+
+
+def _muon_graphs(t, hit_ptr, seg_ptr, layout, entry_start, status=None, layout_ptrs=None):
+    from .hitgraph import HitGraphBatch
+    from .muon_graph import MG_GRAPH_PRESENT, MG_GRAPH_VP_MISSING, MG_GRAPH_WRITTEN, MuonGraphs
+    batch = HitGraphBatch._from_device_arrays(t["X"], t["src"], t["dst"], t["y"], hit_ptr, seg_ptr)
+    if layout_ptrs is not None:                  # the padded offsets, made on the device: nothing to upload later
+        batch._event[0]._both = layout_ptrs
+    f = t["flags"]
+    return MuonGraphs(batch, t["entry"], t["pt"], t["eta"], (f & MG_GRAPH_WRITTEN) != 0,
+                      (f & MG_GRAPH_VP_MISSING) != 0, t["hit_source"], t["hit_row"], layout=layout,
+                      present=(f & MG_GRAPH_PRESENT) != 0, n_hits=t["graph_hits"], n_segments=t["graph_segments"],
+                      status=status, entry_start=entry_start)
+
+
+def muon_graph_flat(mu, pu, n_entries, n_mu, n_pu, muon_only, vp, entry_start):
+    """The muon graph builder's two calls (csrc/muon_graph.hip) around ONE read-back of the sizes and offsets."""
+    from .muon_graph import _raise_status
+    dev = mu["vh_sim_z"].device
+    E = n_entries
+    need = int(load().gnn_muon_graph_workspace_bytes(E))
+    if need == 0:
+        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    nw = ctypes.sizeof(GnnMuonGraphSizes) // 8
+    out = torch.empty(nw + 2 * (E + 1), dtype=torch.int64, device=dev)
+    with _on(dev) as st:
+        hm, hp = _emtf_hits(mu, n_mu), _emtf_hits(pu, n_pu)
+        _check(load().gnn_muon_graph_sizes(ctypes.byref(hm), ctypes.byref(hp), E, int(muon_only), ws.data_ptr(),
+                                           ws.numel(), out.data_ptr(), out[nw:].data_ptr(),
+                                           out[nw + E + 1:].data_ptr(), st))
+        host = out.cpu().numpy()
+        sizes = GnnMuonGraphSizes()
+        ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnMuonGraphSizes))
+        _raise_status(int(sizes.status))
+        G = int(sizes.n_graphs)
+        t, o = _muon_graph_out(dev, int(sizes.n_hits), int(sizes.n_segments), G)
+        _check(load().gnn_muon_graph_fill(ctypes.byref(hm), ctypes.byref(hp), E, int(muon_only),
+                                          _dev(vp[0], torch.float32, "vp_pt"), _dev(vp[1], torch.float32, "vp_eta"),
+                                          int(vp[0].shape[0]), entry_start, ctypes.byref(sizes), ws.data_ptr(),
+                                          ws.numel(), ctypes.byref(o), st))
+    hit_ptr = host[nw:nw + G + 1].copy() if G else np.zeros(1, np.int64)
+    seg_ptr = host[nw + E + 1:nw + E + 2 + G].copy() if G else np.zeros(1, np.int64)
+    return _muon_graphs(t, hit_ptr, seg_ptr, "flat", entry_start)
+
+
+def muon_graph_padded(mu, pu, n_entries, n_mu, n_pu, muon_only, vp, entry_start):
+    """The padded build (gnn_muon_graph_padded): fixed slots, no read-back, no host synchronisation."""
+    from .muon_graph import MAX_GRAPH_HITS, MAX_GRAPH_SEGMENTS
+    dev = mu["vh_sim_z"].device
+    E = n_entries
+    need = int(load().gnn_muon_graph_workspace_bytes(E))
+    if need == 0:
+        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    t, o = _muon_graph_out(dev, E * MAX_GRAPH_HITS, E * MAX_GRAPH_SEGMENTS, E)
+    with _on(dev) as st:
+        hm, hp = _emtf_hits(mu, n_mu), _emtf_hits(pu, n_pu)
+        _check(load().gnn_muon_graph_padded(ctypes.byref(hm), ctypes.byref(hp), E, int(muon_only),
+                                            _dev(vp[0], torch.float32, "vp_pt"), _dev(vp[1], torch.float32, "vp_eta"),
+                                            int(vp[0].shape[0]), entry_start, ws.data_ptr(), ws.numel(),
+                                            ctypes.byref(o), status.data_ptr(), st))
+        step = torch.arange(E + 1, dtype=torch.int32, device=dev)
+        ptrs = torch.stack([step * MAX_GRAPH_HITS, step * MAX_GRAPH_SEGMENTS])
+    hit_ptr = np.arange(E + 1, dtype=np.int64) * MAX_GRAPH_HITS
+    seg_ptr = np.arange(E + 1, dtype=np.int64) * MAX_GRAPH_SEGMENTS
+    return _muon_graphs(t, hit_ptr, seg_ptr, "padded", entry_start, status=status, layout_ptrs=ptrs)
 
 
 def plan_build_fill(X, src, dst, n_hits, n_segments, chunk_segments, sizes, workspace, arrays):

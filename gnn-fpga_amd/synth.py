@@ -215,3 +215,79 @@ def hit_classifier_samples(n, seed=0, n_det_layers=10, n_layer_hits=5, n_seed_la
     Ri[:, dst, edge_idx] = 1
     Ro[:, src, edge_idx] = 1
     return HitSamples(X, Ri, Ro, y, src, dst)
+
+
+# EMTF chambers (vh_type, vh_station, vh_ring) with a LUT layer in gnn/prepareMuonGraphs.py:71-92, and the |z| and
+# r range (cm) a hit in them takes here: one endcap's CSC (type 1), RPC (2), GEM (3) and ME0 (4) chambers
+EMTF_CHAMBERS = (
+    (4, 1, 1, 540.0, 60.0, 150.0), (3, 1, 1, 567.0, 130.0, 260.0), (1, 1, 4, 600.0, 100.0, 150.0),
+    (1, 1, 1, 602.0, 150.0, 270.0), (1, 1, 2, 700.0, 275.0, 460.0), (1, 1, 3, 690.0, 505.0, 700.0),
+    (2, 1, 2, 705.0, 275.0, 460.0), (3, 2, 1, 795.0, 140.0, 320.0), (2, 2, 2, 800.0, 355.0, 700.0),
+    (1, 2, 1, 830.0, 140.0, 350.0), (1, 2, 2, 832.0, 355.0, 700.0), (1, 3, 1, 935.0, 160.0, 350.0),
+    (1, 3, 2, 937.0, 355.0, 700.0), (2, 3, 1, 970.0, 160.0, 350.0), (2, 3, 2, 972.0, 355.0, 520.0),
+    (2, 3, 3, 974.0, 520.0, 700.0), (1, 4, 1, 1025.0, 180.0, 350.0), (1, 4, 2, 1027.0, 355.0, 700.0),
+    (2, 4, 1, 1060.0, 180.0, 350.0), (2, 4, 2, 1062.0, 355.0, 520.0), (2, 4, 3, 1064.0, 520.0, 700.0))
+# (type, station, ring) inside the LUT's [0, 5)^3 that it maps to -99: DT chambers, RE1/3, RE2/3
+EMTF_NO_LAYER = ((0, 1, 1), (0, 2, 1), (0, 3, 2), (0, 4, 1), (2, 1, 3), (2, 2, 3))
+EMTF_INT_COLUMNS = ("vh_bend", "vh_sim_tp1", "vh_sim_tp2", "vh_station", "vh_ring", "vh_type")
+
+
+def _emtf_rows(rng, entry, chamber, side, r, phi, theta_deg, tp_rate, n_entries):
+    """Rows of one source, shuffled within each entry: columns of gnn/prepareMuonGraphs.py:169-170 + event_ptr."""
+    n = entry.shape[0]
+    ch = np.asarray(EMTF_CHAMBERS + tuple(t + (800.0, 100.0, 700.0) for t in EMTF_NO_LAYER))
+    z = side * (ch[chamber, 3] + rng.normal(0.0, 1.0, size=n))
+    tp = rng.random(size=(2, n)) < tp_rate
+    cols = {"vh_sim_z": z, "vh_sim_theta": theta_deg, "vh_sim_phi": np.mod(phi + np.pi, 2 * np.pi) - np.pi,
+            "vh_sim_r": r, "vh_bend": rng.integers(-40, 41, size=n),
+            "vh_sim_tp1": np.where(tp[0], rng.integers(1, 4, size=n), 0),
+            "vh_sim_tp2": np.where(tp[1], rng.integers(-3, 0, size=n), 0),
+            "vh_station": ch[chamber, 1], "vh_ring": ch[chamber, 2], "vh_type": ch[chamber, 0]}
+    order = np.lexsort((rng.random(size=n), entry))
+    out = {k: (v[order].astype(np.int32) if k in EMTF_INT_COLUMNS else v[order].astype(np.float32))
+           for k, v in cols.items()}
+    out["event_ptr"] = np.concatenate([[0], np.cumsum(np.bincount(entry, minlength=n_entries))]).astype(np.int64)
+    return out
+
+
+def emtf_events(n_entries, seed=0, n_pu=24.0, p_hit=0.9, max_dup=3, tp_rate=0.08, p_no_layer=0.05):
+    """Seeded stand-ins for the EMTF ntuple branches gnn/prepareMuonGraphs.py reads (:169-173), for
+    muon_graph.build_muon_graphs: a dict with `muon` and `pu` (the ten hit_features columns - float32 z, theta, phi,
+    r; int32 bend, tp1, tp2, station, ring, type - and event_ptr [n_entries + 1]) and `vp_pt`, `vp_eta` (float32,
+    one row per entry) with `vp_ptr`.
+
+    Muon entry e: one muon on one z side (eta in [1.2, 2.4], uniform phi) crosses every chamber of EMTF_CHAMBERS
+    whose r range holds z tan(theta), with probability p_hit each, and leaves 1 .. max_dup hits per chamber.  A
+    fraction tp_rate of the rows has tp1 or tp2 != 0, and p_no_layer of the rows sit in a chamber the LUT maps to
+    -99.  PU entry e: Poisson(n_pu) hits in random chambers on either side.  Rows are shuffled within an entry."""
+    rng = np.random.default_rng(seed)
+    ch = np.asarray(EMTF_CHAMBERS)
+    eta = rng.uniform(1.2, 2.4, size=n_entries)
+    theta = 2.0 * np.arctan(np.exp(-eta))
+    phi0 = rng.uniform(-np.pi, np.pi, size=n_entries)
+    side = np.where(rng.random(size=n_entries) < 0.5, -1.0, 1.0)
+    r_c = ch[None, :, 3] * np.tan(theta)[:, None]                          # [E, 21]
+    inside = (r_c >= ch[None, :, 4]) & (r_c <= ch[None, :, 5]) & (rng.random(size=r_c.shape) < p_hit)
+    ndup = np.where(inside, rng.integers(1, max_dup + 1, size=r_c.shape), 0)
+    entry = np.repeat(np.repeat(np.arange(n_entries), ch.shape[0]), ndup.ravel())
+    chamber = np.repeat(np.tile(np.arange(ch.shape[0]), n_entries), ndup.ravel())
+    bad = rng.random(size=entry.shape[0]) < p_no_layer
+    chamber = np.where(bad, ch.shape[0] + rng.integers(0, len(EMTF_NO_LAYER), size=entry.shape[0]), chamber)
+    n = entry.shape[0]
+    r = r_c[entry, np.minimum(chamber, ch.shape[0] - 1)] + rng.normal(0.0, 0.5, size=n)
+    muon = _emtf_rows(rng, entry, chamber, side[entry], r, phi0[entry] + rng.normal(0.0, 0.01, size=n),
+                      np.degrees(theta[entry]) + rng.normal(0.0, 0.05, size=n), tp_rate, n_entries)
+    npu = rng.poisson(n_pu, size=n_entries)
+    pe = np.repeat(np.arange(n_entries), npu)
+    m = pe.shape[0]
+    pch = np.where(rng.random(size=m) < p_no_layer, ch.shape[0] + rng.integers(0, len(EMTF_NO_LAYER), size=m),
+                   rng.integers(0, ch.shape[0], size=m))
+    lo = np.where(pch < ch.shape[0], ch[np.minimum(pch, ch.shape[0] - 1), 4], 100.0)
+    hi = np.where(pch < ch.shape[0], ch[np.minimum(pch, ch.shape[0] - 1), 5], 700.0)
+    pr = rng.uniform(lo, hi)
+    pside = np.where(rng.random(size=m) < 0.5, -1.0, 1.0)
+    pu = _emtf_rows(rng, pe, pch, pside, pr, rng.uniform(-np.pi, np.pi, size=m),
+                    np.degrees(np.arctan2(pr, 800.0)), 0.5, n_entries)
+    pt = 1.0 / rng.uniform(0.01, 0.5, size=n_entries)
+    return {"muon": muon, "pu": pu, "vp_pt": pt.astype(np.float32), "vp_eta": (side * eta).astype(np.float32),
+            "vp_ptr": np.arange(n_entries + 1, dtype=np.int64)}

@@ -465,6 +465,68 @@ int gnn_hit_samples_fill(const float *r, const float *phi, const float *z, const
                          void *workspace, size_t workspace_bytes, float *X, float *y, int64_t *hit_index,
                          int32_t *src, int32_t *dst, int64_t *keys, void *stream);
 
+/* ---- muon trigger graphs from EMTF hits, built on the GPU (csrc/muon_graph.hip; ABI 7) ------------------------------
+ * Replaces the reference's host graph preparation of the endcap muon trigger: gnn/prepareMuonGraphs.py main from the
+ * tree.pandas.df reads (:171-173) through save_graphs (:263) - the LUT layer (:49-92, :175-176), the cross-frame and
+ * truth filters (:178-192), the per-source deduplication and the mixing of PU into muon entries by ordinal (:193-232),
+ * the layer pairs from Python set order (:234-246), pt / eta (:254) - and gnn/Muon_graph.py construct_graph with its
+ * segment selection (:60-162).  gnn-fpga_amd/muon_graph.py is the numpy specification; the output is bit-identical.
+ *   gnn_muon_graph_sizes   checks, deduplication, ordinals, graph composition, kept-segment counts -> *sizes_out,
+ *                          hit_ptr, seg_ptr [n_entries + 1] (the first n_graphs + 1 used; DEVICE memory, written
+ *                          asynchronously on `stream`)
+ *   gnn_muon_graph_fill    the graphs into arrays the caller allocated from a HOST copy of the sizes (the same
+ *                          workspace, not touched in between)
+ *   gnn_muon_graph_padded  no read-back at all: graph slot e = entry e owns hits [42 e, 42 e + 42) and segments
+ *                          [441 e, 441 e + 441) (21 chambers per source survive the deduplication; the pairs form a
+ *                          bipartite graph over <= 42 hits); unused hits are X = 0 rows with hit_source = hit_row = -1,
+ *                          unused segments src = dst = -1 with y = 0; outputs sized n_entries; *status (DEVICE int32)
+ *                          receives the status word
+ * Inputs (DEVICE): per source (muon, PU) the ten hit_features columns of :169-170 and event_ptr [n_entries + 1]
+ * (entry e owns rows [event_ptr[e], event_ptr[e+1]), the subentry is the position in the entry); vp_pt, vp_eta
+ * float32 [n_vp] the flat vp rows.  Graph g (flat: ascending entry over the entries that have rows, including graphs
+ * with no layer pair) owns rows hit_ptr[g] .. hit_ptr[g+1] of X [., 11] (float32(column) for the ten features, then
+ * the LUT layer times sign(z), +0 for z = +-0), hit_source (0 = PU, 1 = muon) and hit_row (int64, the row in its source), in the
+ * reference's frame order; segments seg_ptr[g] .. seg_ptr[g+1] of src (l1 hit), dst (l2 hit) int32 in batch numbering
+ * and y = 1 iff both hits are muon rows, pair by pair, l1 hit by l1 hit, then by l2 hit; entry = entry_start + e,
+ * pt / eta = vp row e (NaN where e >= n_vp), flags bit 1 a graph (padded: the slot holds one), bit 2 written (the
+ * reference saves a file: at least one layer pair), bit 4 vp row missing; graph_hits, graph_segments per graph.
+ * status (0 = fine): bit 1 a type, station or ring outside [0, 5), bit 2 a non-finite z, bit 4 an event_ptr not
+ * non-decreasing from 0 to n_rows (or an entry of 2^31 rows or more); gnn_muon_graph_fill refuses flagged sizes.
+ * GNN_ERR_BADARG: null pointers, n_entries < 1; GNN_ERR_UNSUPPORTED: more than (2^31 - 1) / 441 entries.  The output
+ * is the same in every run (no order decided by atomics). */
+typedef struct gnn_emtf_hits {
+    const float *z, *theta, *phi, *r;           /* vh_sim_z, vh_sim_theta, vh_sim_phi, vh_sim_r [n_rows]           */
+    const int32_t *bend, *tp1, *tp2, *station, *ring, *type;   /* vh_bend, vh_sim_tp1, vh_sim_tp2, vh_station, ... */
+    const int64_t *event_ptr;                   /* [n_entries + 1]                                                  */
+    int64_t n_rows;
+} gnn_emtf_hits_t;
+
+typedef struct gnn_muon_graph_sizes {
+    int64_t n_graphs, n_hits, n_segments, max_graph_hits, max_graph_segments, status;
+} gnn_muon_graph_sizes_t;
+
+typedef struct gnn_muon_graph_out {             /* DEVICE arrays: [n_hits] / [n_segments] / [n_graphs]              */
+    float *X;
+    int32_t *src, *dst;
+    float *y;
+    int32_t *hit_source;
+    int64_t *hit_row, *entry;
+    float *pt, *eta;
+    int32_t *flags, *graph_hits, *graph_segments;
+} gnn_muon_graph_out_t;
+
+size_t gnn_muon_graph_workspace_bytes(int64_t n_entries);
+int gnn_muon_graph_sizes(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu, int64_t n_entries, int32_t muon_only,
+                         void *workspace, size_t workspace_bytes, gnn_muon_graph_sizes_t *sizes_out, int64_t *hit_ptr,
+                         int64_t *seg_ptr, void *stream);
+int gnn_muon_graph_fill(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu, int64_t n_entries, int32_t muon_only,
+                        const float *vp_pt, const float *vp_eta, int64_t n_vp, int64_t entry_start,
+                        const gnn_muon_graph_sizes_t *sizes, void *workspace, size_t workspace_bytes,
+                        const gnn_muon_graph_out_t *out, void *stream);
+int gnn_muon_graph_padded(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu, int64_t n_entries, int32_t muon_only,
+                          const float *vp_pt, const float *vp_eta, int64_t n_vp, int64_t entry_start, void *workspace,
+                          size_t workspace_bytes, const gnn_muon_graph_out_t *out, int32_t *status, void *stream);
+
 /* ---- scoring a classifier: confusion counts, score histograms (csrc/metrics.hip; ABI 7) ----------------------------
  * Stands in for the evaluation cells of the reference's notebooks (gnn/MPNN_Seg_ACTS*.ipynb, makeROC and the
  * per-sample cells), which flatten Estimator.predict's scores (gnn/estimator.py:137-146) and call sklearn.metrics

@@ -1,0 +1,223 @@
+"""CPU tests of the muon graph builder's specification (gnn-fpga_amd/muon_graph.py) against fixtures made by running
+the reference's gnn/prepareMuonGraphs.py (tools/gen_muon_graph_golden.py), its set-order emulation against the
+interpreter, input validation and the new C ABI symbols."""
+import ctypes
+import glob
+import os
+import random
+import re
+
+import numpy as np
+import pytest
+
+from gnn_fpga_amd import _lib, build_muon_graphs, synth
+from gnn_fpga_amd import muon_graph as mg
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden", "muon_graph")
+CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz")))
+
+
+def load_case(name):
+    """(muon, pu, vp_pt, vp_eta, entry_start, muon_only, graph_entry, files) of one fixture."""
+    with np.load(os.path.join(GOLDEN, name + ".npz")) as f:
+        mu = {k: f["mu_" + k] for k in mg.HIT_FEATURES + ("event_ptr",)}
+        pu = {k: f["pu_" + k] for k in mg.HIT_FEATURES + ("event_ptr",)}
+        files = []
+        for k, num in enumerate(f["file_graph"]):
+            files.append((int(num), {n: f["f%d_%s" % (k, n)] for n in ("X", "Ri_rows", "Ri_cols", "Ro_rows", "Ro_cols",
+                                                                        "y", "pt", "eta")}))
+        return (mu, pu, f["vp_pt"], f["vp_eta"], int(f["entry_start"]), bool(f["muon_only"]), f["graph_entry"],
+                files, f["vp_ptr"])
+
+
+def sparse_of(src, dst, n_hits):
+    """(Ri_rows, Ri_cols, Ro_rows, Ro_cols) as the reference's Ri.nonzero() / Ro.nonzero() give them."""
+    cols = np.arange(src.shape[0])
+    ri = np.lexsort((cols, dst))
+    ro = np.lexsort((cols, src))
+    return dst[ri], cols[ri], src[ro], cols[ro]
+
+
+def assert_matches_case(res, case):
+    """A MuonGraphs (host arrays) against a fixture, bit for bit."""
+    _, _, _, _, start, _, graph_entry, files, _ = case
+    b = res.batch
+    X, src, dst, y = (np.asarray(t.cpu()) for t in (b.X, b.src, b.dst, b.y))
+    entry = np.asarray(res.entry)
+    assert entry.tolist() == graph_entry.tolist()
+    written = np.asarray(res.written)
+    assert np.flatnonzero(written).tolist() == [n for n, _ in files]
+    for num, f in files:
+        h0, h1, s0, s1 = (int(v) for v in (b.hit_ptr[num], b.hit_ptr[num + 1], b.seg_ptr[num], b.seg_ptr[num + 1]))
+        assert X[h0:h1].tobytes() == f["X"].astype(np.float32).tobytes(), "graph %d: X" % num
+        got = sparse_of(src[s0:s1] - h0, dst[s0:s1] - h0, h1 - h0)
+        for k, name in enumerate(("Ri_rows", "Ri_cols", "Ro_rows", "Ro_cols")):
+            assert got[k].tolist() == f[name].tolist(), "graph %d: %s" % (num, name)
+        assert y[s0:s1].tobytes() == f["y"].tobytes(), "graph %d: y" % num
+        assert np.float32(res.pt[num]).tobytes() == f["pt"].astype(np.float32).tobytes()
+        assert np.float32(res.eta[num]).tobytes() == f["eta"].astype(np.float32).tobytes()
+    for g in np.flatnonzero(~written):
+        assert b.seg_ptr[g + 1] == b.seg_ptr[g]
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_spec_matches_reference(name):
+    case = load_case(name)
+    mu, pu, vpt, veta, start, muon_only = case[:6]
+    res = build_muon_graphs(mu, pu, vpt, veta, entry_start=start, muon_only=muon_only)
+    assert res.batch.n_features == 11 and not res.vp_missing.any()
+    assert_matches_case(res, case)
+
+
+def test_fixtures_exercise_their_traps():
+    assert len(CASES) >= 10
+    lut = mg.lut_array()
+    # trap 1: z = +-0 hits are nodes with layer +-0
+    res = build_muon_graphs(*load_case("layer_z0")[:4])
+    lay = res.batch.X.numpy()[:, 10]
+    assert np.any(lay == 0)
+    mu = load_case("layer_z0")[0]
+    assert np.any((mu["vh_sim_z"] == 0) & np.signbit(mu["vh_sim_z"]))
+    # trap 2: some entry's PU rows outnumber the muon rows (cut to the muon count) and the other way round
+    mu, pu = load_case("cross_filter")[:2]
+    n_mu, n_pu = np.diff(mu["event_ptr"]), np.diff(pu["event_ptr"])
+    assert np.any(n_mu < n_pu) and np.any(n_mu > n_pu)
+    assert np.any(lut[mu["vh_type"], mu["vh_station"], mu["vh_ring"]] == -99)
+    # trap 3: a graph whose muon rows come before its PU rows, and a PU entry dropped
+    res = build_muon_graphs(*load_case("ordinal")[:4])
+    first_mu = [res.hit_source[res.batch.hit_ptr[g]] == 1 and 0 in res.hit_source[res.batch.hit_ptr[g]:
+                res.batch.hit_ptr[g + 1]] for g in range(res.n_graphs)]
+    assert any(first_mu)
+    with_pu = sum(0 in res.hit_source[res.batch.hit_ptr[g]:res.batch.hit_ptr[g + 1]] for g in range(res.n_graphs))
+    assert with_pu < res.n_graphs
+    # trap 4: more rows than chambers in an entry
+    mu = load_case("duplicates")[0]
+    assert np.diff(mu["event_ptr"]).max() > 21
+    # trap 5: -1 and -2 both in one graph, and the non-ascending positive order
+    res = build_muon_graphs(*load_case("set_order")[:4])
+    g1 = res.batch.X.numpy()[res.batch.hit_ptr[1]:res.batch.hit_ptr[2], 10]
+    assert -1.0 in g1 and -2.0 in g1
+    assert mg.set_order([3.0, 8.0, 9.0, 11.0]) == [8.0, 9.0, 3.0, 11.0]
+    # trap 6: in graph 0 every hit has r = 250: every pair has dr = 0 and no segment is kept
+    res = build_muon_graphs(*load_case("segments")[:4])
+    assert res.written[0] and res.n_segments[0] == 0
+    # trap 8: a vp frame with an entry of 0 rows and one of 2
+    vp_ptr = load_case("vp_shift")[8]
+    assert 0 in np.diff(vp_ptr) and 2 in np.diff(vp_ptr) and load_case("vp_shift")[4] > 0
+    # trap 9: a graph without a file and a written graph with zero segments
+    case = load_case("no_file")
+    res = build_muon_graphs(*case[:4])
+    assert not res.written.all()
+    assert any(res.written[g] and res.n_segments[g] == 0 for g in range(res.n_graphs))
+    # trap 10
+    assert load_case("muononly")[5]
+
+
+def test_set_order_matches_the_interpreter():
+    rng = random.Random(7)
+    for _ in range(12000):
+        vals = [float(rng.randint(-12, 12)) for _ in range(rng.randint(0, 60))]
+        if rng.random() < 0.2:
+            vals = [-0.0 if v == 0 else v for v in vals]
+        want = list(set(vals))
+        got = mg.set_order(vals)
+        assert [repr(v) for v in got] == [repr(v) for v in want], vals
+    assert mg.set_order([-1.0, -3.0, -2.0, -10.0, -12.0, 4.0, 5.0]) == [4.0, 5.0, -12.0, -10.0, -2.0, -3.0, -1.0]
+
+
+def _events(n=6, seed=3):
+    return synth.emtf_events(n, seed=seed)
+
+
+def test_validation():
+    d = _events()
+    ok = lambda mu=d["muon"], pu=d["pu"], **k: build_muon_graphs(mu, pu, d["vp_pt"], d["vp_eta"], **k)  # noqa: E731
+    ok()
+    for col, val in (("vh_type", 5), ("vh_ring", -1), ("vh_station", 7)):
+        mu = dict(d["muon"])
+        mu[col] = mu[col].copy()
+        mu[col][3] = val
+        with pytest.raises(ValueError, match="outside"):
+            ok(mu=mu)
+    for val in (np.nan, np.inf):
+        pu = dict(d["pu"])
+        pu["vh_sim_z"] = pu["vh_sim_z"].copy()
+        pu["vh_sim_z"][2] = val
+        with pytest.raises(ValueError, match="non-finite"):
+            ok(pu=pu)
+    mu = dict(d["muon"], vh_sim_r=d["muon"]["vh_sim_r"].astype(np.float64))
+    with pytest.raises(ValueError, match="float64"):
+        ok(mu=mu)
+    mu = dict(d["muon"], vh_bend=d["muon"]["vh_bend"].astype(np.int64))
+    with pytest.raises(ValueError, match="32 bits"):
+        ok(mu=mu)
+    mu = dict(d["muon"], event_ptr=d["muon"]["event_ptr"][::-1])
+    with pytest.raises(ValueError, match="event_ptr"):
+        ok(mu=mu)
+    pu = dict(d["pu"], event_ptr=d["pu"]["event_ptr"][:-1])
+    with pytest.raises(ValueError):
+        ok(pu=pu)
+    mu = {k: v for k, v in d["muon"].items() if k != "vh_ring"}
+    with pytest.raises(ValueError, match="columns"):
+        ok(mu=mu)
+    with pytest.raises(ValueError, match="layout"):
+        ok(layout="dense")
+
+
+def test_missing_vp_row_gives_nan_and_flag():
+    d = _events(5, seed=4)
+    res = build_muon_graphs(d["muon"], d["pu"], d["vp_pt"][:3], d["vp_eta"][:3])
+    late = res.entry >= 3
+    assert late.any() and res.vp_missing[late].all() and not res.vp_missing[~late].any()
+    assert np.isnan(res.pt[late]).all() and np.isnan(res.eta[late]).all()
+
+
+def test_padded_host_layout_holds_the_flat_graphs():
+    d = _events(9, seed=5)
+    flat = build_muon_graphs(d["muon"], d["pu"], d["vp_pt"], d["vp_eta"], entry_start=3)
+    pad = build_muon_graphs(d["muon"], d["pu"], d["vp_pt"], d["vp_eta"], entry_start=3, layout="padded")
+    assert pad.batch.n_graphs == 9 and pad.batch.n_hits == 9 * 42 and pad.batch.n_segments == 9 * 441
+    H, S = mg.MAX_GRAPH_HITS, mg.MAX_GRAPH_SEGMENTS
+    for g in range(flat.n_graphs):
+        e = int(flat.entry[g]) - 3
+        h0, h1 = flat.batch.hit_ptr[g], flat.batch.hit_ptr[g + 1]
+        s0, s1 = flat.batch.seg_ptr[g], flat.batch.seg_ptr[g + 1]
+        assert pad.present[e] and pad.entry[e] == flat.entry[g]
+        assert np.array_equal(pad.batch.X.numpy()[e * H:e * H + h1 - h0], flat.batch.X.numpy()[h0:h1])
+        assert not pad.batch.X.numpy()[e * H + h1 - h0:(e + 1) * H].any()
+        assert np.array_equal(pad.batch.src.numpy()[e * S:e * S + s1 - s0] - e * H, flat.batch.src.numpy()[s0:s1] - h0)
+        assert (pad.batch.src.numpy()[e * S + s1 - s0:(e + 1) * S] == -1).all()
+
+
+def test_new_symbols_declared_bound_exported():
+    import gnn_fpga_amd
+    assert gnn_fpga_amd.build_muon_graphs is build_muon_graphs
+    with open(os.path.join(REPO, "include", "gnn_hip.h")) as f:
+        hdr = f.read()
+    names = ("gnn_muon_graph_workspace_bytes", "gnn_muon_graph_sizes", "gnn_muon_graph_fill", "gnn_muon_graph_padded")
+    for n in names:
+        assert re.search(r"\b%s\(" % n, hdr), n
+        assert n in _lib.SIGNATURES, n
+    assert "#define GNN_ABI_VERSION 7" in hdr and _lib.GNN_ABI_VERSION == 7
+    for n in ("GnnEmtfHits", "GnnMuonGraphSizes", "GnnMuonGraphOut"):
+        assert issubclass(getattr(_lib, n), ctypes.Structure)
+    with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "Makefile")) as f:
+        assert re.search(r"^UNITS\s*:=.*\bmuon_graph\b", f.read(), re.M)
+    for tool in ("ab_build.sh", "ablate_build.sh"):
+        with open(os.path.join(REPO, "tools", tool)) as f:
+            assert "muon_graph" in f.read(), tool
+
+
+def test_muon_graph_kernels_have_no_scratch():
+    path = os.path.join(REPO, "build", "muon_graph.remarks")
+    if not os.path.exists(path):
+        import subprocess
+        subprocess.check_call(["make", "-C", os.path.join(REPO, "gnn-fpga_amd", "csrc"), "--no-print-directory"])
+    with open(path) as f:
+        text = f.read()
+    kernels = re.findall(r"Function Name: (\S*k_mg_\S*)", text)
+    assert len(kernels) >= 7, "k_mg_* kernels missing from the remarks: %s" % kernels
+    scratch = re.findall(r"Function Name: (\S*k_mg_\S*).*\n(?:.*\n)*?.*ScratchSize \[bytes/lane\]: (\d+)", text)
+    assert len(scratch) == len(kernels)
+    assert all(int(s) == 0 for _, s in scratch), scratch
