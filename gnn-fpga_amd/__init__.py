@@ -4,7 +4,8 @@ Layout: `csrc/` HIP kernels + the C-ABI library (`include/gnn_hip.h`), `_lib.py`
 ctypes binding, `model.py` the drop-in nn.Module tree, `hitgraph.py` the index-form
 batch/loader, `synth.py` synthetic inputs, `shard.py` event-batch sharding over ranks,
 `graph_build.py` segment graphs from detector hits, `hit_samples.py` the hit classifier's track samples from
-detector hits, `muon_graph.py` the muon trigger graphs from EMTF hits, `metrics.py` confusion counts, ROC and AUC.
+detector hits, `muon_graph.py` the muon trigger graphs from EMTF hits, `event_graphs.py` the ACTS full-event graphs
+from cluster hits, `metrics.py` confusion counts, ROC and AUC.
 """
 from .synth import HitGraph  # noqa: F401
 from .hitgraph import HitGraphBatch  # noqa: F401
@@ -12,4 +13,5 @@ from .batcher import GraphStore, batch_generator, merge_graphs  # noqa: F401,E40
 from .graph_build import build_graphs  # noqa: F401,E402
 from .hit_samples import HitSamples, build_hit_samples  # noqa: F401,E402
 from .muon_graph import MuonGraphs, build_muon_graphs  # noqa: F401,E402
+from .event_graphs import EventGraphs, build_event_graphs  # noqa: F401,E402
 from .metrics import SegmentMetrics, evaluate  # noqa: F401,E402

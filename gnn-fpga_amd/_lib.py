@@ -73,6 +73,10 @@ class GnnHitSamplesSizes(ctypes.Structure):
     _fields_ = [(n, _i64) for n in ("n_samples", "n_hits", "n_segments", "n_kept", "n_groups", "n_tasks", "status")]
 
 
+class GnnEventGraphsSizes(ctypes.Structure):
+    _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "n_kept", "n_tasks", "n_tested", "status")]
+
+
 class GnnEmtfHits(ctypes.Structure):
     _fields_ = [(n, _f) for n in ("z", "theta", "phi", "r", "bend", "tp1", "tp2", "station", "ring", "type",
                                   "event_ptr")] + [("n_rows", _i64)]
@@ -165,6 +169,12 @@ SIGNATURES = {
                                            ctypes.POINTER(GnnMuonGraphOut), _f]),
     "gnn_muon_graph_padded": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f,
                                              _f, _i64, _i64, _f, _sz, ctypes.POINTER(GnnMuonGraphOut), _f, _f]),
+    "gnn_event_graphs_workspace_bytes": (_sz, [_i64, _i64]),
+    "gnn_event_graphs_sizes": (ctypes.c_int, [_f, _f, _f, _f, _f, _f, _i64, _f, _i64, ctypes.c_float, ctypes.c_float,
+                                              _i64, _i64, _i64, _f, _sz, _f, _f, _f, _f, _f]),
+    "gnn_event_graphs_fill": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, ctypes.c_float, ctypes.c_float,
+                                             ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                             ctypes.POINTER(GnnEventGraphsSizes), _f, _sz, _f, _f, _f, _f, _f, _f, _f]),
     "gnn_metrics_bins": (_i64, [_i32]),
     "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
@@ -958,6 +968,51 @@ def hit_samples_fill(ws, sizes, r, phi, z, particle_id, n_events, n_det_layers, 
             ws.numel(), X.data_ptr(), y.data_ptr(), hit_index.data_ptr(), src.data_ptr(), dst.data_ptr(),
             keys.data_ptr(), st))
     return X, y, hit_index, src, dst, keys
+
+
+def event_graphs_sizes(r, phi, z, volid, layid, barcode, event_ptr, cuts, bounds):
+    """Stage 1 of the full-event graph builder (csrc/event_graphs.hip): (workspace, GnnEventGraphsSizes, hit_ptr,
+    seg_ptr, event_index) - the sizes struct and both offset arrays come back in ONE read-back; event_index stays on
+    the device.  cuts: (dphi_max, dz_max); bounds: (n_nodes_min, n_nodes_max, n_edges_max) as the library takes them."""
+    dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
+    need = int(load().gnn_event_graphs_workspace_bytes(n, E))
+    if need == 0:
+        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    nw = ctypes.sizeof(GnnEventGraphsSizes) // 8
+    out = torch.empty(nw + 3 * (E + 1), dtype=torch.int64, device=dev)
+    with _on(r) as st:
+        _check(load().gnn_event_graphs_sizes(
+            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
+            _dev(volid, torch.int32, "volid"), _dev(layid, torch.int32, "layid"), _dev(barcode, torch.int64, "barcode"),
+            n, _dev(event_ptr, torch.int64, "event_ptr"), E, cuts[0], cuts[1], bounds[0], bounds[1], bounds[2],
+            ws.data_ptr(), ws.numel(), out.data_ptr(), out[nw:].data_ptr(), out[nw + E + 1:].data_ptr(),
+            out[nw + 2 * (E + 1):].data_ptr(), st))
+    host = out[:nw + 2 * (E + 1)].cpu().numpy()
+    sizes = GnnEventGraphsSizes()
+    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnEventGraphsSizes))
+    G = int(sizes.n_graphs)
+    o = nw + 2 * (E + 1)
+    return ws, sizes, host[nw:nw + G + 1].copy(), host[nw + E + 1:nw + E + 2 + G].copy(), out[o:o + G].clone()
+
+
+def event_graphs_fill(ws, sizes, r, phi, z, barcode, n_events, cuts, feature_scale):
+    """Stage 2: (X [N, 3], src, dst [S] int32, y [S], hit_index [N] int64, layer [N] int32), N and S from `sizes`."""
+    dev = ws.device
+    N, S = int(sizes.n_hits), int(sizes.n_segments)
+    X = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    src = torch.empty(S, dtype=torch.int32, device=dev)
+    dst = torch.empty(S, dtype=torch.int32, device=dev)
+    y = torch.empty(S, dtype=torch.float32, device=dev)
+    hit_index = torch.empty(N, dtype=torch.int64, device=dev)
+    layer = torch.empty(N, dtype=torch.int32, device=dev)
+    with _on(ws) as st:
+        _check(load().gnn_event_graphs_fill(
+            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
+            _dev(barcode, torch.int64, "barcode"), int(r.shape[0]), n_events, cuts[0], cuts[1], feature_scale[0],
+            feature_scale[1], feature_scale[2], ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(),
+            src.data_ptr(), dst.data_ptr(), y.data_ptr(), hit_index.data_ptr(), layer.data_ptr(), st))
+    return X, src, dst, y, hit_index, layer
 
 
 def _emtf_hits(cols, n_rows):

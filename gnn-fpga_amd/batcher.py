@@ -124,6 +124,27 @@ class GraphStore:
         store.pt, store.eta = pt, eta
         return store
 
+    @classmethod
+    def from_batch(cls, batch):
+        """The store of a block-diagonal HitGraphBatch that already lives where it will be used (what the device
+        graph builders return): its global hit ids become ids local to the graph with one subtract there, its
+        pointers are kept; no host pass over hits or segments."""
+        hp, sp = np.asarray(batch.hit_ptr, dtype=np.int64), np.asarray(batch.seg_ptr, dtype=np.int64)
+        if hp.shape != sp.shape or hp[0] != 0 or sp[0] != 0 or hp[-1] != batch.n_hits or sp[-1] != batch.n_segments \
+                or np.any(np.diff(hp) < 0) or np.any(np.diff(sp) < 0):
+            raise ValueError("hit_ptr / seg_ptr do not describe the batch's graphs")
+        store = cls.__new__(cls)
+        store.n_graphs = hp.shape[0] - 1
+        store.hit_ptr, store.seg_ptr = hp.copy(), sp.copy()
+        dev = store.device = batch.X.device
+        off = torch.repeat_interleave(torch.from_numpy(hp[:-1].astype(np.int32)).to(dev),
+                                      torch.from_numpy(np.diff(sp)).to(dev), output_size=int(sp[-1]))
+        store.X = batch.X
+        store.src = torch.where(batch.src >= 0, batch.src - off, batch.src)     # (-1: a padded segment stays)
+        store.dst = torch.where(batch.dst >= 0, batch.dst - off, batch.dst)
+        store.y = batch.y
+        return store
+
     def batch(self, j, batch_size=1, layout="padded"):
         """(HitGraphBatch, y) of graphs j ... j + batch_size - 1, like `merge_graphs(graphs[j:j + batch_size], layout)`."""
         if layout not in ("padded", "flat"):

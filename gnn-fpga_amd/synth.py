@@ -291,3 +291,69 @@ def emtf_events(n_entries, seed=0, n_pu=24.0, p_hit=0.9, max_dup=3, tp_rate=0.08
     pt = 1.0 / rng.uniform(0.01, 0.5, size=n_entries)
     return {"muon": muon, "pu": pu, "vp_pt": pt.astype(np.float32), "vp_eta": (side * eta).astype(np.float32),
             "vp_ptr": np.arange(n_entries + 1, dtype=np.int64)}
+
+
+# Raw ACTS cluster columns as gnn/MPNN_Seg_ACTS_fullEvents.ipynb's select_hits (cell 5) takes them: r, phi, z float32,
+# volid, layid int32, barcode int64; event_ptr int64 [n_events + 1].  The ten barrel layers as (volid, layid):
+ActsColumns = namedtuple("ActsColumns", ["r", "phi", "z", "volid", "layid", "barcode", "event_ptr"])
+ACTS_BARREL_LAYERS = ((8, 2), (8, 4), (8, 6), (8, 8), (13, 2), (13, 4), (13, 6), (13, 8), (17, 2), (17, 4))
+ACTS_OTHER_VOLUMES = (7, 9, 12, 14, 16, 18)        # endcaps: dropped by the selection
+
+
+def acts_events(n_events, n_tracks, n_noise, seed=0, missing=0.1, dup=0.05, dup_equal=0.5, non_barrel=0.02):
+    """Seeded raw hit columns of `n_events` ACTS-like events for event_graphs.build_event_graphs.
+
+    `n_tracks` and `n_noise` are counts per event, or (lo, hi) ranges drawn per event (hi exclusive).  Tracks cross
+    the ten barrel layers as in `barrel_event`; a fraction `missing` of them misses one layer; a fraction `dup` of
+    the track hits has a second hit on the same layer, `dup_equal` of those with exactly the same r (the
+    deduplication's tie); noise hits sit on random barrel layers with their own negative barcodes, a few of them
+    sharing barcode 0; a fraction `non_barrel` of extra rows lies in endcap volumes.  Rows are shuffled per event."""
+    rng = np.random.default_rng(seed)
+    radii = np.asarray(BARREL_RADII)
+    lay_v = np.asarray([v for v, _ in ACTS_BARREL_LAYERS])
+    lay_l = np.asarray([l for _, l in ACTS_BARREL_LAYERS])
+    L = radii.shape[0]
+    draw = lambda v: int(rng.integers(v[0], v[1])) if isinstance(v, (tuple, list)) else int(v)   # noqa: E731
+    cols = {k: [] for k in ("r", "phi", "z", "volid", "layid", "barcode")}
+    event_ptr = np.zeros(n_events + 1, dtype=np.int64)
+    for e in range(n_events):
+        nt, nn_ = draw(n_tracks), draw(n_noise)
+        phi0 = rng.uniform(-np.pi, np.pi, size=(nt, 1))
+        k = rng.uniform(-4e-4, 4e-4, size=(nt, 1))
+        z0 = rng.normal(0.0, 40.0, size=(nt, 1))
+        cot = rng.uniform(-1.0, 1.0, size=(nt, 1))
+        r = radii[None, :] + rng.normal(0.0, 0.1, size=(nt, L))
+        phi = phi0 + k * r
+        z = z0 + r * cot + rng.normal(0.0, 0.5, size=(nt, L))
+        lay = np.broadcast_to(np.arange(L), (nt, L))
+        bc = np.broadcast_to(rng.integers(1, 2 ** 40, size=(nt, 1)), (nt, L))
+        skip = np.where(rng.random(size=nt) < missing, rng.integers(0, L, size=nt), -1)
+        have = (lay != skip[:, None]).ravel()
+        R, P, Z, Ly, B = (a.ravel()[have] for a in (r, phi, z, lay, bc))
+        d = np.flatnonzero(rng.random(size=R.shape[0]) < dup)
+        same = rng.random(size=d.shape[0]) < dup_equal
+        nl = rng.integers(0, L, size=nn_)
+        nb = -rng.integers(1, 2 ** 40, size=nn_)
+        nb[rng.random(size=nn_) < 0.05] = 0
+        R = np.concatenate([R, np.where(same, R[d], R[d] + rng.normal(0.0, 0.3, size=d.shape[0])),
+                            radii[nl] + rng.normal(0.0, 0.1, size=nn_)])
+        P = np.concatenate([P, P[d] + rng.normal(0.0, 1e-3, size=d.shape[0]), rng.uniform(-np.pi, np.pi, size=nn_)])
+        Z = np.concatenate([Z, Z[d] + rng.normal(0.0, 0.5, size=d.shape[0]), rng.uniform(-1000.0, 1000.0, size=nn_)])
+        Ly = np.concatenate([Ly, Ly[d], nl])
+        B = np.concatenate([B, B[d], nb])
+        V, Li = lay_v[Ly], lay_l[Ly]
+        m = int(rng.binomial(max(R.shape[0], 1), non_barrel))
+        R = np.concatenate([R, rng.uniform(30.0, 1000.0, size=m)])
+        P = np.concatenate([P, rng.uniform(-np.pi, np.pi, size=m)])
+        Z = np.concatenate([Z, rng.uniform(-3000.0, 3000.0, size=m)])
+        V = np.concatenate([V, rng.choice(ACTS_OTHER_VOLUMES, size=m)])
+        Li = np.concatenate([Li, 2 * rng.integers(1, 7, size=m)])
+        B = np.concatenate([B, rng.integers(1, 2 ** 40, size=m)])
+        P = np.mod(P + np.pi, 2 * np.pi) - np.pi                  # into [-pi, pi)
+        order = rng.permutation(R.shape[0])
+        for name, v in (("r", R), ("phi", P), ("z", Z), ("volid", V), ("layid", Li), ("barcode", B)):
+            cols[name].append(v[order])
+        event_ptr[e + 1] = event_ptr[e] + R.shape[0]
+    cat = lambda k, dt: (np.concatenate(cols[k]) if cols[k] else np.zeros(0)).astype(dt)     # noqa: E731
+    return ActsColumns(cat("r", np.float32), cat("phi", np.float32), cat("z", np.float32), cat("volid", np.int32),
+                       cat("layid", np.int32), cat("barcode", np.int64), event_ptr)

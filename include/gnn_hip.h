@@ -527,6 +527,52 @@ int gnn_muon_graph_padded(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu
                           const float *vp_pt, const float *vp_eta, int64_t n_vp, int64_t entry_start, void *workspace,
                           size_t workspace_bytes, const gnn_muon_graph_out_t *out, int32_t *status, void *stream);
 
+/* ---- ACTS full-event graphs from cluster hits, built on the GPU (csrc/event_graphs.hip; ABI 7) ----------------------
+ * Replaces the host graph preparation of gnn/MPNN_Seg_ACTS_fullEvents.ipynb: select_hits (cell 5: barrel selection,
+ * layer renumbering, deduplication in pandas), calc_dphi (cell 7), construct_graph (cell 8: three dense N x N masks,
+ * two dense N x E matrices, an int64 matmul for the labels) and the dataset loop with its occupancy filter (cells
+ * 16-18).  gnn-fpga_amd/event_graphs.py is the numpy specification; the output is bit-identical.  Two calls around
+ * ONE host read-back of the sizes:
+ *   gnn_event_graphs_workspace_bytes  device scratch both calls need (cells 5 and 8 allocate theirs in numpy)
+ *   gnn_event_graphs_sizes  cell 5, the window test of cell 8 counted per start hit, the filter of cells 17-18 ->
+ *                           *sizes_out, hit_ptr, seg_ptr [n_events + 1] and event_index [n_events] (the first
+ *                           n_graphs (+ 1) used; DEVICE memory, written asynchronously on `stream`)
+ *   gnn_event_graphs_fill   cell 8's X, edge list and labels (and merge_samples' float32 cast, cell 24) into arrays
+ *                           the caller allocated from a HOST copy of the sizes (the same workspace, not touched in
+ *                           between; the same cuts)
+ * Inputs (DEVICE): r, phi, z float32 [n_rows], volid, layid int32 [n_rows], barcode int64 [n_rows], event_ptr int64
+ * [n_events + 1] (event e owns rows [event_ptr[e], event_ptr[e+1])).  Rows whose volid is not 8, 13 or 17 are
+ * dropped; layer = int8(layid / 2 - 1 + 4 * volume) in float64, truncated toward zero (negative layers are legal);
+ * per (event, barcode, layer) the hit of smallest r is kept (the first row on ties); an event's hits are ordered by
+ * (barcode, layer), both signed.  For start hit i in that order, then end hit j in that order with layer[j] -
+ * layer[i] == 1, float32: dphi = phi[i] - phi[j], minus f32(2 pi) if > f32(pi), then plus f32(2 pi) if < -f32(pi);
+ * kept when |dphi| < dphi_max and |z[j] - z[i]| < dz_max.  An event is a graph when it has a kept hit and
+ * n_hits > n_nodes_min, n_hits < n_nodes_max, n_segments < n_edges_max (pass -1 / INT64_MAX for no test).  Graph g
+ * (event event_index[g], ascending) owns rows hit_ptr[g] .. hit_ptr[g+1] of X [., 3] (float32(float64(v) / scale)
+ * of r, phi, z), hit_index (int64, the input row) and layer (int32), and segments seg_ptr[g] .. seg_ptr[g+1] of src
+ * (start hit), dst (end hit) int32 in batch numbering and y = 1 iff both hits share a barcode.
+ * sizes.status (0 = fine): bit 1 a barrel row whose layer is outside int8, bit 2 more than 2^31 - 1 tested segments,
+ * bit 4 event_ptr not non-decreasing from 0 to n_rows, bit 8 a non-finite r, phi or z; gnn_event_graphs_fill refuses
+ * flagged sizes.  GNN_ERR_BADARG: null pointers, n_rows < 0, n_events < 1, a NaN cut, a zero or NaN scale;
+ * GNN_ERR_UNSUPPORTED: 2^31 - 1 rows or events, or more.  The output is the same in every run (no order decided by
+ * atomics). */
+typedef struct gnn_event_graphs_sizes {
+    int64_t n_graphs, n_hits, n_segments;       /* kept events; their hits; their segments                          */
+    int64_t n_kept, n_tasks, n_tested, status;  /* hits after deduplication; pair work items; segments counted      */
+} gnn_event_graphs_sizes_t;
+
+size_t gnn_event_graphs_workspace_bytes(int64_t n_rows, int64_t n_events);
+int gnn_event_graphs_sizes(const float *r, const float *phi, const float *z, const int32_t *volid, const int32_t *layid,
+                           const int64_t *barcode, int64_t n_rows, const int64_t *event_ptr, int64_t n_events,
+                           float dphi_max, float dz_max, int64_t n_nodes_min, int64_t n_nodes_max, int64_t n_edges_max,
+                           void *workspace, size_t workspace_bytes, gnn_event_graphs_sizes_t *sizes_out,
+                           int64_t *hit_ptr, int64_t *seg_ptr, int64_t *event_index, void *stream);
+int gnn_event_graphs_fill(const float *r, const float *phi, const float *z, const int64_t *barcode, int64_t n_rows,
+                          int64_t n_events, float dphi_max, float dz_max, double scale_r, double scale_phi,
+                          double scale_z, const gnn_event_graphs_sizes_t *sizes, void *workspace,
+                          size_t workspace_bytes, float *X, int32_t *src, int32_t *dst, float *y, int64_t *hit_index,
+                          int32_t *layer, void *stream);
+
 /* ---- scoring a classifier: confusion counts, score histograms (csrc/metrics.hip; ABI 7) ----------------------------
  * Stands in for the evaluation cells of the reference's notebooks (gnn/MPNN_Seg_ACTS*.ipynb, makeROC and the
  * per-sample cells), which flatten Estimator.predict's scores (gnn/estimator.py:137-146) and call sklearn.metrics
