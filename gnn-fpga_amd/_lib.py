@@ -235,6 +235,27 @@ def _dev(t, dtype, what):
     return t.data_ptr()
 
 
+def _rphiz(r, phi, z):
+    """The pointers of the three float32 hit columns, as the builders' entry points take them."""
+    return _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z")
+
+
+def _workspace(dev, need):
+    """A workspace of the `need` bytes a *_workspace_bytes call asked for (0: it refused its arguments)."""
+    if need == 0:
+        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
+    return torch.empty(int(need), dtype=torch.uint8, device=dev)
+
+
+def _read_back(struct_type, words):
+    """Device int64 words that start with a sizes struct -> (the struct, all the words as a host array): the ONE
+    device-to-host copy of a build."""
+    host = words.cpu().numpy()
+    sizes = struct_type()
+    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(struct_type))
+    return sizes, host
+
+
 class _on:
     """`with _on(tensor_or_device) as stream:` - makes that device CURRENT for the library call (the
     kernels launch on the current device; a stream of another device would be an invalid handle and
@@ -875,10 +896,7 @@ def plan_build_sizes(src, dst, hit_ptr, n_hits, n_segments, n_graphs, tile_hits,
                 _dev(src, torch.int32, "src"), _dev(dst, torch.int32, "dst"), _dev(hit_ptr, torch.int64, "hit_ptr"),
                 n_hits, n_segments, n_graphs, tile_hits, iter_records, chunk_segments, edge_records,
                 workspace.data_ptr(), workspace.numel(), sizes.data_ptr(), st))
-    host = sizes.cpu()
-    out = GnnPlanSizes()
-    ctypes.memmove(ctypes.byref(out), host.data_ptr(), ctypes.sizeof(GnnPlanSizes))
-    return out
+    return _read_back(GnnPlanSizes, sizes)[0]
 
 
 def graph_build_sizes(r, phi, z, layer, event_ptr, pairs, n_layers, n_phi_sectors, cuts):
@@ -889,21 +907,15 @@ def graph_build_sizes(r, phi, z, layer, event_ptr, pairs, n_layers, n_phi_sector
     pairs = np.ascontiguousarray(pairs, dtype=np.int32)
     pp = pairs.ctypes.data if pairs.size else None
     G = E * n_phi_sectors
-    need = int(load().gnn_graph_build_workspace_bytes(n, E, pp, pairs.shape[0], n_layers, n_phi_sectors))
-    if need == 0:
-        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace(dev, load().gnn_graph_build_workspace_bytes(n, E, pp, pairs.shape[0], n_layers, n_phi_sectors))
     nw = ctypes.sizeof(GnnGraphBuildSizes) // 8
     out = torch.empty(nw + 2 * (G + 1), dtype=torch.int64, device=dev)
     with _on(r) as st:
         _check(load().gnn_graph_build_sizes(
-            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
-            _dev(layer, torch.int32, "layer"), n, _dev(event_ptr, torch.int64, "event_ptr"), E, pp, pairs.shape[0],
-            n_layers, n_phi_sectors, cuts[0], cuts[1], cuts[2], ws.data_ptr(), ws.numel(), out.data_ptr(),
+            *_rphiz(r, phi, z), _dev(layer, torch.int32, "layer"), n, _dev(event_ptr, torch.int64, "event_ptr"), E, pp,
+            pairs.shape[0], n_layers, n_phi_sectors, *cuts, ws.data_ptr(), ws.numel(), out.data_ptr(),
             out[nw:].data_ptr(), out[nw + G + 1:].data_ptr(), st))
-    host = out.cpu().numpy()
-    sizes = GnnGraphBuildSizes()
-    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnGraphBuildSizes))
+    sizes, host = _read_back(GnnGraphBuildSizes, out)
     return ws, sizes, host[nw:nw + G + 1].copy(), host[nw + G + 1:].copy()
 
 
@@ -921,8 +933,7 @@ def graph_build_fill(ws, sizes, particle_id, event_ptr, pairs, n_layers, n_phi_s
         _check(load().gnn_graph_build_fill(
             None if particle_id is None else _dev(particle_id, torch.int64, "particle_id"), n_hits,
             int(event_ptr.shape[0]) - 1, pairs.ctypes.data if pairs.size else None, pairs.shape[0], n_layers,
-            n_phi_sectors, cuts[0], cuts[1], cuts[2], feature_scale[0], feature_scale[1], feature_scale[2],
-            ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(), src.data_ptr(), dst.data_ptr(),
+            n_phi_sectors, *cuts, *feature_scale, ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(), src.data_ptr(), dst.data_ptr(),
             None if y is None else y.data_ptr(), hit_index.data_ptr(), st))
     return X, src, dst, y, hit_index
 
@@ -931,21 +942,14 @@ def hit_samples_sizes(r, phi, z, layer, particle_id, event_ptr, n_det_layers, n_
     """Stage 1 of the hit-sample builder (csrc/hit_samples.hip): (workspace, GnnHitSamplesSizes) - the sizes come
     back in ONE read-back."""
     dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
-    need = int(load().gnn_hit_samples_workspace_bytes(n, E, n_det_layers, n_layer_hits))
-    if need == 0:
-        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace(dev, load().gnn_hit_samples_workspace_bytes(n, E, n_det_layers, n_layer_hits))
     out = torch.empty(ctypes.sizeof(GnnHitSamplesSizes) // 8, dtype=torch.int64, device=dev)
     with _on(r) as st:
         _check(load().gnn_hit_samples_sizes(
-            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
-            _dev(layer, torch.int32, "layer"), _dev(particle_id, torch.int64, "particle_id"), n,
+            *_rphiz(r, phi, z), _dev(layer, torch.int32, "layer"), _dev(particle_id, torch.int64, "particle_id"), n,
             _dev(event_ptr, torch.int64, "event_ptr"), E, n_det_layers, n_layer_hits, ws.data_ptr(), ws.numel(),
             out.data_ptr(), st))
-    host = out.cpu().numpy()
-    sizes = GnnHitSamplesSizes()
-    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnHitSamplesSizes))
-    return ws, sizes
+    return ws, _read_back(GnnHitSamplesSizes, out)[0]
 
 
 def hit_samples_fill(ws, sizes, r, phi, z, particle_id, n_events, n_det_layers, n_layer_hits, n_seed_layers,
@@ -962,11 +966,9 @@ def hit_samples_fill(ws, sizes, r, phi, z, particle_id, n_events, n_det_layers, 
     keys = torch.empty((S, 2), dtype=torch.int64, device=dev)
     with _on(ws) as st:
         _check(load().gnn_hit_samples_fill(
-            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
-            _dev(particle_id, torch.int64, "particle_id"), int(r.shape[0]), n_events, n_det_layers, n_layer_hits,
-            n_seed_layers, feature_scale[0], feature_scale[1], feature_scale[2], ctypes.byref(sizes), ws.data_ptr(),
-            ws.numel(), X.data_ptr(), y.data_ptr(), hit_index.data_ptr(), src.data_ptr(), dst.data_ptr(),
-            keys.data_ptr(), st))
+            *_rphiz(r, phi, z), _dev(particle_id, torch.int64, "particle_id"), int(r.shape[0]), n_events, n_det_layers,
+            n_layer_hits, n_seed_layers, *feature_scale, ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(),
+            y.data_ptr(), hit_index.data_ptr(), src.data_ptr(), dst.data_ptr(), keys.data_ptr(), st))
     return X, y, hit_index, src, dst, keys
 
 
@@ -975,22 +977,16 @@ def event_graphs_sizes(r, phi, z, volid, layid, barcode, event_ptr, cuts, bounds
     seg_ptr, event_index) - the sizes struct and both offset arrays come back in ONE read-back; event_index stays on
     the device.  cuts: (dphi_max, dz_max); bounds: (n_nodes_min, n_nodes_max, n_edges_max) as the library takes them."""
     dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
-    need = int(load().gnn_event_graphs_workspace_bytes(n, E))
-    if need == 0:
-        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ws = _workspace(dev, load().gnn_event_graphs_workspace_bytes(n, E))
     nw = ctypes.sizeof(GnnEventGraphsSizes) // 8
     out = torch.empty(nw + 3 * (E + 1), dtype=torch.int64, device=dev)
     with _on(r) as st:
         _check(load().gnn_event_graphs_sizes(
-            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
-            _dev(volid, torch.int32, "volid"), _dev(layid, torch.int32, "layid"), _dev(barcode, torch.int64, "barcode"),
-            n, _dev(event_ptr, torch.int64, "event_ptr"), E, cuts[0], cuts[1], bounds[0], bounds[1], bounds[2],
+            *_rphiz(r, phi, z), _dev(volid, torch.int32, "volid"), _dev(layid, torch.int32, "layid"),
+            _dev(barcode, torch.int64, "barcode"), n, _dev(event_ptr, torch.int64, "event_ptr"), E, cuts[0], cuts[1], bounds[0], bounds[1], bounds[2],
             ws.data_ptr(), ws.numel(), out.data_ptr(), out[nw:].data_ptr(), out[nw + E + 1:].data_ptr(),
             out[nw + 2 * (E + 1):].data_ptr(), st))
-    host = out[:nw + 2 * (E + 1)].cpu().numpy()
-    sizes = GnnEventGraphsSizes()
-    ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnEventGraphsSizes))
+    sizes, host = _read_back(GnnEventGraphsSizes, out[:nw + 2 * (E + 1)])
     G = int(sizes.n_graphs)
     o = nw + 2 * (E + 1)
     return ws, sizes, host[nw:nw + G + 1].copy(), host[nw + E + 1:nw + E + 2 + G].copy(), out[o:o + G].clone()
@@ -1008,10 +1004,9 @@ def event_graphs_fill(ws, sizes, r, phi, z, barcode, n_events, cuts, feature_sca
     layer = torch.empty(N, dtype=torch.int32, device=dev)
     with _on(ws) as st:
         _check(load().gnn_event_graphs_fill(
-            _dev(r, torch.float32, "r"), _dev(phi, torch.float32, "phi"), _dev(z, torch.float32, "z"),
-            _dev(barcode, torch.int64, "barcode"), int(r.shape[0]), n_events, cuts[0], cuts[1], feature_scale[0],
-            feature_scale[1], feature_scale[2], ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(),
-            src.data_ptr(), dst.data_ptr(), y.data_ptr(), hit_index.data_ptr(), layer.data_ptr(), st))
+            *_rphiz(r, phi, z), _dev(barcode, torch.int64, "barcode"), int(r.shape[0]), n_events, cuts[0], cuts[1],
+            *feature_scale, ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(), src.data_ptr(),
+            dst.data_ptr(), y.data_ptr(), hit_index.data_ptr(), layer.data_ptr(), st))
     return X, src, dst, y, hit_index, layer
 
 
@@ -1061,32 +1056,32 @@ def _muon_graphs(t, hit_ptr, seg_ptr, layout, entry_start, status=None, layout_p
                       status=status, entry_start=entry_start)
 
 
+def _muon_graph_begin(mu, pu, n_entries, n_mu, n_pu, muon_only, vp, entry_start):
+    """What both muon graph builds start with, inside `_on`: (workspace, the entry points' leading arguments muon, pu,
+    n_entries, muon_only, their arguments vp_pt, vp_eta, n_vp, entry_start)."""
+    ws = _workspace(mu["vh_sim_z"].device, load().gnn_muon_graph_workspace_bytes(n_entries))
+    hits = (ctypes.byref(_emtf_hits(mu, n_mu)), ctypes.byref(_emtf_hits(pu, n_pu)), n_entries, int(muon_only))
+    vps = (_dev(vp[0], torch.float32, "vp_pt"), _dev(vp[1], torch.float32, "vp_eta"), int(vp[0].shape[0]), entry_start)
+    return ws, hits, vps
+
+
 def muon_graph_flat(mu, pu, n_entries, n_mu, n_pu, muon_only, vp, entry_start):
     """The muon graph builder's two calls (csrc/muon_graph.hip) around ONE read-back of the sizes and offsets."""
     from .muon_graph import _raise_status
     dev = mu["vh_sim_z"].device
     E = n_entries
-    need = int(load().gnn_muon_graph_workspace_bytes(E))
-    if need == 0:
-        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
     nw = ctypes.sizeof(GnnMuonGraphSizes) // 8
     out = torch.empty(nw + 2 * (E + 1), dtype=torch.int64, device=dev)
     with _on(dev) as st:
-        hm, hp = _emtf_hits(mu, n_mu), _emtf_hits(pu, n_pu)
-        _check(load().gnn_muon_graph_sizes(ctypes.byref(hm), ctypes.byref(hp), E, int(muon_only), ws.data_ptr(),
-                                           ws.numel(), out.data_ptr(), out[nw:].data_ptr(),
+        ws, hits, vps = _muon_graph_begin(mu, pu, E, n_mu, n_pu, muon_only, vp, entry_start)
+        _check(load().gnn_muon_graph_sizes(*hits, ws.data_ptr(), ws.numel(), out.data_ptr(), out[nw:].data_ptr(),
                                            out[nw + E + 1:].data_ptr(), st))
-        host = out.cpu().numpy()
-        sizes = GnnMuonGraphSizes()
-        ctypes.memmove(ctypes.byref(sizes), host.ctypes.data, ctypes.sizeof(GnnMuonGraphSizes))
+        sizes, host = _read_back(GnnMuonGraphSizes, out)
         _raise_status(int(sizes.status))
         G = int(sizes.n_graphs)
         t, o = _muon_graph_out(dev, int(sizes.n_hits), int(sizes.n_segments), G)
-        _check(load().gnn_muon_graph_fill(ctypes.byref(hm), ctypes.byref(hp), E, int(muon_only),
-                                          _dev(vp[0], torch.float32, "vp_pt"), _dev(vp[1], torch.float32, "vp_eta"),
-                                          int(vp[0].shape[0]), entry_start, ctypes.byref(sizes), ws.data_ptr(),
-                                          ws.numel(), ctypes.byref(o), st))
+        _check(load().gnn_muon_graph_fill(*hits, *vps, ctypes.byref(sizes), ws.data_ptr(), ws.numel(),
+                                          ctypes.byref(o), st))
     hit_ptr = host[nw:nw + G + 1].copy() if G else np.zeros(1, np.int64)
     seg_ptr = host[nw + E + 1:nw + E + 2 + G].copy() if G else np.zeros(1, np.int64)
     return _muon_graphs(t, hit_ptr, seg_ptr, "flat", entry_start)
@@ -1097,18 +1092,12 @@ def muon_graph_padded(mu, pu, n_entries, n_mu, n_pu, muon_only, vp, entry_start)
     from .muon_graph import MAX_GRAPH_HITS, MAX_GRAPH_SEGMENTS
     dev = mu["vh_sim_z"].device
     E = n_entries
-    need = int(load().gnn_muon_graph_workspace_bytes(E))
-    if need == 0:
-        raise GnnHipError("libgnn_hip: %s" % load().gnn_last_error().decode())
-    ws = torch.empty(need, dtype=torch.uint8, device=dev)
     status = torch.empty(1, dtype=torch.int32, device=dev)
     t, o = _muon_graph_out(dev, E * MAX_GRAPH_HITS, E * MAX_GRAPH_SEGMENTS, E)
     with _on(dev) as st:
-        hm, hp = _emtf_hits(mu, n_mu), _emtf_hits(pu, n_pu)
-        _check(load().gnn_muon_graph_padded(ctypes.byref(hm), ctypes.byref(hp), E, int(muon_only),
-                                            _dev(vp[0], torch.float32, "vp_pt"), _dev(vp[1], torch.float32, "vp_eta"),
-                                            int(vp[0].shape[0]), entry_start, ws.data_ptr(), ws.numel(),
-                                            ctypes.byref(o), status.data_ptr(), st))
+        ws, hits, vps = _muon_graph_begin(mu, pu, E, n_mu, n_pu, muon_only, vp, entry_start)
+        _check(load().gnn_muon_graph_padded(*hits, *vps, ws.data_ptr(), ws.numel(), ctypes.byref(o),
+                                            status.data_ptr(), st))
         step = torch.arange(E + 1, dtype=torch.int32, device=dev)
         ptrs = torch.stack([step * MAX_GRAPH_HITS, step * MAX_GRAPH_SEGMENTS])
     hit_ptr = np.arange(E + 1, dtype=np.int64) * MAX_GRAPH_HITS

@@ -32,13 +32,13 @@
 // Nothing is ordered by atomics (one integer total is summed by them): two builds of one input give the same bits.
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
 
 #include <cmath>
 
 #pragma clang fp contract(off)
+
+#include "builder_sort.h"
 
 namespace gnn {
 namespace {
@@ -46,26 +46,6 @@ namespace {
 constexpr int kFB = 64;                                // start hits per task, one lane each (one wave)
 constexpr int kTile = 512;                             // end hits per LDS tile
 constexpr int kPairWgPerCu = 16;
-constexpr float kPiF = (float)M_PI;                    // numpy compares float32 data with float32(np.pi)
-constexpr float kTwoPiF = (float)(2.0 * M_PI);
-constexpr int kStatusLayer = 1, kStatusInt32 = 2, kStatusEvents = 4, kStatusFinite = 8;
-
-typedef unsigned long long u64;
-
-// cell 7 calc_dphi, float32
-__device__ __forceinline__ float wrap_dphi(float d)
-{
-    if (d > kPiF) d = d - kTwoPiF;
-    if (d < -kPiF) d = d + kTwoPiF;
-    return d;
-}
-
-int bits_for(u64 v)                                    // bits to hold 0 .. v
-{
-    int b = 1;
-    while (b < 64 && (v >> b) != 0) ++b;
-    return b;
-}
 
 struct EgWs {
     int32_t *status;                                   // head: [status | pad | total (u64) at byte 8]
@@ -83,65 +63,44 @@ struct EgWs {
     size_t bytes;
 };
 
-size_t sort_temp_bytes(int64_t n)
-{
-    size_t t = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, t, (const u64 *)nullptr, (u64 *)nullptr, (const int32_t *)nullptr,
-                                    (int32_t *)nullptr, (size_t)n, 0u, 64u, (hipStream_t)0, false);
-    return t + 256;
-}
-
 EgWs carve_eg(char *base, int64_t n, int64_t E)
 {
     EgWs w;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += align256(b); return p; };
-    char *head = take(256);
+    Carver c{base};
+    char *head = c.take<char>(256);
     w.status = reinterpret_cast<int32_t *>(head);
     w.total = head ? reinterpret_cast<u64 *>(head + 8) : nullptr;
-    auto i32 = [&](int64_t k) { return reinterpret_cast<int32_t *>(take((size_t)k * 4)); };
     w.stride = (E + 64) & ~(int64_t)63;
-    w.evt = i32(n);
-    w.lay = i32(n);
-    w.gf = i32(n);
-    w.gx = i32(n + 1);
-    w.best = i32(n);
-    w.krow = i32(n);
-    w.kevt = i32(n);
-    w.klay = i32(n);
-    w.ehit = i32(E + 1);
-    w.tf = i32(n);
-    w.tx = i32(n + 1);
-    w.tstart = i32(n);
-    w.cnt = i32(n);
-    w.soff = i32(n + 1);
-    w.ev3 = i32(3 * w.stride);
-    w.ogr = i32(E + 1);
-    w.ohit = i32(E + 1);
-    w.oseg = i32(E + 1);
-    w.ka = reinterpret_cast<u64 *>(take((size_t)n * 8));
-    w.kb = reinterpret_cast<u64 *>(take((size_t)n * 8));
-    w.va = i32(n);
-    w.vb = i32(n);
-    w.sphi = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.sz = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.sbc = reinterpret_cast<int64_t *>(take((size_t)n * 8));
-    w.sums = i32(scan_sums_words(max(n, E)));
+    w.evt = c.take<int32_t>(n);
+    w.lay = c.take<int32_t>(n);
+    w.gf = c.take<int32_t>(n);
+    w.gx = c.take<int32_t>(n + 1);
+    w.best = c.take<int32_t>(n);
+    w.krow = c.take<int32_t>(n);
+    w.kevt = c.take<int32_t>(n);
+    w.klay = c.take<int32_t>(n);
+    w.ehit = c.take<int32_t>(E + 1);
+    w.tf = c.take<int32_t>(n);
+    w.tx = c.take<int32_t>(n + 1);
+    w.tstart = c.take<int32_t>(n);
+    w.cnt = c.take<int32_t>(n);
+    w.soff = c.take<int32_t>(n + 1);
+    w.ev3 = c.take<int32_t>(3 * w.stride);
+    w.ogr = c.take<int32_t>(E + 1);
+    w.ohit = c.take<int32_t>(E + 1);
+    w.oseg = c.take<int32_t>(E + 1);
+    w.ka = c.take<u64>(n);
+    w.kb = c.take<u64>(n);
+    w.va = c.take<int32_t>(n);
+    w.vb = c.take<int32_t>(n);
+    w.sphi = c.take<float>(n);
+    w.sz = c.take<float>(n);
+    w.sbc = c.take<int64_t>(n);
+    w.sums = c.take<int32_t>(scan_sums_words(max(n, E)));
     w.temp_bytes = n > 0 ? sort_temp_bytes(n) : 0;
-    w.temp = take(w.temp_bytes);
-    w.bytes = off + 256;
+    w.temp = c.take<char>(w.temp_bytes);
+    w.bytes = c.bytes();
     return w;
-}
-
-// the first position p in [0, n) with key[p] >= v (n when there is none)
-__device__ __forceinline__ int64_t lower_bound(const u64 *__restrict__ key, int64_t n, u64 v)
-{
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (key[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
 }
 
 // cell 5: the barrel selection and the layer, int8(layid / 2 - 1 + 4 * volume) in float64, truncated toward zero
@@ -154,13 +113,9 @@ __global__ __launch_bounds__(kBlock) void k_eg_key(const float *__restrict__ r, 
                                                    int32_t *__restrict__ status)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < E && (ep[i] > ep[i + 1] || (i == 0 && (ep[0] != 0 || ep[E] != n)))) atomicOr(status, kStatusEvents);
+    check_event_ptr(ep, E, n, i, status);
     if (i >= n) return;
-    int64_t lo = 0, hi = E;                            // the event: the largest e with ep[e] <= i
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ep[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int64_t lo = last_le(ep, E, i);              // the event
     int e = (int)lo, l = 0;
     const int v = volid[i];
     const int vol = v == 8 ? 0 : v == 13 ? 1 : v == 17 ? 2 : -1;
@@ -178,7 +133,7 @@ __global__ __launch_bounds__(kBlock) void k_eg_key(const float *__restrict__ r, 
             l = (int)lf;
         }
     }
-    if (e < E && !(ep[lo] <= i && i < ep[lo + 1])) e = (int)E;   // (flagged above: event_ptr is malformed)
+    if (e < E && !event_owns(ep, lo, i)) e = (int)E;   // (flagged above: event_ptr is malformed)
     evt[i] = e;
     lay[i] = l;
     ka[i] = (u64)(l + 128);                            // signed order
@@ -349,7 +304,7 @@ __global__ __launch_bounds__(kFB) void k_eg_pairs(int64_t n, const int32_t *__re
             __syncthreads();
             if (valid) {
                 for (int k = 0; k < mt; ++k) {
-                    const float dphi = wrap_dphi(my_phi - s_phi[k]);   // calc_dphi(phi[None, :], phi[:, None])
+                    const float dphi = wrap_dphi(my_phi - s_phi[k]);   // cell 7: calc_dphi(phi[None, :], phi[:, None])
                     const float dz = s_z[k] - my_z;
                     if (fabsf(dphi) < dphi_max && fabsf(dz) < dz_max) {
                         if (FILL) {
@@ -407,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void k_eg_final(int64_t n, int64_t E, const
     const int G = ogr[E];
     hit_ptr[G] = ohit[E];
     seg_ptr[G] = oseg[E];
-    const bool ovf = *total >= ((u64)1 << 31);
+    const bool ovf = *total >= (u64)kInt32End;
     sizes->n_graphs = G;
     sizes->n_hits = ovf ? 0 : ohit[E];
     sizes->n_segments = ovf ? 0 : oseg[E];
@@ -432,9 +387,9 @@ __global__ __launch_bounds__(kBlock) void k_eg_hits(int64_t n, const int32_t *__
     if (!keep[e]) return;
     const int64_t o = (int64_t)ohit[e] + (q - ehit[e]);
     const int row = krow[q];
-    X[3 * o] = (float)((double)r[row] / sc_r);         // cell 8: float32 columns / a float64 array, then float32
-    X[3 * o + 1] = (float)((double)phi[row] / sc_phi);
-    X[3 * o + 2] = (float)((double)z[row] / sc_z);
+    X[3 * o] = feature(r[row], sc_r);                  // cell 8: float32 columns / a float64 array, then float32
+    X[3 * o + 1] = feature(phi[row], sc_phi);
+    X[3 * o + 2] = feature(z[row], sc_z);
     hit_index[o] = row;
     layer[o] = klay[q];
 }
@@ -444,7 +399,7 @@ int check_args(const char *who, int64_t n_rows, int64_t n_events)
     if (n_rows < 0 || n_events < 1)
         return fail(GNN_ERR_BADARG, "%s: bad argument (n_rows %lld, n_events %lld)", who, (long long)n_rows,
                     (long long)n_events);
-    if (n_rows >= ((int64_t)1 << 31) - 1 || n_events >= ((int64_t)1 << 31) - 1)
+    if (n_rows >= kInt32End - 1 || n_events >= kInt32End - 1)
         return fail(GNN_ERR_UNSUPPORTED, "%s: sizes outside the int32 index range", who);
     return 0;
 }
@@ -454,21 +409,6 @@ int check_cuts(const char *who, float dphi_max, float dz_max)
     if (dphi_max != dphi_max || dz_max != dz_max) return fail(GNN_ERR_BADARG, "%s: dphi_max or dz_max is NaN", who);
     return 0;
 }
-
-char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
-
-#define EG_SORT(WHAT, KIN, KOUT, VIN, VOUT, BITS)                                                                     \
-    do {                                                                                                              \
-        size_t tb_ = 0;                                                                                               \
-        hipError_t e_ = rocprim::radix_sort_pairs(nullptr, tb_, (const u64 *)(KIN), (KOUT), (const int32_t *)(VIN),   \
-                                                  (VOUT), (size_t)n, 0u, (unsigned)(BITS), s, false);                 \
-        if (e_ == hipSuccess && tb_ > w.temp_bytes) e_ = hipErrorInvalidValue;                                        \
-        tb_ = w.temp_bytes;                                                                                           \
-        if (e_ == hipSuccess) e_ = rocprim::radix_sort_pairs(w.temp, tb_, (const u64 *)(KIN), (KOUT), (const int32_t *)(VIN),   \
-                                                  (VOUT), (size_t)n, 0u, (unsigned)(BITS), s, false);                 \
-        if (e_ != hipSuccess) return fail(-(int)e_, "gnn_event_graphs_sizes: radix sort %s: %s", WHAT,               \
-                                          hipGetErrorString(e_));                                                     \
-    } while (0)
 
 }  // namespace
 }  // namespace gnn
@@ -497,8 +437,7 @@ int gnn_event_graphs_sizes(const float *r, const float *phi, const float *z, con
         !seg_ptr || !event_index)
         return fail(GNN_ERR_BADARG, "gnn_event_graphs_sizes: pointer missing");
     const int64_t n = n_rows, E = n_events;
-    const size_t need = carve_eg(nullptr, n, E).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_eg(nullptr, n, E).bytes)) return rc;
     EgWs w = carve_eg(align_ws(workspace), n, E);
     hipError_t err = hipMemsetAsync(w.status, 0, 256, s);
     if (err == hipSuccess) err = hipMemsetAsync(sizes_out, 0, sizeof(gnn_event_graphs_sizes_t), s);
@@ -508,13 +447,16 @@ int gnn_event_graphs_sizes(const float *r, const float *phi, const float *z, con
     if (err != hipSuccess) return fail(-(int)err, "gnn_event_graphs_sizes: memset failed: %s", hipGetErrorString(err));
     GNN_LAUNCH("k_eg_key", k_eg_key, max(grid_for(max(n, E)), 1u), kBlock, s, r, phi, z, volid, layid, n, event_ptr, E,
                w.evt, w.lay, w.ka, w.va, w.status);
+    auto sort = [&](const char *what, const u64 *kin, u64 *kout, const int32_t *vin, int32_t *vout, int bits) {
+        return sort_pairs("gnn_event_graphs_sizes", what, w.temp, w.temp_bytes, kin, kout, vin, vout, n, bits, s);
+    };
     if (n > 0) {
         // (event, barcode, layer, row) order: the least significant key first, every sort stable
-        EG_SORT("by layer", w.ka, w.kb, w.va, w.vb, 8);
+        if (int rc = sort("by layer", w.ka, w.kb, w.va, w.vb, 8)) return rc;
         GNN_LAUNCH("k_eg_bckey", k_eg_bckey, grid_for(n), kBlock, s, n, barcode, w.vb, w.ka);
-        EG_SORT("by barcode", w.ka, w.kb, w.vb, w.va, 64);
+        if (int rc = sort("by barcode", w.ka, w.kb, w.vb, w.va, 64)) return rc;
         GNN_LAUNCH("k_eg_evkey", k_eg_evkey, grid_for(n), kBlock, s, n, w.evt, w.va, w.ka);
-        EG_SORT("by event", w.ka, w.kb, w.va, w.vb, bits_for((u64)E));
+        if (int rc = sort("by event", w.ka, w.kb, w.va, w.vb, bits_for((u64)E))) return rc;
         GNN_LAUNCH("k_eg_dedup", k_eg_dedup, grid_for(n), kBlock, s, n, E, w.vb, w.evt, w.lay, barcode, r, w.gf, w.best);
         if (int rc = scan_counts(w.gf, 0, 1, w.gx, nullptr, n, w.sums, s)) return rc;
     }
@@ -523,7 +465,7 @@ int gnn_event_graphs_sizes(const float *r, const float *phi, const float *z, con
         GNN_LAUNCH("k_eg_compact", k_eg_compact, grid_for(n), kBlock, s, n, E, w.gf, w.gx, w.best, w.evt, w.lay, w.krow,
                    w.kevt, w.klay, w.ka, w.va, w.cnt);
         // every (event, layer) bucket in position order
-        EG_SORT("by event and layer", w.ka, w.kb, w.va, w.vb, bits_for(((u64)E << 8) | 255));
+        if (int rc = sort("by event and layer", w.ka, w.kb, w.va, w.vb, bits_for(((u64)E << 8) | 255))) return rc;
         GNN_LAUNCH("k_eg_stage", k_eg_stage, grid_for(n), kBlock, s, n, w.gx, w.kb, w.vb, w.krow, phi, z, barcode,
                    w.sphi, w.sz, w.sbc, w.tf);
         if (int rc = scan_counts(w.tf, 0, 1, w.tx, nullptr, n, w.sums, s)) return rc;
@@ -556,16 +498,14 @@ int gnn_event_graphs_fill(const float *r, const float *phi, const float *z, cons
     const int64_t n = n_rows, E = n_events;
     if (!sizes || sizes->status != 0 || sizes->n_graphs < 0 || sizes->n_graphs > E || sizes->n_hits < 0 ||
         sizes->n_hits > sizes->n_kept || sizes->n_kept > n || sizes->n_segments < 0 ||
-        sizes->n_segments > sizes->n_tested || sizes->n_tested >= ((int64_t)1 << 31) || sizes->n_tasks < 0 ||
+        sizes->n_segments > sizes->n_tested || sizes->n_tested >= kInt32End || sizes->n_tasks < 0 ||
         sizes->n_tasks > n || (sizes->n_graphs == 0) != (sizes->n_hits == 0))
         return fail(GNN_ERR_BADARG, "gnn_event_graphs_fill: sizes missing, flagged or not from this input");
     if (sizes->n_hits == 0) return 0;
     if (!r || !phi || !z || !barcode || !X || !hit_index || !layer || (sizes->n_segments > 0 && (!src || !dst || !y)))
         return fail(GNN_ERR_BADARG, "gnn_event_graphs_fill: pointer missing");
-    if (!(scale_r != 0.0 && scale_phi != 0.0 && scale_z != 0.0))
-        return fail(GNN_ERR_BADARG, "gnn_event_graphs_fill: a feature scale is zero or NaN");
-    const size_t need = carve_eg(nullptr, n, E).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_scales("gnn_event_graphs_fill", scale_r, scale_phi, scale_z)) return rc;
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_eg(nullptr, n, E).bytes)) return rc;
     EgWs w = carve_eg(align_ws(workspace), n, E);
     GNN_LAUNCH("k_eg_hits", k_eg_hits, grid_for(sizes->n_kept), kBlock, s, n, w.gx, w.krow, w.kevt, w.klay, w.ehit,
                w.ev3, w.ohit, r, phi, z, scale_r, scale_phi, scale_z, X, hit_index, layer);

@@ -4,9 +4,9 @@
 // then construct_graph (gnn/graph.py:37-142), which merges every hit of layer l1 with every hit of layer l2 in pandas,
 // keeps the pairs that pass a phi-slope and a z0 cut, and builds two dense [N, E] uint8 matrices to find their
 // indices.  gnn-fpga_amd/graph_build.py is the numpy specification of what is computed here, and why it is float32;
-// the selected set is bit-identical to the reference's: the cut arithmetic below is the same float32 operations in
-// the same order, with contraction to FMA off (the pragma), IEEE division, and the sector test in float64 as pandas
-// does it.
+// the selected set is bit-identical to the reference's: the cut arithmetic (keep_pair, builder_common.h) is the same
+// float32 operations in the same order, with contraction to FMA off (the pragma), IEEE division, and the sector test
+// in float64 as pandas does it.
 //
 //   gnn_graph_build_sizes
 //     k_gb_key       one lane per hit: its event (binary search of event_ptr), sector, (graph, layer) bucket; counts
@@ -32,6 +32,8 @@
 
 #pragma clang fp contract(off)
 
+#include "builder_common.h"
+
 namespace gnn {
 namespace {
 
@@ -39,9 +41,6 @@ constexpr int kMaxPairs = 128;
 constexpr int kRows = 128;                             // l1 hits per task (one per lane)
 constexpr int kTile = 512;                             // l2 hits per LDS tile
 constexpr int kTaskWgPerCu = 8;
-constexpr float kPiF = (float)M_PI;                    // numpy rounds np.pi / 2 np.pi to float32 against float32 data
-constexpr float kTwoPiF = (float)(2.0 * M_PI);
-constexpr int kStatusLayer = 1, kStatusInt32 = 2, kStatusEvents = 4;
 
 struct PairTab {                                       // by value: layer_pairs and the cut each pair takes
     int32_t l1[kMaxPairs], l2[kMaxPairs];
@@ -62,19 +61,6 @@ __device__ __forceinline__ int sector_of(float phi, int S, double step)
     for (int k = max(c - 1, 0); k <= min(c + 1, S - 1); ++k)
         if (p > sector_edge(k, S, step) && p < sector_edge(k + 1, S, step)) return k;
     return -1;                                         // on an edge: in no sector (strict bounds)
-}
-
-// gnn/graph.py:43-66, float32, in the reference's order of operations
-__device__ __forceinline__ bool keep_pair(float r1, float p1, float z1, float r2, float p2, float z2, float cut,
-                                          float z0_max)
-{
-    float dphi = p2 - p1;
-    if (dphi > kPiF) dphi = dphi - kTwoPiF;
-    if (dphi < -kPiF) dphi = dphi + kTwoPiF;
-    const float dz = z2 - z1, dr = r2 - r1;
-    const float slope = dphi / dr;
-    const float z0 = z1 - (r1 * dz) / dr;
-    return fabsf(slope) < cut && fabsf(z0) < z0_max;  // NaN (dr = 0, dphi = 0) compares false
 }
 
 struct GbWs {
@@ -110,30 +96,29 @@ GbWs carve_gb(char *base, int64_t n, int64_t E, int L, int P, int S, int64_t RB)
     w.GP = w.G * P;
     w.gp_stride = (w.GP + 64) & ~(int64_t)63;
     w.RB = RB;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += align256(b); return p; };
+    Carver c{base};
     // [head 256 B | bcnt | bfill]: cleared by ONE memset
     w.head_bytes = 256 + 2 * w.B * (int64_t)sizeof(int32_t);
-    char *head = take((size_t)w.head_bytes);
+    char *head = c.take<char>(w.head_bytes);
     w.status = reinterpret_cast<int32_t *>(head);
     w.total = head ? reinterpret_cast<unsigned long long *>(head + 8) : nullptr;
     w.bcnt = head ? reinterpret_cast<int32_t *>(head + 256) : nullptr;
     w.bfill = w.bcnt ? w.bcnt + w.B : nullptr;
-    w.boff = reinterpret_cast<int32_t *>(take((size_t)(w.B + 1) * 4));
-    w.gpc = reinterpret_cast<int32_t *>(take((size_t)2 * w.gp_stride * 4));
-    w.rbase = reinterpret_cast<int32_t *>(take((size_t)(w.GP + 1) * 4));
-    w.tbase = reinterpret_cast<int32_t *>(take((size_t)(w.GP + 1) * 4));
-    w.hkey = reinterpret_cast<int32_t *>(take((size_t)n * 4));
-    w.unsorted = reinterpret_cast<int32_t *>(take((size_t)n * 4));
-    w.lrow = reinterpret_cast<int32_t *>(take((size_t)n * 4));
-    w.lout = reinterpret_cast<int32_t *>(take((size_t)n * 4));
-    w.lr = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.lphi = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.lz = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.rcnt = reinterpret_cast<int32_t *>(take((size_t)RB * 4));
-    w.roff = reinterpret_cast<int32_t *>(take((size_t)(RB + 1) * 4));
-    w.sums = reinterpret_cast<int32_t *>(take((size_t)scan_sums_words(max(max(w.B, w.GP), RB)) * 4));
-    w.bytes = off + 256;
+    w.boff = c.take<int32_t>(w.B + 1);
+    w.gpc = c.take<int32_t>(2 * w.gp_stride);
+    w.rbase = c.take<int32_t>(w.GP + 1);
+    w.tbase = c.take<int32_t>(w.GP + 1);
+    w.hkey = c.take<int32_t>(n);
+    w.unsorted = c.take<int32_t>(n);
+    w.lrow = c.take<int32_t>(n);
+    w.lout = c.take<int32_t>(n);
+    w.lr = c.take<float>(n);
+    w.lphi = c.take<float>(n);
+    w.lz = c.take<float>(n);
+    w.rcnt = c.take<int32_t>(RB);
+    w.roff = c.take<int32_t>(RB + 1);
+    w.sums = c.take<int32_t>(scan_sums_words(max(max(w.B, w.GP), RB)));
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -143,18 +128,14 @@ __global__ __launch_bounds__(kBlock) void k_gb_key(const float *__restrict__ phi
                                                    int32_t *__restrict__ status)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < E && (ep[i] > ep[i + 1] || (i == 0 && (ep[0] != 0 || ep[E] != n)))) atomicOr(status, kStatusEvents);
+    check_event_ptr(ep, E, n, i, status);
     if (i >= n) return;
-    int64_t lo = 0, hi = E;                            // the event: the largest e with ep[e] <= i
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ep[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int64_t lo = last_le(ep, E, i);              // the event
     const int l = layer[i];
     int key = -1;
     if (l < 0 || l >= L) {
         atomicOr(status, kStatusLayer);
-    } else if (ep[lo] <= i && i < ep[lo + 1]) {
+    } else if (event_owns(ep, lo, i)) {
         const int s = sector_of(phi[i], S, step);
         if (s >= 0) {
             key = (int)((lo * S + s) * L + l);
@@ -230,12 +211,7 @@ __global__ __launch_bounds__(kRows) void k_gb_pairs(int64_t GP, int P, int L, Pa
     const bool with_y = FILL && y != nullptr;
     unsigned long long acc = 0;
     for (int t = blockIdx.x; t < n_tasks; t += gridDim.x) {
-        int64_t lo = 0, hi = GP;                       // the (graph, pair): the largest gp with tbase[gp] <= t
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (tbase[mid] <= t) lo = mid; else hi = mid;
-        }
-        const int64_t gp = lo, g = gp / P;
+        const int64_t gp = last_le(tbase, GP, t), g = gp / P;   // the (graph, pair) of the task
         const int p = (int)(gp - g * P);
         const int k1 = (int)(g * L + pt.l1[p]), k2 = (int)(g * L + pt.l2[p]);
         const int n1 = bcnt[k1], n2 = bcnt[k2], b1 = boff[k1], b2 = boff[k2];
@@ -270,7 +246,7 @@ __global__ __launch_bounds__(kRows) void k_gb_pairs(int64_t GP, int P, int L, Pa
             __syncthreads();
             if (valid) {
                 for (int k = 0; k < m; ++k) {
-                    if (keep_pair(r1, p1, z1, sr[k], sp[k], sz[k], cut, z0_max)) {
+                    if (keep_pair(r1, p1, z1, sr[k], sp[k], sz[k], cut, z0_max)) {   // gnn/graph.py:43-66
                         if (FILL) {
                             src[o] = out1;
                             dst[o] = so[k];
@@ -348,9 +324,9 @@ __global__ __launch_bounds__(kBlock) void k_gb_features(int64_t n_out, int L, co
     }
     lout[j] = pos;
     hit_index[pos] = row;
-    X[3 * (int64_t)pos + 0] = (float)((double)lr[j] / sc_r);     // gnn/graph.py:118, the divide in float64
-    X[3 * (int64_t)pos + 1] = (float)((double)lphi[j] / sc_phi);
-    X[3 * (int64_t)pos + 2] = (float)((double)lz[j] / sc_z);
+    X[3 * (int64_t)pos + 0] = feature(lr[j], sc_r);    // gnn/graph.py:118, the divide in float64
+    X[3 * (int64_t)pos + 1] = feature(lphi[j], sc_phi);
+    X[3 * (int64_t)pos + 2] = feature(lz[j], sc_z);
 }
 
 int check_common(const char *who, int64_t n_hits, int64_t n_events, const int32_t *pairs, int32_t n_pairs,
@@ -365,8 +341,8 @@ int check_common(const char *who, int64_t n_hits, int64_t n_events, const int32_
     if (n_pairs > kMaxPairs) return fail(GNN_ERR_UNSUPPORTED, "%s: more than %d layer pairs", who, kMaxPairs);
     *rb = row_bound(n_hits, pairs, n_pairs);
     const int64_t G = n_events * n_phi_sectors;
-    if (n_hits >= ((int64_t)1 << 31) || n_events >= ((int64_t)1 << 31) || G * n_layers >= ((int64_t)1 << 31) ||
-        G * n_pairs >= ((int64_t)1 << 31) || *rb >= ((int64_t)1 << 31))
+    if (n_hits >= kInt32End || n_events >= kInt32End || G * n_layers >= kInt32End || G * n_pairs >= kInt32End ||
+        *rb >= kInt32End)
         return fail(GNN_ERR_UNSUPPORTED, "%s: sizes outside the int32 index range", who);
     return 0;
 }
@@ -381,8 +357,6 @@ PairTab pair_tab(const int32_t *pairs, int n_pairs, float psm, float pso)
     }
     return pt;
 }
-
-char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
 
 }  // namespace
 }  // namespace gnn
@@ -415,8 +389,9 @@ int gnn_graph_build_sizes(const float *r, const float *phi, const float *z, cons
         return rc;
     if ((n_hits > 0 && (!r || !phi || !z || !layer)) || !event_ptr || !sizes_out || !hit_ptr || !seg_ptr)
         return fail(GNN_ERR_BADARG, "gnn_graph_build_sizes: pointer missing");
-    const size_t need = carve_gb(nullptr, n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_workspace(workspace, workspace_bytes,
+                                 carve_gb(nullptr, n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb).bytes))
+        return rc;
     GbWs w = carve_gb(align_ws(workspace), n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb);
     const PairTab pt = pair_tab(layer_pairs, n_pairs, phi_slope_max, phi_slope_outer_max);
     const double step = (M_PI - -M_PI) / n_phi_sectors;
@@ -464,14 +439,14 @@ int gnn_graph_build_fill(const int64_t *particle_id, int64_t n_hits, int64_t n_e
                               &rb))
         return rc;
     if (!sizes || sizes->status != 0 || sizes->n_hits < 0 || sizes->n_hits > n_hits || sizes->n_segments < 0 ||
-        sizes->n_segments >= ((int64_t)1 << 31) || sizes->n_graphs != n_events * n_phi_sectors)
+        sizes->n_segments >= kInt32End || sizes->n_graphs != n_events * n_phi_sectors)
         return fail(GNN_ERR_BADARG, "gnn_graph_build_fill: sizes missing, flagged or not from this input");
     if ((sizes->n_hits > 0 && (!X || !hit_index)) || (sizes->n_segments > 0 && (!src || !dst)))
         return fail(GNN_ERR_BADARG, "gnn_graph_build_fill: output pointer missing");
-    if (!(scale_r != 0.0 && scale_phi != 0.0 && scale_z != 0.0))
-        return fail(GNN_ERR_BADARG, "gnn_graph_build_fill: a feature scale is zero or NaN");
-    const size_t need = carve_gb(nullptr, n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_scales("gnn_graph_build_fill", scale_r, scale_phi, scale_z)) return rc;
+    if (int rc = check_workspace(workspace, workspace_bytes,
+                                 carve_gb(nullptr, n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb).bytes))
+        return rc;
     GbWs w = carve_gb(align_ws(workspace), n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb);
     const PairTab pt = pair_tab(layer_pairs, n_pairs, phi_slope_max, phi_slope_outer_max);
     if (sizes->n_hits > 0)

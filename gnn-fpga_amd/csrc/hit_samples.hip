@@ -33,13 +33,13 @@
 // Nothing is ordered by atomics: two builds of one input give the same bits.
 #include <cstring>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
 
 #include <cmath>
 
 #pragma clang fp contract(off)
+
+#include "builder_sort.h"
 
 namespace gnn {
 namespace {
@@ -48,35 +48,15 @@ constexpr int kMaxK = 16, kMaxL = 64;                  // n_layer_hits, n_det_la
 constexpr int kFB = 64;                                // samples per fill workgroup, one lane each
 constexpr int kTile = 1024;                            // layer hits per LDS tile
 constexpr int kFillWgPerCu = 16;
-constexpr float kPiF = (float)M_PI;                    // numpy compares float32 data with float32(np.pi)
-constexpr float kTwoPiF = (float)(2.0 * M_PI);
-constexpr int kStatusLayer = 1, kStatusInt32 = 2, kStatusEvents = 4, kStatusFinite = 8;
 constexpr uint32_t kNanKey = 0x7FC00000u, kNoKey = 0xFFFFFFFFu;
-
-typedef unsigned long long u64;
 
 // gnn/MPNN_HitClassifier.ipynb cell 9 calc_eta on float32 columns: numpy's float32 ufuncs
 __device__ __forceinline__ float eta32(float r, float z) { return -1.0f * logf(tanf(atan2f(r, z) / 2.0f)); }
 // ... and on the track hit, an iloc row of a mixed-dtype frame: float64
 __device__ __forceinline__ double eta64(float r, float z) { return -1.0 * log(tan(atan2((double)r, (double)z) / 2.0)); }
 
-// cell 9 calc_dphi, float32
-__device__ __forceinline__ float wrap_dphi(float d)
-{
-    if (d > kPiF) d = d - kTwoPiF;
-    if (d < -kPiF) d = d + kTwoPiF;
-    return d;
-}
-
 // an order-preserving key of a non-negative float (a sum of squares or its sqrt); every NaN is one key above +inf
 __device__ __forceinline__ uint32_t dkey(float v) { return v != v ? kNanKey : __float_as_uint(v); }
-
-int bits_for(int64_t v)                                // bits to hold 0 .. v
-{
-    int b = 1;
-    while (b < 63 && (v >> b) != 0) ++b;
-    return b;
-}
 
 struct HsWs {
     int32_t *status;                                   // head: [status | pad] [cnt E*L] [gpc 2 * stride]
@@ -92,53 +72,43 @@ struct HsWs {
     size_t bytes;
 };
 
-size_t sort_temp_bytes(int64_t n)
-{
-    size_t t = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, t, (const u64 *)nullptr, (u64 *)nullptr, (const int32_t *)nullptr,
-                                    (int32_t *)nullptr, (size_t)n, 0u, 64u, (hipStream_t)0, false);
-    return t + 256;
-}
-
 HsWs carve_hs(char *base, int64_t n, int64_t E, int L)
 {
     HsWs w;
     w.EL = E * L;
     w.stride = (E + 64) & ~(int64_t)63;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += align256(b); return p; };
+    Carver c{base};
     w.head_bytes = 256 + (w.EL + 2 * w.stride) * (int64_t)sizeof(int32_t);
-    char *head = take((size_t)w.head_bytes);
+    char *head = c.take<char>(w.head_bytes);
     w.status = reinterpret_cast<int32_t *>(head);
     w.cnt = head ? reinterpret_cast<int32_t *>(head + 256) : nullptr;
     w.gpc = w.cnt ? w.cnt + w.EL : nullptr;
-    auto i32 = [&](int64_t k) { return reinterpret_cast<int32_t *>(take((size_t)k * 4)); };
-    w.evt = i32(n);
-    w.kept = i32(n);
-    w.gf = i32(n);
-    w.gx = i32(n + 1);
-    w.sf = i32(n);
-    w.sx = i32(n + 1);
-    w.gst = i32(n + 1);
-    w.gnl = i32(n);
-    w.gev = i32(n);
-    w.ok = i32(E);
-    w.sptr = i32(E + 1);
-    w.tbase = i32(E + 1);
-    w.trk = i32(n);
-    w.sev = i32(n);
-    w.boff = i32(w.EL + 1);
-    w.ka = reinterpret_cast<u64 *>(take((size_t)n * 8));
-    w.kb = reinterpret_cast<u64 *>(take((size_t)n * 8));
-    w.va = i32(n);
-    w.vb = i32(n);
-    w.leta = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.lphi = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.teta = reinterpret_cast<float *>(take((size_t)n * 4));
-    w.sums = i32(scan_sums_words(max(max(n, w.EL), E)));
+    w.evt = c.take<int32_t>(n);
+    w.kept = c.take<int32_t>(n);
+    w.gf = c.take<int32_t>(n);
+    w.gx = c.take<int32_t>(n + 1);
+    w.sf = c.take<int32_t>(n);
+    w.sx = c.take<int32_t>(n + 1);
+    w.gst = c.take<int32_t>(n + 1);
+    w.gnl = c.take<int32_t>(n);
+    w.gev = c.take<int32_t>(n);
+    w.ok = c.take<int32_t>(E);
+    w.sptr = c.take<int32_t>(E + 1);
+    w.tbase = c.take<int32_t>(E + 1);
+    w.trk = c.take<int32_t>(n);
+    w.sev = c.take<int32_t>(n);
+    w.boff = c.take<int32_t>(w.EL + 1);
+    w.ka = c.take<u64>(n);
+    w.kb = c.take<u64>(n);
+    w.va = c.take<int32_t>(n);
+    w.vb = c.take<int32_t>(n);
+    w.leta = c.take<float>(n);
+    w.lphi = c.take<float>(n);
+    w.teta = c.take<float>(n);
+    w.sums = c.take<int32_t>(scan_sums_words(max(max(n, w.EL), E)));
     w.temp_bytes = n > 0 ? sort_temp_bytes(n) : 0;
-    w.temp = take(w.temp_bytes);
-    w.bytes = off + 256;
+    w.temp = c.take<char>(w.temp_bytes);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -151,13 +121,9 @@ __global__ __launch_bounds__(kBlock) void k_hs_key(const float *__restrict__ r, 
                                                    int32_t *__restrict__ status)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < E && (ep[i] > ep[i + 1] || (i == 0 && (ep[0] != 0 || ep[E] != n)))) atomicOr(status, kStatusEvents);
+    check_event_ptr(ep, E, n, i, status);
     if (i >= n) return;
-    int64_t lo = 0, hi = E;                            // the event: the largest e with ep[e] <= i
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ep[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int64_t lo = last_le(ep, E, i);              // the event
     const int l = layer[i];
     int e = (int)lo;
     if (l < 0 || l >= L) {
@@ -166,7 +132,7 @@ __global__ __launch_bounds__(kBlock) void k_hs_key(const float *__restrict__ r, 
     } else if (!(isfinite(r[i]) && isfinite(phi[i]) && isfinite(z[i]))) {
         atomicOr(status, kStatusFinite);
         e = (int)E;
-    } else if (!(ep[lo] <= i && i < ep[lo + 1])) {
+    } else if (!event_owns(ep, lo, i)) {
         e = (int)E;                                    // (flagged above: event_ptr is malformed)
     }
     evt[i] = e;
@@ -218,7 +184,33 @@ __global__ __launch_bounds__(kBlock) void k_hs_gstart(int64_t n, const u64 *__re
     if (i == n - 1) gst[g + 1] = (int)n;
 }
 
-// one lane per (event, pid) group: its hits are stored layer by layer, each layer's in frame order
+// the hits [p0, p1) of one (event, pid) group are stored layer by layer, each layer's in frame order: when a layer's
+// run ends its hit of smallest r is kept -> kept(layer, row)
+template <typename Kept>
+__device__ __forceinline__ void walk_group(int p0, int p1, const u64 *__restrict__ key, const int32_t *__restrict__ rows,
+                                           const float *__restrict__ r, Kept kept)
+{
+    int best = -1, lay = -1;
+    float rb = 0.f;
+    for (int p = p0; p <= p1; ++p) {
+        const int l = p < p1 ? (int)(key[p] & 63) : -1;
+        if (l != lay) {
+            if (best >= 0) kept(lay, best);
+            if (p == p1) break;
+            lay = l;
+            best = rows[p];
+            rb = r[best];
+        } else {
+            const int row = rows[p];
+            if (r[row] < rb) {                         // idxmin: the first in frame order on ties
+                best = row;
+                rb = r[row];
+            }
+        }
+    }
+}
+
+// one lane per (event, pid) group
 __global__ __launch_bounds__(kBlock) void k_hs_walk(int64_t n, int64_t E, int L, const int32_t *__restrict__ gx,
                                                     const int32_t *__restrict__ gst, const u64 *__restrict__ key,
                                                     const int32_t *__restrict__ rows, const int32_t *__restrict__ evt,
@@ -231,30 +223,12 @@ __global__ __launch_bounds__(kBlock) void k_hs_walk(int64_t n, int64_t E, int L,
     const int p0 = gst[g], p1 = gst[g + 1];
     const int e = evt[rows[p0]];
     int runs = 0;
-    if (e < E) {
-        int best = -1, lay = -1;
-        float rb = 0.f;
-        for (int p = p0; p <= p1; ++p) {
-            const int l = p < p1 ? (int)(key[p] & 63) : -1;
-            if (l != lay) {                            // a layer's run ends: its hit of smallest r is kept
-                if (best >= 0) {
-                    kept[best] = 1;
-                    atomicAdd(cnt + (int64_t)e * L + lay, 1);
-                    ++runs;
-                }
-                if (p == p1) break;
-                lay = l;
-                best = rows[p];
-                rb = r[best];
-            } else {
-                const int row = rows[p];
-                if (r[row] < rb) {                     // idxmin: the first in frame order on ties
-                    best = row;
-                    rb = r[row];
-                }
-            }
-        }
-    }
+    if (e < E)
+        walk_group(p0, p1, key, rows, r, [&](int lay, int best) {
+            kept[best] = 1;
+            atomicAdd(cnt + (int64_t)e * L + lay, 1);
+            ++runs;
+        });
     gnl[g] = runs;
     gev[g] = e;
 }
@@ -306,24 +280,10 @@ __global__ __launch_bounds__(kBlock) void k_hs_track(int64_t n, int L, const int
     if (g >= gx[n] || !sf[g]) return;
     const int64_t s = sx[g];
     const int p0 = gst[g], p1 = gst[g + 1];
-    int best = -1, lay = -1;
-    float rb = 0.f;
-    for (int p = p0; p <= p1; ++p) {                   // the walk of k_hs_walk again: the kept hit of every layer
-        const int l = p < p1 ? (int)(key[p] & 63) : -1;
-        if (l != lay) {
-            if (best >= 0) {
-                trk[s * L + lay] = best;
-                teta[s * L + lay] = (float)eta64(r[best], z[best]);   // pandas: float32(lay_eta) - float32(trk_eta)
-            }
-            if (p == p1) break;
-            lay = l;
-            best = rows[p];
-            rb = r[best];
-        } else if (r[rows[p]] < rb) {
-            best = rows[p];
-            rb = r[best];
-        }
-    }
+    walk_group(p0, p1, key, rows, r, [&](int lay, int best) {
+        trk[s * L + lay] = best;
+        teta[s * L + lay] = (float)eta64(r[best], z[best]);   // pandas: float32(lay_eta) - float32(trk_eta)
+    });
     sev[s] = gev[g];
 }
 
@@ -365,7 +325,7 @@ __global__ void k_hs_final(int64_t n, int64_t E, int L, int K, const int32_t *__
     sizes->n_kept = n > 0 ? boff[E * L] : 0;
     sizes->n_groups = n > 0 ? gx[n] : 0;
     sizes->n_tasks = (int64_t)tbase[E] * L;
-    sizes->status = *status | (hits >= ((int64_t)1 << 31) || segs >= ((int64_t)1 << 31) ? kStatusInt32 : 0);
+    sizes->status = *status | (hits >= kInt32End || segs >= kInt32End ? kStatusInt32 : 0);
 }
 
 // cells 9 and 15 for one (event, block of samples, layer) per task: d = sqrt(deta^2 + dphi^2) in float32, the K
@@ -386,12 +346,7 @@ __global__ __launch_bounds__(kFB) void k_hs_fill(int64_t n_tasks, int L, int n_s
     for (int64_t t = blockIdx.x; t < n_tasks; t += gridDim.x) {
         const int64_t tb = t / L;
         const int l = (int)(t - tb * L);
-        int64_t lo = 0, hi = E;                        // the event: the largest e with tbase[e] <= tb
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (tbase[mid] <= tb) lo = mid; else hi = mid;
-        }
-        const int64_t e = lo;
+        const int64_t e = last_le(tbase, E, tb);       // the event of the task
         const int64_t s = sptr[e] + (tb - tbase[e]) * kFB + threadIdx.x;
         const bool valid = s < sptr[e + 1];
         float teta = 0.f, tphi = 0.f;
@@ -422,7 +377,7 @@ __global__ __launch_bounds__(kFB) void k_hs_fill(int64_t n_tasks, int L, int n_s
             if (valid) {
                 for (int k = 0; k < mt; ++k) {
                     const float deta = se[k] - teta;
-                    const float dphi = wrap_dphi(sp[k] - tphi);
+                    const float dphi = wrap_dphi(sp[k] - tphi);   // cell 9 calc_dphi
                     const float s2 = deta * deta + dphi * dphi;
                     const uint32_t ks = dkey(s2);
                     if (ks >= sk[K - 1]) continue;     // sqrt is monotone: d >= the last d, which came earlier
@@ -455,9 +410,9 @@ __global__ __launch_bounds__(kFB) void k_hs_fill(int64_t n_tasks, int L, int n_s
             const float lab = pid[row] == spid ? 1.0f : 0.0f;
             const float pc = wrap_dphi(phi[row] - phi0);
             float4 v;
-            v.x = (float)((double)r[row] / sc_r);      // cell 15: the DataFrame / float64 array, then float32
-            v.y = (float)((double)pc / sc_phi);
-            v.z = (float)((double)z[row] / sc_z);
+            v.x = feature(r[row], sc_r);               // cell 15: the DataFrame / float64 array, then float32
+            v.y = feature(pc, sc_phi);
+            v.z = feature(z[row], sc_z);
             v.w = seed ? lab : 0.0f;
             reinterpret_cast<float4 *>(X)[o] = v;
             y[o] = lab;
@@ -498,12 +453,10 @@ int check_args(const char *who, int64_t n_hits, int64_t n_events, int32_t L, int
                     who, (long long)n_hits, (long long)n_events, L, K);
     if (L > kMaxL || K > kMaxK)
         return fail(GNN_ERR_BADARG, "%s: n_det_layers %d > %d or n_layer_hits %d > %d", who, L, kMaxL, K, kMaxK);
-    if (n_hits >= ((int64_t)1 << 31) - 1 || n_events * L >= ((int64_t)1 << 31) - 1)
+    if (n_hits >= kInt32End - 1 || n_events * L >= kInt32End - 1)
         return fail(GNN_ERR_UNSUPPORTED, "%s: sizes outside the int32 index range", who);
     return 0;
 }
-
-char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
 
 template <int K>
 int launch_fill(unsigned grid, hipStream_t s, int64_t n_tasks, int L, int n_seed, int64_t E, const HsWs &w,
@@ -528,19 +481,6 @@ int fill_any(int K, unsigned grid, hipStream_t s, int64_t n_tasks, int L, int n_
     }
     return fail(GNN_ERR_BADARG, "n_layer_hits %d outside [1, %d]", K, kMaxK);
 }
-
-#define HS_SORT(WHAT, KIN, KOUT, VIN, VOUT, BITS)                                                                     \
-    do {                                                                                                              \
-        size_t tb_ = 0;                                                                                               \
-        hipError_t e_ = rocprim::radix_sort_pairs(nullptr, tb_, (const u64 *)(KIN), (KOUT), (const int32_t *)(VIN),   \
-                                                  (VOUT), (size_t)n, 0u, (unsigned)(BITS), s, false);                 \
-        if (e_ == hipSuccess && tb_ > w.temp_bytes) e_ = hipErrorInvalidValue;                                        \
-        tb_ = w.temp_bytes;                                                                                           \
-        if (e_ == hipSuccess) e_ = rocprim::radix_sort_pairs(w.temp, tb_, (const u64 *)(KIN), (KOUT), (const int32_t *)(VIN),   \
-                                                  (VOUT), (size_t)n, 0u, (unsigned)(BITS), s, false);                 \
-        if (e_ != hipSuccess) return fail(-(int)e_, "gnn_hit_samples_sizes: radix sort %s: %s", WHAT,                \
-                                          hipGetErrorString(e_));                                                     \
-    } while (0)
 
 }  // namespace
 }  // namespace gnn
@@ -567,24 +507,26 @@ int gnn_hit_samples_sizes(const float *r, const float *phi, const float *z, cons
         return fail(GNN_ERR_BADARG, "gnn_hit_samples_sizes: pointer missing");
     const int64_t n = n_hits, E = n_events;
     const int L = n_det_layers, K = n_layer_hits;
-    const size_t need = carve_hs(nullptr, n, E, L).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_hs(nullptr, n, E, L).bytes)) return rc;
     HsWs w = carve_hs(align_ws(workspace), n, E, L);
     hipError_t err = hipMemsetAsync(w.status, 0, (size_t)w.head_bytes, s);
     if (err == hipSuccess) err = hipMemsetAsync(sizes_out, 0, sizeof(gnn_hit_samples_sizes_t), s);
     if (err != hipSuccess) return fail(-(int)err, "gnn_hit_samples_sizes: memset failed: %s", hipGetErrorString(err));
     GNN_LAUNCH("k_hs_key", k_hs_key, max(grid_for(max(n, E)), 1u), kBlock, s, r, phi, z, layer, particle_id, n,
                event_ptr, E, L, w.evt, w.kept, w.ka, w.va, w.status);
+    auto sort = [&](const char *what, const u64 *kin, u64 *kout, const int32_t *vin, int32_t *vout, int bits) {
+        return sort_pairs("gnn_hit_samples_sizes", what, w.temp, w.temp_bytes, kin, kout, vin, vout, n, bits, s);
+    };
     if (n > 0) {
         // (event, pid, row) order: pid first, then a stable sort by event
-        HS_SORT("by particle", w.ka, w.kb, w.va, w.vb, 64);
+        if (int rc = sort("by particle", w.ka, w.kb, w.va, w.vb, 64)) return rc;
         GNN_LAUNCH("k_hs_evkey", k_hs_evkey, grid_for(n), kBlock, s, n, w.evt, w.vb, w.ka);
-        HS_SORT("by event", w.ka, w.kb, w.vb, w.va, bits_for(E));
+        if (int rc = sort("by event", w.ka, w.kb, w.vb, w.va, bits_for(E))) return rc;
         GNN_LAUNCH("k_hs_gflag", k_hs_gflag, grid_for(n), kBlock, s, n, w.evt, particle_id, w.va, w.gf);
         if (int rc = scan_counts(w.gf, 0, 1, w.gx, nullptr, n, w.sums, s)) return rc;
         // each group layer by layer, frame order within a layer
         GNN_LAUNCH("k_hs_layerkey", k_hs_layerkey, grid_for(n), kBlock, s, n, L, layer, w.va, w.gx, w.ka, w.vb);
-        HS_SORT("by group and layer", w.ka, w.kb, w.vb, w.va, 6 + bits_for(n));
+        if (int rc = sort("by group and layer", w.ka, w.kb, w.vb, w.va, 6 + bits_for(n))) return rc;
         GNN_LAUNCH("k_hs_gstart", k_hs_gstart, grid_for(n), kBlock, s, n, w.kb, w.gst);
         GNN_LAUNCH("k_hs_walk", k_hs_walk, grid_for(n), kBlock, s, n, E, L, w.gx, w.gst, w.kb, w.va, w.evt, r, w.kept,
                    w.cnt, w.gnl, w.gev);
@@ -602,7 +544,7 @@ int gnn_hit_samples_sizes(const float *r, const float *phi, const float *z, cons
         // the kept hits of every (event, layer) in frame order
         GNN_LAUNCH("k_hs_bucketkey", k_hs_bucketkey, grid_for(n), kBlock, s, n, E, L, w.evt, layer, w.kept, w.ka,
                    w.vb);
-        HS_SORT("by event and layer", w.ka, w.kb, w.vb, w.va, bits_for(w.EL));
+        if (int rc = sort("by event and layer", w.ka, w.kb, w.vb, w.va, bits_for(w.EL))) return rc;
     }
     if (int rc = scan_counts(w.cnt, 0, 1, w.boff, nullptr, w.EL, w.sums, s)) return rc;
     if (n > 0)
@@ -624,7 +566,7 @@ int gnn_hit_samples_fill(const float *r, const float *phi, const float *z, const
     const int L = n_det_layers, K = n_layer_hits;
     if (!sizes || sizes->status != 0 || sizes->n_samples < 0 || sizes->n_samples * L > n ||
         sizes->n_hits != sizes->n_samples * L * K || sizes->n_segments != sizes->n_samples * K * K * (L - 1) ||
-        sizes->n_hits >= ((int64_t)1 << 31) || sizes->n_segments >= ((int64_t)1 << 31) || sizes->n_tasks < 0 ||
+        sizes->n_hits >= kInt32End || sizes->n_segments >= kInt32End || sizes->n_tasks < 0 ||
         sizes->n_tasks > ((sizes->n_samples + kFB - 1) / kFB + E) * L)
         return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: sizes missing, flagged or not from this input");
     if (n_seed_layers < 0) return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: n_seed_layers < 0");
@@ -632,10 +574,8 @@ int gnn_hit_samples_fill(const float *r, const float *phi, const float *z, const
     if (S == 0) return 0;
     if (!r || !phi || !z || !particle_id || !X || !y || !hit_index || !keys || (sizes->n_segments > 0 && (!src || !dst)))
         return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: pointer missing");
-    if (!(scale_r != 0.0 && scale_phi != 0.0 && scale_z != 0.0))
-        return fail(GNN_ERR_BADARG, "gnn_hit_samples_fill: a feature scale is zero or NaN");
-    const size_t need = carve_hs(nullptr, n, E, L).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_scales("gnn_hit_samples_fill", scale_r, scale_phi, scale_z)) return rc;
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_hs(nullptr, n, E, L).bytes)) return rc;
     HsWs w = carve_hs(align_ws(workspace), n, E, L);
     const unsigned grid = (unsigned)min(sizes->n_tasks, (int64_t)device_cus() * kFillWgPerCu);
     if (grid > 0)

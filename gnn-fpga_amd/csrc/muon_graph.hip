@@ -4,9 +4,9 @@
 // in a row-wise DataFrame.apply, filters, deduplicates and mixes the muon and PU frames entry by entry, takes the
 // layer pairs from Python set order, and calls gnn/Muon_graph.py construct_graph per entry, which merges every hit of
 // layer l1 with every hit of layer l2.  gnn-fpga_amd/muon_graph.py is the numpy specification of what is computed
-// here; the output is bit-identical to it: the pair test is the reference's float32 operations in the same order, with
-// contraction to FMA off (the pragma) and IEEE division, and the layer order is an exact emulation of CPython's set
-// insertion.
+// here; the output is bit-identical to it: the pair test (keep_pair, builder_common.h) is the reference's float32
+// operations in the same order, with contraction to FMA off (the pragma) and IEEE division, and the layer order is an
+// exact emulation of CPython's set insertion.
 //
 //   gnn_muon_graph_sizes
 //     k_mg_check      one lane per row of either source and per entry: LUT index range, finite z, event_ptr -> status
@@ -33,6 +33,8 @@
 
 #pragma clang fp contract(off)
 
+#include "builder_common.h"
+
 namespace gnn {
 namespace {
 
@@ -42,10 +44,8 @@ constexpr int kGraphSegs = kChambers * kChambers;      // 441: the pairs form a 
 constexpr int kWave = 64;
 constexpr int kLayerHits = 8;                          // hits of one signed layer value != 0: <= 3 chambers x 2 sources
 constexpr int kMaxEntries = 0x7FFFFFFF / kGraphSegs;
-constexpr float kPiF = (float)M_PI;                    // numpy rounds np.pi / 2 np.pi to float32 against float32 data
-constexpr float kTwoPiF = (float)(2.0 * M_PI);
 constexpr float kCutF = 10e30f;                        // gnn/Muon_graph.py:60: 10e30, compared in float32
-constexpr int kStatusIndex = 1, kStatusFinite = 2, kStatusEvents = 4;
+constexpr int kMgStatusIndex = 1, kMgStatusFinite = 2, kMgStatusEvents = 4;   // (not the hit builders' bits)
 constexpr int kFlagPresent = 1, kFlagWritten = 2, kFlagVpMissing = 4;
 constexpr unsigned kAllChambers = (1u << kChambers) - 1;
 constexpr int8_t kEmpty = -128;
@@ -76,18 +76,6 @@ __device__ __forceinline__ void entry_rows(const gnn_emtf_hits_t &h, int64_t e, 
     *len = min(b - a, (int64_t)0x7FFFFFFF);
 }
 
-// gnn/Muon_graph.py:60-83 with the default thresholds, float32, in the reference's order of operations
-__device__ __forceinline__ bool keep_pair(float r1, float p1, float z1, float r2, float p2, float z2)
-{
-    float dphi = p2 - p1;
-    if (dphi > kPiF) dphi = dphi - kTwoPiF;
-    if (dphi < -kPiF) dphi = dphi + kTwoPiF;
-    const float dz = z2 - z1, dr = r2 - r1;
-    const float slope = dphi / dr;
-    const float z0 = z1 - (r1 * dz) / dr;
-    return fabsf(slope) < kCutF && fabsf(z0) < kCutF;  // NaN (dr = 0, dphi = 0) compares false, inf too
-}
-
 struct MgWs {
     int32_t *status;
     int32_t *fl, *kmu, *kpu, *cnt, *rows, *hc, *hoff, *goff, *meta, *scnt, *soff, *sums;
@@ -100,22 +88,21 @@ MgWs carve_mg(char *base, int64_t E)
     MgWs w;
     w.E = E;
     w.stride = (E + 64) & ~(int64_t)63;
-    size_t off = 0;
-    auto take = [&](size_t b) { char *p = base ? base + off : nullptr; off += align256(b); return p; };
-    w.status = reinterpret_cast<int32_t *>(take(256));
-    w.fl = reinterpret_cast<int32_t *>(take((size_t)2 * w.stride * 4));
-    w.kmu = reinterpret_cast<int32_t *>(take((size_t)(E + 1) * 4));
-    w.kpu = reinterpret_cast<int32_t *>(take((size_t)(E + 1) * 4));
-    w.cnt = reinterpret_cast<int32_t *>(take((size_t)2 * E * 4));
-    w.rows = reinterpret_cast<int32_t *>(take((size_t)2 * E * kChambers * 4));
-    w.hc = reinterpret_cast<int32_t *>(take((size_t)2 * w.stride * 4));
-    w.hoff = reinterpret_cast<int32_t *>(take((size_t)(E + 1) * 4));
-    w.goff = reinterpret_cast<int32_t *>(take((size_t)(E + 1) * 4));
-    w.meta = reinterpret_cast<int32_t *>(take((size_t)E * 4));
-    w.scnt = reinterpret_cast<int32_t *>(take((size_t)E * 4));
-    w.soff = reinterpret_cast<int32_t *>(take((size_t)(E + 1) * 4));
-    w.sums = reinterpret_cast<int32_t *>(take((size_t)scan_sums_words(E) * 4));
-    w.bytes = off + 256;
+    Carver c{base};
+    w.status = c.take<int32_t>(64);
+    w.fl = c.take<int32_t>(2 * w.stride);
+    w.kmu = c.take<int32_t>(E + 1);
+    w.kpu = c.take<int32_t>(E + 1);
+    w.cnt = c.take<int32_t>(2 * E);
+    w.rows = c.take<int32_t>(2 * E * kChambers);
+    w.hc = c.take<int32_t>(2 * w.stride);
+    w.hoff = c.take<int32_t>(E + 1);
+    w.goff = c.take<int32_t>(E + 1);
+    w.meta = c.take<int32_t>(E);
+    w.scnt = c.take<int32_t>(E);
+    w.soff = c.take<int32_t>(E + 1);
+    w.sums = c.take<int32_t>(scan_sums_words(E));
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -123,13 +110,13 @@ __device__ __forceinline__ void check_source(const gnn_emtf_hits_t &h, int64_t i
 {
     if (i < h.n_rows) {
         const int t = h.type[i], s = h.station[i], r = h.ring[i];
-        if ((unsigned)t >= 5u || (unsigned)s >= 5u || (unsigned)r >= 5u) atomicOr(status, kStatusIndex);
-        if (!isfinite(h.z[i])) atomicOr(status, kStatusFinite);
+        if ((unsigned)t >= 5u || (unsigned)s >= 5u || (unsigned)r >= 5u) atomicOr(status, kMgStatusIndex);
+        if (!isfinite(h.z[i])) atomicOr(status, kMgStatusFinite);
     }
     if (i < E) {
         const int64_t a = h.event_ptr[i], b = h.event_ptr[i + 1];
         if (a > b || b - a > 0x7FFFFFFF || (i == 0 && (a != 0 || h.event_ptr[E] != h.n_rows)))
-            atomicOr(status, kStatusEvents);
+            atomicOr(status, kMgStatusEvents);
     }
 }
 
@@ -390,7 +377,8 @@ __global__ __launch_bounds__(kWave) void k_mg_pairs(gnn_emtf_hits_t mu, gnn_emtf
             const int d1 = pd1[p] + 12, d2 = pd2[p] + 12, q = t - pre[p], n2 = lcnt[d2];
             a = lst[d1 * kLayerHits + q / n2];
             b = lst[d2 * kLayerHits + q % n2];
-            keep = keep_pair(sr[a], sp[a], sz[a], sr[b], sp[b], sz[b]);
+            // gnn/Muon_graph.py:60-83 with the default thresholds: inf (dr = 0) is not kept either
+            keep = keep_pair(sr[a], sp[a], sz[a], sr[b], sp[b], sz[b], kCutF, kCutF);
         }
         const unsigned long long msk = __ballot(keep);
         if (MODE != 0 && keep) {
@@ -481,8 +469,6 @@ MgOut out_of(const gnn_muon_graph_out_t *o)
                  o->graph_hits, o->graph_segments};
 }
 
-char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
-
 // the part both layouts share: checks, deduplication, ordinals, per-entry graph composition
 int prologue(const gnn_emtf_hits_t *mu, const gnn_emtf_hits_t *pu, int64_t E, int muon_only, const MgWs &w,
              hipStream_t s)
@@ -524,8 +510,7 @@ int gnn_muon_graph_sizes(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu,
     const int64_t E = n_entries;
     if (int rc = check_args("gnn_muon_graph_sizes", muon, pu, E)) return rc;
     if (!sizes_out || !hit_ptr || !seg_ptr) return fail(GNN_ERR_BADARG, "gnn_muon_graph_sizes: pointer missing");
-    const size_t need = carve_mg(nullptr, E).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_mg(nullptr, E).bytes)) return rc;
     const MgWs w = carve_mg(align_ws(workspace), E);
     hipError_t err = hipMemsetAsync(sizes_out, 0, sizeof(gnn_muon_graph_sizes_t), s);
     if (err != hipSuccess) return fail(-(int)err, "gnn_muon_graph_sizes: memset failed: %s", hipGetErrorString(err));
@@ -555,8 +540,7 @@ int gnn_muon_graph_fill(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu, 
         return fail(GNN_ERR_BADARG, "gnn_muon_graph_fill: vp arrays missing");
     if (sizes->n_graphs == 0) return 0;
     if (int rc = check_out("gnn_muon_graph_fill", out, sizes->n_segments > 0)) return rc;
-    const size_t need = carve_mg(nullptr, E).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_mg(nullptr, E).bytes)) return rc;
     const MgWs w = carve_mg(align_ws(workspace), E);
     GNN_LAUNCH("k_mg_fill", k_mg_pairs<1>, (unsigned)E, kWave, s, *muon, *pu, E, w.meta, w.rows, w.hoff, w.goff,
                w.soff, nullptr, vp_pt, vp_eta, n_vp, entry_start, out_of(out));
@@ -574,8 +558,7 @@ int gnn_muon_graph_padded(const gnn_emtf_hits_t *muon, const gnn_emtf_hits_t *pu
     if (int rc = check_out("gnn_muon_graph_padded", out, true)) return rc;
     if (!status || n_vp < 0 || (n_vp > 0 && (!vp_pt || !vp_eta)))
         return fail(GNN_ERR_BADARG, "gnn_muon_graph_padded: status or vp arrays missing");
-    const size_t need = carve_mg(nullptr, E).bytes;
-    if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    if (int rc = check_workspace(workspace, workspace_bytes, carve_mg(nullptr, E).bytes)) return rc;
     const MgWs w = carve_mg(align_ws(workspace), E);
     if (int rc = prologue(muon, pu, E, muon_only, w, s)) return rc;
     GNN_LAUNCH("k_mg_padded", k_mg_pairs<2>, (unsigned)E, kWave, s, *muon, *pu, E, w.meta, w.rows, nullptr, nullptr,

@@ -40,7 +40,7 @@ CUDA tensors run csrc/event_graphs.hip (two calls around one read-back of the si
 import numpy as np
 import torch
 
-from .graph_build import _host
+from .graph_build import _check_on_device, _host, _raise_builder_status, wrap_dphi32
 from .hitgraph import HitGraphBatch
 
 BARREL_VOLUMES = (8, 13, 17)      # cell 5: vids
@@ -52,13 +52,11 @@ _STATUS_WORDS = ((EG_STATUS_LAYER, "layer outside int8"), (EG_STATUS_INT32, "mor
                  (EG_STATUS_EVENTS, "malformed event_ptr"), (EG_STATUS_FINITE, "a non-finite r, phi or z"))
 NO_MIN, NO_MAX = -1, 2 ** 63 - 1  # what an absent bound is for the library: every count passes
 
-_PI32 = np.float32(np.pi)
-_TWO_PI32 = np.float32(2 * np.pi)
 _DENSE_HITS = 96                  # the specification tests events up to this size as one dense block
 
 
 def _raise_status(st):
-    raise ValueError("event graph builder status %d (%s)" % (st, ", ".join(w for b, w in _STATUS_WORDS if st & b)))
+    _raise_builder_status("event graph builder", _STATUS_WORDS, st)
 
 
 class EventGraphs:
@@ -169,9 +167,7 @@ def _event_segments(phi, z, lay, dphi_cut, dz_cut):
     layer (a dense block per adjacent-layer pair), then put in start-hit order (the dense N x N masks of a
     detector-size event would not fit)."""
     if lay.shape[0] <= _DENSE_HITS:                      # a small event: cell 8 as it stands, one N x N block
-        d = phi[:, None] - phi[None, :]
-        d = np.where(d > _PI32, d - _TWO_PI32, d)
-        d = np.where(d < -_PI32, d + _TWO_PI32, d)
+        d = wrap_dphi32(phi[:, None] - phi[None, :])
         dz = z[None, :] - z[:, None]
         assert d.dtype == dz.dtype == np.float32
         return np.nonzero(((lay[None, :] - lay[:, None]) == 1) & (np.abs(d) < dphi_cut) & (np.abs(dz) < dz_cut))
@@ -184,9 +180,7 @@ def _event_segments(phi, z, lay, dphi_cut, dz_cut):
         if vals[k + 1] - vals[k] != 1:
             continue
         a, b = order[first[k]:last[k]], order[first[k + 1]:last[k + 1]]        # ascending positions on each layer
-        d = phi[a][:, None] - phi[b][None, :]                                   # cell 7 as cell 8 calls it
-        d = np.where(d > _PI32, d - _TWO_PI32, d)
-        d = np.where(d < -_PI32, d + _TWO_PI32, d)
+        d = wrap_dphi32(phi[a][:, None] - phi[b][None, :])                      # cell 7 as cell 8 calls it
         dz = z[b][None, :] - z[a][:, None]
         assert d.dtype == dz.dtype == np.float32
         ii, jj = np.nonzero((np.abs(d) < dphi_cut) & (np.abs(dz) < dz_cut))
@@ -253,18 +247,14 @@ def build_event_graphs_numpy(r, phi, z, volid, layid, barcode, event_ptr, dphi_m
 
 def _build_device(r, phi, z, volid, layid, barcode, event_ptr, cuts, scale, bounds):
     from . import _lib
-    dev = r.device
-    for name, t in (("phi", phi), ("z", z), ("volid", volid), ("layid", layid), ("barcode", barcode)):
-        if not torch.is_tensor(t) or t.device != dev:
-            raise ValueError("%s must be a tensor on %s like r" % (name, dev))
+    _check_on_device(r.device, phi=phi, z=z, volid=volid, layid=layid, barcode=barcode)
     volid, layid = (t.to(torch.int32).contiguous() for t in (volid, layid))
     barcode = barcode.to(torch.int64).contiguous()
-    ep = torch.from_numpy(event_ptr).to(dev)
+    ep = torch.from_numpy(event_ptr).to(r.device)
     r, phi, z = (t.contiguous() for t in (r, phi, z))
     ws, sizes, hit_ptr, seg_ptr, event_index = _lib.event_graphs_sizes(r, phi, z, volid, layid, barcode, ep, cuts,
                                                                        bounds)
-    if sizes.status:
-        _raise_status(int(sizes.status))
+    _raise_status(int(sizes.status))
     X, src, dst, y, hit_index, layer = _lib.event_graphs_fill(ws, sizes, r, phi, z, barcode,
                                                               int(event_ptr.shape[0]) - 1, cuts, scale)
     batch = HitGraphBatch._from_device_arrays(X, src, dst, y, hit_ptr, seg_ptr)

@@ -38,9 +38,20 @@ INNER_LAYERS = 5          # gnn/graph.py:65: pairs whose first layer is below th
 GB_STATUS_LAYER = 1       # csrc/graph_build.hip: a layer outside [0, n_layers)
 GB_STATUS_INT32 = 2       # more than 2^31 - 1 segments
 GB_STATUS_EVENTS = 4      # event_ptr not 0 .. n_hits, non-decreasing
+_STATUS_WORDS = ((GB_STATUS_LAYER, "layer outside [0, n_layers)"), (GB_STATUS_INT32, "more than 2^31 - 1 segments"),
+                 (GB_STATUS_EVENTS, "malformed event_ptr"))
 
-_PI32 = np.float32(np.pi)
+_PI32 = np.float32(np.pi)             # numpy rounds np.pi and 2 np.pi to float32 against float32 data
 _TWO_PI32 = np.float32(2 * np.pi)
+
+
+def wrap_dphi32(d):
+    """The references' phi wrap (calc_dphi) on a float32 difference: minus f32(2 pi) where > f32(pi), then plus
+    f32(2 pi) where < -f32(pi).  The one numpy statement of csrc/builder_common.h's wrap_dphi."""
+    d = np.asarray(d)
+    assert d.dtype == np.float32
+    d = np.where(d > _PI32, d - _TWO_PI32, d)
+    return np.where(d < -_PI32, d + _TWO_PI32, d)
 
 
 def sector_edges(n_phi_sectors):
@@ -48,10 +59,23 @@ def sector_edges(n_phi_sectors):
     return np.linspace(-np.pi, np.pi, n_phi_sectors + 1), 2 * np.pi / n_phi_sectors / 2
 
 
-def _host(a, what):
+def _host(a, what=None):
     if torch.is_tensor(a):
         a = a.detach().cpu().numpy()
     return np.asarray(a)
+
+
+def _raise_builder_status(builder, words, status):
+    """ValueError for a non-zero status word of a builder: `words` is its ((bit, what it means), ...) table."""
+    if status:
+        raise ValueError("%s status %d (%s)" % (builder, status, ", ".join(w for b, w in words if status & b)))
+
+
+def _check_on_device(dev, **columns):
+    """Every column (None: not given) must be a tensor on r's device."""
+    for name, t in columns.items():
+        if t is not None and (not torch.is_tensor(t) or t.device != dev):
+            raise ValueError("%s must be a tensor on %s like r" % (name, dev))
 
 
 def _check_inputs(r, phi, z, layer, layer_pairs, particle_id, event_ptr, n_phi_sectors):
@@ -125,9 +149,7 @@ def _segments(rr, pp, zz, lay, pairs, cut_inner, cut_outer, z0_cut):
             continue
         i = np.repeat(a, b.size)                # the merge's order: left rows, then right rows, in frame order
         j = np.tile(b, a.size)
-        dphi = pp[j] - pp[i]
-        dphi = np.where(dphi > _PI32, dphi - _TWO_PI32, dphi)
-        dphi = np.where(dphi < -_PI32, dphi + _TWO_PI32, dphi)
+        dphi = wrap_dphi32(pp[j] - pp[i])
         dz = zz[j] - zz[i]
         dr = rr[j] - rr[i]
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -185,11 +207,7 @@ def build_graphs_numpy(r, phi, z, layer, pairs, particle_id, event_ptr, n_phi_se
 
 def _build_device(r, phi, z, layer, pairs, particle_id, event_ptr, n_phi_sectors, cuts, feature_scale):
     from . import _lib
-    dev = r.device
-    for name, t in (("phi", phi), ("z", z), ("layer", layer)) + ((("particle_id", particle_id),)
-                                                                 if particle_id is not None else ()):
-        if not torch.is_tensor(t) or t.device != dev:
-            raise ValueError("%s must be a tensor on %s like r" % (name, dev))
+    _check_on_device(r.device, phi=phi, z=z, layer=layer, particle_id=particle_id)
     layer = layer.to(torch.int32).contiguous()
     n = int(r.shape[0])
     if n:
@@ -201,13 +219,10 @@ def _build_device(r, phi, z, layer, pairs, particle_id, event_ptr, n_phi_sectors
         hi = -1
     n_layers = max(hi, int(pairs.max()) if pairs.size else -1) + 1
     pid = None if particle_id is None else particle_id.to(torch.int64).contiguous()
-    ep = torch.from_numpy(event_ptr).to(dev)
+    ep = torch.from_numpy(event_ptr).to(r.device)
     r, phi, z = (t.contiguous() for t in (r, phi, z))
     ws, sizes, hit_ptr, seg_ptr = _lib.graph_build_sizes(r, phi, z, layer, ep, pairs, n_layers, n_phi_sectors, cuts)
-    if sizes.status:
-        raise ValueError("graph builder status %d (%s)" % (sizes.status, ", ".join(
-            w for b, w in ((GB_STATUS_LAYER, "layer outside [0, n_layers)"), (GB_STATUS_INT32, "more than 2^31 - 1 "
-                           "segments"), (GB_STATUS_EVENTS, "malformed event_ptr")) if sizes.status & b)))
+    _raise_builder_status("graph builder", _STATUS_WORDS, sizes.status)
     X, src, dst, y, hit_index = _lib.graph_build_fill(ws, sizes, pid, ep, pairs, n_layers, n_phi_sectors, cuts,
                                                       feature_scale, n)
     batch = HitGraphBatch._from_device_arrays(X, src, dst, y, hit_ptr, seg_ptr)

@@ -46,7 +46,7 @@ CUDA tensors run csrc/hit_samples.hip (two calls around one read-back of the siz
 import numpy as np
 import torch
 
-from .graph_build import _check_inputs, _host
+from .graph_build import _check_inputs, _check_on_device, _host, _raise_builder_status, wrap_dphi32
 from .hitgraph import HitGraphBatch
 
 MAX_LAYER_HITS = 16       # csrc/hit_samples.hip: the top-K list is unrolled per K
@@ -59,8 +59,6 @@ _STATUS_WORDS = ((HS_STATUS_LAYER, "layer outside [0, n_det_layers)"),
                  (HS_STATUS_INT32, "more than 2^31 - 1 sample hits or segments"),
                  (HS_STATUS_EVENTS, "malformed event_ptr"), (HS_STATUS_FINITE, "a non-finite r, phi or z"))
 
-_PI32 = np.float32(np.pi)
-_TWO_PI32 = np.float32(2 * np.pi)
 _NAN_KEY = np.uint32(0x7FC00000)
 
 
@@ -73,10 +71,7 @@ def segment_pattern(n_det_layers, n_layer_hits):
 
 def calc_dphi32(phi1, phi2):
     """Cell 9 calc_dphi on float32: phi2 - phi1 wrapped against float32(pi)."""
-    d = np.asarray(phi2 - phi1)
-    assert d.dtype == np.float32
-    d = np.where(d > _PI32, d - _TWO_PI32, d)
-    return np.where(d < -_PI32, d + _TWO_PI32, d)
+    return wrap_dphi32(phi2 - phi1)
 
 
 def eta32(r, z):
@@ -189,9 +184,9 @@ def build_hit_samples_numpy(r, phi, z, layer, particle_id, event_ptr, n_det_laye
     ep = np.asarray(event_ptr, dtype=np.int64)
     n, E = r.shape[0], ep.shape[0] - 1
     if n and (layer.min() < 0 or layer.max() >= L):
-        raise ValueError("hit-sample status %d (%s)" % (HS_STATUS_LAYER, _STATUS_WORDS[0][1]))
+        _raise_builder_status("hit-sample", _STATUS_WORDS, HS_STATUS_LAYER)
     if not (np.isfinite(r).all() and np.isfinite(phi).all() and np.isfinite(z).all()):
-        raise ValueError("hit-sample status %d (%s)" % (HS_STATUS_FINITE, _STATUS_WORDS[3][1]))
+        _raise_builder_status("hit-sample", _STATUS_WORDS, HS_STATUS_FINITE)
     NH, NE = L * K, K * K * (L - 1)
     evt = np.repeat(np.arange(E, dtype=np.int64), np.diff(ep))
     rows = np.arange(n, dtype=np.int64)
@@ -214,7 +209,7 @@ def build_hit_samples_numpy(r, phi, z, layer, particle_id, event_ptr, n_det_laye
     trk = np.stack([kept[gs[is_s] + l] for l in range(L)], axis=1) if is_s.any() else np.zeros((0, L), np.int64)
     S = trk.shape[0]
     if S * NH >= 2 ** 31 or S * NE >= 2 ** 31:
-        raise ValueError("hit-sample status %d (%s)" % (HS_STATUS_INT32, _STATUS_WORDS[1][1]))
+        _raise_builder_status("hit-sample", _STATUS_WORDS, HS_STATUS_INT32)
     keys = np.stack([evt[trk[:, 0]], pid[trk[:, 0]]], axis=1) if S else np.zeros((0, 2), np.int64)
     # cells 9 and 15: the K nearest kept hits per (sample, layer)
     cand = np.zeros((S, L, K), dtype=np.int64)
@@ -254,19 +249,14 @@ def build_hit_samples_numpy(r, phi, z, layer, particle_id, event_ptr, n_det_laye
 
 def _build_device(r, phi, z, layer, particle_id, event_ptr, L, K, n_seed, feature_scale):
     from . import _lib
-    dev = r.device
-    for name, t in (("phi", phi), ("z", z), ("layer", layer), ("particle_id", particle_id)):
-        if not torch.is_tensor(t) or t.device != dev:
-            raise ValueError("%s must be a tensor on %s like r" % (name, dev))
+    _check_on_device(r.device, phi=phi, z=z, layer=layer, particle_id=particle_id)
     layer = layer.to(torch.int32).contiguous()
     pid = particle_id.to(torch.int64).contiguous()
-    ep = torch.from_numpy(event_ptr).to(dev)
+    ep = torch.from_numpy(event_ptr).to(r.device)
     r, phi, z = (t.contiguous() for t in (r, phi, z))
     E = int(event_ptr.shape[0]) - 1
     ws, sizes = _lib.hit_samples_sizes(r, phi, z, layer, pid, ep, L, K)
-    if sizes.status:
-        raise ValueError("hit-sample builder status %d (%s)" % (sizes.status, ", ".join(
-            w for b, w in _STATUS_WORDS if sizes.status & b)))
+    _raise_builder_status("hit-sample builder", _STATUS_WORDS, sizes.status)
     X, y, hit_index, src, dst, keys = _lib.hit_samples_fill(ws, sizes, r, phi, z, pid, E, L, K, n_seed,
                                                             feature_scale)
     return HitSamples(X, y, hit_index, keys, src, dst, L, K)

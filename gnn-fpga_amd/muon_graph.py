@@ -56,6 +56,7 @@ and no read-back at all); numpy arrays or CPU tensors run `build_muon_graphs_num
 import numpy as np
 import torch
 
+from .graph_build import _host, _raise_builder_status, wrap_dphi32
 from .hitgraph import HitGraphBatch
 
 HIT_FEATURES = ("vh_sim_z", "vh_sim_theta", "vh_sim_phi", "vh_sim_r", "vh_bend", "vh_sim_tp1", "vh_sim_tp2",
@@ -81,8 +82,6 @@ _STATUS_WORDS = ((MG_STATUS_INDEX, "a type, station or ring outside [0, 5)"), (M
 # per-graph flags of the device builder
 MG_GRAPH_PRESENT, MG_GRAPH_WRITTEN, MG_GRAPH_VP_MISSING = 1, 2, 4
 
-_PI32 = np.float32(np.pi)
-_TWO_PI32 = np.float32(2 * np.pi)
 _CUT32 = np.float32(10e30)                  # Muon_graph.py:60: phi_slope_max = z0_max = 10e30, compared in float32
 
 
@@ -191,14 +190,7 @@ class MuonGraphs:
 
 
 def _raise_status(st):
-    if st:
-        raise ValueError("muon graph builder status %d (%s)" % (st, ", ".join(w for b, w in _STATUS_WORDS if st & b)))
-
-
-def _host(a):
-    if torch.is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a)
+    _raise_builder_status("muon graph builder", _STATUS_WORDS, st)
 
 
 def _columns(src, name, device):
@@ -366,9 +358,7 @@ def build_muon_graphs_numpy(muon, pu, vp_pt, vp_eta, entry_start, muon_only):
             b = np.flatnonzero(signed == l2)
             i = np.repeat(a, b.size)                # the merge on "entry": left rows, then right rows, in frame order
             j = np.tile(b, a.size)
-            dphi = phi[j] - phi[i]
-            dphi = np.where(dphi > _PI32, dphi - _TWO_PI32, dphi)
-            dphi = np.where(dphi < -_PI32, dphi + _TWO_PI32, dphi)
+            dphi = wrap_dphi32(phi[j] - phi[i])
             dz = z[j] - z[i]
             dr = r[j] - r[i]
             with np.errstate(divide="ignore", invalid="ignore"):
