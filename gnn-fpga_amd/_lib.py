@@ -92,6 +92,23 @@ class GnnMuonGraphOut(ctypes.Structure):
                                   "graph_hits", "graph_segments")]
 
 
+GNN_GCN_MAX_LAYERS = 16
+
+
+class GnnGcnAdj(ctypes.Structure):
+    _fields_ = [(n, _f) for n in ("row_cnt", "row_idx", "row_val", "col_cnt", "col_idx", "col_val")] + \
+               [("B", _i64), ("N", _i32), ("W", _i32)]
+
+
+class GnnGcnNet(ctypes.Structure):
+    _fields_ = [(n, _f) for n in ("Wf", "bf", "Wc", "bc")] + \
+               [(n, _f * GNN_GCN_MAX_LAYERS) for n in ("Wn", "bn", "Wg")] + \
+               [("dims", _i32 * (GNN_GCN_MAX_LAYERS + 1))] + \
+               [(n, _i32 * GNN_GCN_MAX_LAYERS) for n in ("off_n", "off_b", "off_g")] + \
+               [(n, _i32) for n in ("off_f", "off_bf", "off_c", "off_bc", "n_params", "n_dims", "F", "residual",
+                                    "max_width")]
+
+
 # name -> (restype, argtypes); must list every function include/gnn_hip.h declares
 SIGNATURES = {
     "gnn_abi_version": (ctypes.c_int, []),
@@ -179,6 +196,13 @@ SIGNATURES = {
     "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
                                                   _f]),
+    "gnn_gcn_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
+    "gnn_gcn_compress_count": (ctypes.c_int, [_f, _i64, _i32, _f, _f, _f, _f]),
+    "gnn_gcn_compress_fill": (ctypes.c_int, [_f, _i64, _i32, _i32, _f, _f, _f, _f, _f]),
+    "gnn_gcn_forward": (ctypes.c_int, [ctypes.POINTER(GnnGcnAdj), ctypes.POINTER(GnnGcnNet), _f, _f, _f, _f]),
+    "gnn_gcn_backward_workspace_bytes": (_sz, [_i64, _i32]),
+    "gnn_gcn_backward": (ctypes.c_int, [ctypes.POINTER(GnnGcnAdj), ctypes.POINTER(GnnGcnNet), _f, _f, _f, _f, _f, _sz,
+                                        _f]),
     "gnn_profile_begin": (ctypes.c_int, [_i32]),
     "gnn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p),
                                        ctypes.POINTER(ctypes.c_float), _i32]),
@@ -1142,6 +1166,114 @@ def segment_metrics_update(e, y, src, thresholds, key_shift, counts, hist, statu
             None if seg_ptr is None else _dev(seg_ptr, torch.int64, "seg_ptr"), G,
             None if per_graph is None else _dev(per_graph, torch.int64, "per_graph"),
             _dev(status, torch.int32, "status"), None if ws is None else ws.data_ptr(), need, st))
+
+
+# ---- graph-convolution classifiers (csrc/gcn.hip) ---------------------------------------------------------------------
+def gcn_supported(N, F, max_width, list_width):
+    return bool(load().gnn_gcn_supported(N, F, max_width, list_width))
+
+
+def gcn_require(N, F, max_width, list_width):
+    """Raises with the limit the shape misses (gnn_last_error names it)."""
+    lib = load()
+    if not lib.gnn_gcn_supported(N, F, max_width, list_width):
+        raise GnnHipError("no HIP kernels for this shape: %s" % lib.gnn_last_error().decode())
+
+
+def gcn_compress(a):
+    """Dense fp32 [B, N, N] on the device -> (row_cnt, row_idx, row_val, col_cnt, col_idx, col_val, W, status):
+    the counts [B, N] int32, the lists [B, N, W] (zero-padded), W >= 1 the widest list.  ONE read-back (W and the
+    status word, bit 0 = a non-finite entry) between the counting and the filling launches."""
+    B, N = int(a.shape[0]), int(a.shape[1])
+    dev = a.device
+    lib = load()
+    with _on(a) as st:
+        ap = _dev(a, torch.float32, "a")
+        row_cnt = torch.empty((B, N), dtype=torch.int32, device=dev)
+        col_cnt = torch.empty((B, N), dtype=torch.int32, device=dev)
+        info = torch.empty(2, dtype=torch.int32, device=dev)
+        _check(lib.gnn_gcn_compress_count(ap, B, N, row_cnt.data_ptr(), col_cnt.data_ptr(), info.data_ptr(), st))
+        width, status = (int(v) for v in info.cpu().numpy())
+        W = max(1, width)
+        idx = torch.zeros((2, B, N, W), dtype=torch.int32, device=dev)
+        val = torch.zeros((2, B, N, W), dtype=torch.float32, device=dev)
+        if status == 0:
+            _check(lib.gnn_gcn_compress_fill(ap, B, N, W, idx[0].data_ptr(), val[0].data_ptr(), idx[1].data_ptr(),
+                                             val[1].data_ptr(), st))
+    return row_cnt, idx[0], val[0], col_cnt, idx[1], val[1], W, status
+
+
+def gcn_adj_struct(adj):
+    """gnn_gcn_adj_t of a SparseAdjacency (or a batch slice of one: the lists of a slice are views)."""
+    s = GnnGcnAdj()
+    for n in ("row_cnt", "row_idx", "col_cnt", "col_idx"):
+        setattr(s, n, _dev(getattr(adj, n), torch.int32, n))
+    s.row_val = _dev(adj.row_val, torch.float32, "row_val")
+    s.col_val = _dev(adj.col_val, torch.float32, "col_val")
+    s.B, s.N, s.W = len(adj), adj.n_nodes, adj.width
+    return s
+
+
+def gcn_net_struct(F, dims, residual, self_int, Wf, bf, layers, Wc, bc):
+    """gnn_gcn_net_t: `layers` = [(Wn, bn, Wg)] (GraphConvSelfInt) or [(None, bl, Wl)] (GraphConv), float32 device
+    tensors; the gradient offsets follow the module's parameter order."""
+    if len(dims) - 1 > GNN_GCN_MAX_LAYERS:
+        raise GnnHipError("no HIP kernels for this shape: %d graph-convolution layers, the kernels take at most %d"
+                          % (len(dims) - 1, GNN_GCN_MAX_LAYERS))
+    s = GnnGcnNet()
+    f32 = torch.float32
+    s.Wf, s.bf = _dev(Wf, f32, "feature_extractor.weight"), _dev(bf, f32, "feature_extractor.bias")
+    s.Wc, s.bc = _dev(Wc, f32, "classifier.weight"), _dev(bc, f32, "classifier.bias")
+    s.off_f, s.off_bf = 0, Wf.numel()
+    off = Wf.numel() + bf.numel()
+    for l, (Wn, bn, Wg) in enumerate(layers):
+        cin = dims[l] + (F if residual else 0)
+        if tuple(Wg.shape) != (dims[l + 1], cin) or bn.numel() != dims[l + 1] or \
+                (Wn is not None and Wn.shape != Wg.shape):
+            raise GnnHipError("layer %d: weight shapes do not match hidden_dims" % l)
+        if Wn is not None:
+            s.Wn[l], s.off_n[l] = _dev(Wn, f32, "node_mod.weight"), off
+            off += Wn.numel()
+            s.bn[l], s.off_b[l] = _dev(bn, f32, "node_mod.bias"), off
+            s.Wg[l], s.off_g[l] = _dev(Wg, f32, "neighbor_mod.weight"), off + bn.numel()
+        else:
+            s.Wg[l], s.off_g[l] = _dev(Wg, f32, "linear.weight"), off
+            s.bn[l], s.off_b[l] = _dev(bn, f32, "linear.bias"), off + Wg.numel()
+        off += bn.numel() + Wg.numel()
+    s.off_c, s.off_bc = off, off + Wc.numel()
+    s.n_params = off + Wc.numel() + 1
+    for l, d in enumerate(dims):
+        s.dims[l] = d
+    s.n_dims, s.F, s.residual, s.max_width = len(dims), F, int(bool(residual)), max(dims)
+    return s
+
+
+def gcn_forward(adj, net, x, train):
+    """Logits [B, N] in one launch; with `train` also H_all [B, n_dims, N, max_width], the post-ReLU h of every
+    layer (columns past a layer's width are not written)."""
+    B, N = len(adj), adj.n_nodes
+    gcn_require(N, net.F, net.max_width, adj.width)
+    with _on(x) as st:
+        a = gcn_adj_struct(adj)
+        out = torch.empty((B, N), dtype=torch.float32, device=x.device)
+        H_all = torch.empty((B, net.n_dims, N, net.max_width), dtype=torch.float32, device=x.device) if train else None
+        _check(load().gnn_gcn_forward(ctypes.byref(a), ctypes.byref(net), _dev(x, torch.float32, "x"), out.data_ptr(),
+                                      None if H_all is None else H_all.data_ptr(), st))
+    return out, H_all
+
+
+def gcn_backward(adj, net, x, H_all, grad_out):
+    """The flat gradient [n_params] (module parameter order): one backward launch and one fixed-order reduction."""
+    lib = load()
+    with _on(x) as st:
+        a = gcn_adj_struct(adj)
+        need = int(lib.gnn_gcn_backward_workspace_bytes(len(adj), net.n_params))
+        ws = _workspace(x.device, need)
+        grads = torch.empty(net.n_params, dtype=torch.float32, device=x.device)
+        _check(lib.gnn_gcn_backward(ctypes.byref(a), ctypes.byref(net), _dev(x, torch.float32, "x"),
+                                    _dev(H_all, torch.float32, "H_all"), _dev(grad_out, torch.float32, "grad_out"),
+                                    grads.data_ptr(), ws.data_ptr(), ws.numel(), st))
+    return grads
 
 
 class profile:

@@ -184,3 +184,85 @@ def nodeclf_apply(model, batch):
                nn_[0].effective_weight(), nn_[0].bias, nn_[2].effective_weight(), nn_[2].bias,
                out.weight, out.bias]
     return _NodeClf.apply(batch, F, D, model.n_iters, *weights)
+
+
+# ---- graph-convolution classifiers (gnn/GCN_Seg_Toy2D.ipynb cells 20-21, gnn/GCN_Toy2D.ipynb cells 11-14): the whole
+# model forward in one launch (csrc/gcn.hip) keeping every layer's post-ReLU h, the backward in one launch plus one
+# fixed-order reduction over the graphs.  No gradient for x or the adjacency -----------------------------------------
+def _gcn_net(model, params):
+    """gnn_gcn_net_t of a GCN/GCRNBinaryClassifier over `params` (its parameters, module order, detached)."""
+    from .gcn import GraphConvSelfInt
+    it = iter(params)
+    Wf, bf = next(it), next(it)
+    self_int = all(isinstance(gc, GraphConvSelfInt) for gc in model.gc_layers)
+    layers = []
+    for _ in model.gc_layers:
+        if self_int:
+            Wn, bn, Wg = next(it), next(it), next(it)          # node_mod.weight, node_mod.bias, neighbor_mod.weight
+            layers.append((Wn, bn, Wg))
+        else:
+            Wl, bl = next(it), next(it)                        # linear.weight, linear.bias
+            layers.append((None, bl, Wl))
+    Wc, bc = next(it), next(it)
+    return _lib.gcn_net_struct(model.input_dim, model.hidden_dims, model.residual, self_int, Wf, bf, layers, Wc, bc)
+
+
+class _Gcn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, adj, x, *params):
+        w = [t.detach().to(torch.float32).contiguous() for t in params]
+        net = _gcn_net(model, w)
+        out, H_all = _lib.gcn_forward(adj, net, x, train=True)
+        ctx.model, ctx.adj, ctx.shapes = model, adj, [p.shape for p in params]
+        ctx.save_for_backward(x, H_all, *w)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, H_all, *w = ctx.saved_tensors
+        net = _gcn_net(ctx.model, w)
+        flat = _lib.gcn_backward(ctx.adj, net, x, H_all, grad_out.to(torch.float32).contiguous())
+        grads, off = [], 0
+        for k, t in enumerate(w):                              # (the flat gradient is in module parameter order)
+            grads.append(flat[off:off + t.numel()].view(ctx.shapes[k]))
+            off += t.numel()
+        return (None, None, None) + tuple(grads)
+
+
+def gcn_apply(model, x, a):
+    """Forward of a gnn_fpga_amd GCN/GCRNBinaryClassifier: logits [B, N].  `a`: a SparseAdjacency (fast) or a dense
+    [B, N, N] tensor (compressed on every call: slow).  Differentiable w.r.t. the parameters in training mode."""
+    from .gcn import GraphConv, GraphConvSelfInt, SparseAdjacency, compress_adjacency
+    name = type(model).__name__
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise _lib.GnnHipError("%s.forward needs tensors on a ROCm device; there is no CPU path" % name)
+    if x.requires_grad:
+        raise _lib.GnnHipError("%s: x requires grad, and the kernels have no gradient for it" % name)
+    if not isinstance(a, SparseAdjacency):
+        a = compress_adjacency(a)                     # (raises for CPU tensors and for a.requires_grad)
+    if x.dim() != 3 or x.shape[2] != model.input_dim or x.shape[0] != len(a) or x.shape[1] != a.n_nodes:
+        raise _lib.GnnHipError("%s: x %s does not match input_dim %d and the adjacency %s"
+                               % (name, tuple(x.shape), model.input_dim, a.shape))
+    if a.device != x.device:
+        raise _lib.GnnHipError("%s: x is on %s, the adjacency on %s" % (name, x.device, a.device))
+    kinds = {type(gc) for gc in model.gc_layers}
+    if len(kinds) > 1 or not kinds <= {GraphConv, GraphConvSelfInt}:
+        raise _lib.GnnHipError("%s: the layers must all be GraphConv or all GraphConvSelfInt" % name)
+    x = x.to(torch.float32).contiguous()
+    params = list(model.parameters())
+    _lib.gcn_require(a.n_nodes, model.input_dim, max(model.hidden_dims), a.width)
+    if model.training and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        return _Gcn.apply(model, a, x, *params)
+    w = [p.detach().to(torch.float32).contiguous() for p in params]
+    return _lib.gcn_forward(a, _gcn_net(model, w), x, train=False)[0]
+
+
+def gcn_forward_layers(model, x, a):
+    """(logits [B, N], [h_0 .. h_L]) - the post-ReLU h of every layer, [B, N, hidden_dims[l]], as the training
+    forward keeps them (what the tests compare with the reference's per-layer activations)."""
+    from .gcn import SparseAdjacency, compress_adjacency
+    if not isinstance(a, SparseAdjacency):
+        a = compress_adjacency(a)
+    w = [p.detach().to(torch.float32).contiguous() for p in model.parameters()]
+    out, H_all = _lib.gcn_forward(a, _gcn_net(model, w), x.to(torch.float32).contiguous(), train=True)
+    return out, [H_all[:, l, :, :d] for l, d in enumerate(model.hidden_dims)]

@@ -476,3 +476,8 @@ class NodeClassifier(nn.Module):
         if batch.dense_shape:
             y = y.view(batch.dense_shape[0], batch.dense_shape[1])
         return (y, res[1]) if trace else y
+
+
+# the graph-convolution classifiers of the toy notebooks live in gcn.py; they are importable from here like the
+# other model classes
+from .gcn import GraphConv, GraphConvSelfInt, GCNBinaryClassifier, GCRNBinaryClassifier  # noqa: E402,F401

@@ -357,3 +357,97 @@ def acts_events(n_events, n_tracks, n_noise, seed=0, missing=0.1, dup=0.05, dup_
     cat = lambda k, dt: (np.concatenate(cols[k]) if cols[k] else np.zeros(0)).astype(dt)     # noqa: E731
     return ActsColumns(cat("r", np.float32), cat("phi", np.float32), cat("z", np.float32), cat("volid", np.int32),
                        cat("layid", np.int32), cat("barcode", np.int64), event_ptr)
+
+
+# ---- the toy notebooks' graphs (gnn/GCN_Seg_Toy2D.ipynb, gnn/GCN_Toy2D.ipynb): straight 2D tracks through ten detector
+# layers, for the graph-convolution classifiers of gcn.py ---------------------------------------------------------------
+TOY_DET_R = (0.0, 1.0, 2.0, 3.0, 5.0, 7.0, 9.0, 11.0, 13.0, 15.0)
+
+
+def _toy_tracks(rng, n_events, n_tracks, det_r):
+    """[n_events, n_tracks, n_layers] float32 hit positions of straight tracks entering and leaving inside (0, 1)."""
+    xin = rng.uniform(size=(n_events, n_tracks)).astype(np.float32)
+    xout = rng.uniform(size=(n_events, n_tracks)).astype(np.float32)
+    slope = (xout - xin) / np.float32(det_r[-1] - det_r[0])
+    return slope[:, :, None] * det_r[None, None, :] + xin[:, :, None]
+
+
+def toy_segment_graphs_from_hits(hit_x, hit_y, det_r=TOY_DET_R, sigma=0.01):
+    """The segment graphs of GCN_Seg_Toy2D.ipynb (cells 10-17 and 24) from hits sorted within each layer: hit_x, hit_y
+    [n_events, n_layers * n_tracks] (layer-major; positions and track labels).
+
+    A segment joins a hit to a hit of the next layer; segment (l, a, b) = hit a of layer l to hit b of layer l + 1 has
+    index (l T + a) T + b, the order cell 10's np.triu(...).nonzero() gives.  Two segments are adjacent when one ends
+    where the other starts (cell 12's triple loop, here an index comparison), weighted by a Gaussian of their slope
+    difference (cell 17, float32).  Returns X [E, S, 5] = (x0, x1, r0, r1, slope), A [E, S, S], y [E, S], float32;
+    a row of A has at most 2 T non-zeros."""
+    det_r = np.asarray(det_r, dtype=np.float32)
+    L = det_r.shape[0]
+    E = hit_x.shape[0]
+    T = hit_x.shape[1] // L
+    lay, a, b = np.meshgrid(np.arange(L - 1), np.arange(T), np.arange(T), indexing="ij")
+    h0 = (lay * T + a).ravel()                       # first hit of each segment
+    h1 = ((lay + 1) * T + b).ravel()                 # second hit
+    hit_r = np.repeat(det_r, T)
+    seg_x = np.stack([hit_x[:, h0], hit_x[:, h1]], axis=-1).astype(np.float32)
+    seg_r = np.broadcast_to(np.stack([hit_r[h0], hit_r[h1]], axis=-1)[None], seg_x.shape).astype(np.float32)
+    slope = (seg_x[:, :, 1] - seg_x[:, :, 0]) / (seg_r[:, :, 1] - seg_r[:, :, 0])
+    y = (hit_y[:, h0] == hit_y[:, h1]).astype(np.float32)
+    fwd = h1[:, None] == h0[None, :]                 # segment i ends where segment j starts
+    adj = (fwd | fwd.T).astype(np.float32)
+    dslope = slope[:, None, :] - slope[:, :, None]
+    kern = np.exp(-(dslope ** 2) / np.float32(2 * sigma ** 2)).astype(np.float32)
+    X = np.concatenate([seg_x, seg_r, slope[:, :, None]], axis=-1).astype(np.float32)
+    return X, (adj[None] * kern).astype(np.float32), y.reshape(E, -1)
+
+
+def toy_segment_graphs(n_events, seed=0, n_tracks=5, det_r=TOY_DET_R, sigma=0.01):
+    """Seeded inputs of GCN_Seg_Toy2D.ipynb (cells 3, 4, 10-17, 24) without its Python triple loop: n_tracks straight
+    tracks per event, hits sorted within each layer, all 225 (at the defaults) layer-to-next-layer segments.
+    Returns (X [E, 225, 5], A [E, 225, 225] the kernel-weighted segment adjacency, y [E, 225]), float32."""
+    rng = np.random.default_rng(seed)
+    r = np.asarray(det_r, dtype=np.float32)
+    tracks = _toy_tracks(rng, n_events, n_tracks, r).transpose(0, 2, 1)        # [E, L, T]
+    order = np.argsort(tracks, axis=-1)
+    x = np.take_along_axis(tracks, order, axis=-1)
+    return toy_segment_graphs_from_hits(x.reshape(n_events, -1), order.reshape(n_events, -1), det_r, sigma)
+
+
+def toy_hit_graphs(n_events, seed=0, n_tracks=4, seed_size=3, norm="row", det_r=TOY_DET_R):
+    """Seeded inputs of GCN_Toy2D.ipynb (cells 4, 8, 17): hit graphs of n_tracks straight tracks, hits sorted within
+    each layer.  X [E, 40, 3] = (x, r / r_max, seed: the target-track flag on the first seed_size layers), y [E, 40] =
+    hit is on track 0, and A [E, 40, 40]: hits of adjacent layers whose connecting line enters and leaves inside
+    (0, 1), with `norm` = None (binary), "row" (norm_adjacency: row i divided by sum_k a[k, i]; NOT symmetric) or
+    "kw" (kwnorm_adjacency: D (I + a) D with D = diag(1 / sqrt(sum_k (I + a)[k, i])); has a diagonal).
+
+    A hit with no neighbour keeps a ZERO row under "row"; the notebook writes NaN there (1 / 0 times 0), which the
+    compressed adjacency refuses."""
+    if norm not in (None, "row", "kw"):
+        raise ValueError("norm must be None, 'row' or 'kw'")
+    rng = np.random.default_rng(seed)
+    det = np.asarray(det_r, dtype=np.float64)
+    L = det.shape[0]
+    tracks = _toy_tracks(rng, n_events, n_tracks, det.astype(np.float32)).astype(np.float64).transpose(0, 2, 1)
+    order = np.argsort(tracks, axis=-1)
+    x = np.take_along_axis(tracks, order, axis=-1).reshape(n_events, -1)
+    y = order.reshape(n_events, -1)
+    r = np.broadcast_to(np.repeat(det, n_tracks)[None], x.shape)
+    lay = np.broadcast_to(np.repeat(np.arange(L), n_tracks)[None], x.shape)
+    y0 = (y == 0).astype(np.float32)
+    X = np.stack([x, r / r.max(), np.where(lay < seed_size, y0, 0.0)], axis=-1).astype(np.float32)
+    adj_l = np.abs(lay[:, None, :] - lay[:, :, None]) == 1
+    dx = x[:, None, :] - x[:, :, None]
+    dr = r[:, None, :] - r[:, :, None]
+    dr = np.where(dr == 0, 1e-7, dr)
+    slope = dx / dr
+    x0 = x[:, None, :] - slope * r[:, None, :]
+    xn = x[:, None, :] + slope * (r.max() - r[:, None, :])
+    a = (adj_l & (x0 < 1) & (x0 > 0) & (xn < 1) & (xn > 0)).astype(np.float64)
+    if norm == "row":
+        s = a.sum(axis=1)
+        a = np.where(s > 0, 1.0 / np.where(s > 0, s, 1.0), 0.0)[:, :, None] * a
+    elif norm == "kw":
+        ahat = np.eye(a.shape[1])[None] + a
+        d = 1.0 / np.sqrt(ahat.sum(axis=1))
+        a = d[:, :, None] * ahat * d[:, None, :]
+    return X, a.astype(np.float32), y0

@@ -597,6 +597,58 @@ int gnn_segment_metrics_update(const float *e, const float *y, const int32_t *sr
                                const int64_t *seg_ptr, int64_t n_graphs, int64_t *per_graph, int32_t *status,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- graph-convolution classifiers (csrc/gcn.hip; ABI 7) ------------------------------------------------------------
+ * Stand in for GraphConv / GraphConvSelfInt (gnn/GCN_Seg_Toy2D.ipynb cell 20, gnn/GCN_Toy2D.ipynb cell 11),
+ * GCNBinaryClassifier (Seg cell 21, Toy2D cell 13) and GCRNBinaryClassifier (Toy2D cell 14), which multiply a dense
+ * [B, N, N] adjacency into the node features once per layer (torch.matmul(a, x)).  gnn-fpga_amd/gcn.py holds the
+ * modules; exact fp32 throughout.
+ *   gnn_gcn_adj_t: the compressed adjacency of B graphs of N nodes.  row_cnt [B][N] entries of row i, row_idx /
+ *     row_val [B][N][W] their column indices (ascending) and values; col_* the same for the transposed matrix (the
+ *     entries of column j, ascending row index).  W >= 1 is one width for the whole tensor.  Nothing assumes A = A^T.
+ *   gnn_gcn_net_t: the model.  dims [n_dims] = hidden_dims (n_dims - 1 graph-convolution layers, at most
+ *     GNN_GCN_MAX_LAYERS); layer l takes cin = dims[l] (+ F with `residual`, GCRN's [h | x]) to dims[l + 1].
+ *     GraphConvSelfInt: Wn [dout][cin] and bn [dout] = node_mod, Wg [dout][cin] = neighbor_mod.  GraphConv: Wn NULL,
+ *     bn and Wg = linear's bias and weight.  Wf [dims[0]][F], bf: feature_extractor; Wc [dims[last]], bc [1]:
+ *     classifier.  off_*: where each gradient starts in the flat grads [n_params] the backward writes.
+ *   gnn_gcn_supported(N, F, max_width, list_width): 1 if the kernels take the shape; 0 otherwise, and gnn_last_error
+ *     names the limit (the forward keeps two [N][max_width + F] row buffers and x in the 160 KB of LDS).
+ *   gnn_gcn_compress_count: row_cnt, col_cnt [B][N] and info [2] (device int32: the widest list; status, bit 0 = a
+ *     non-finite entry) from the dense fp32 a [B][N][N]; every entry with a != 0 counts.  The caller reads info back
+ *     (the ONE read-back of a compression), sizes the lists (zero-filled) and calls gnn_gcn_compress_fill.
+ *   gnn_gcn_forward: ONE launch, one workgroup per graph: out [B][N] logits from x [B][N][F].  H_all (NULL for
+ *     inference) [B][n_dims][N][max_width] receives the post-ReLU h of every layer, which the backward reads.
+ *   gnn_gcn_backward: ONE launch, one workgroup per graph (per-graph partial sums into the workspace, A^T gz pulled
+ *     over the column lists, no float atomics) and ONE fixed-order reduction launch: grads [n_params] is WRITTEN, the
+ *     same bits in every run.  grad_out [B][N] is the gradient of the logits.  No gradient for x or a.
+ *   Everything is asynchronous on `stream`; no call reads anything back. */
+#define GNN_GCN_MAX_LAYERS 16
+typedef struct {
+    const int32_t *row_cnt, *row_idx;
+    const float *row_val;
+    const int32_t *col_cnt, *col_idx;
+    const float *col_val;
+    int64_t B;
+    int32_t N, W;
+} gnn_gcn_adj_t;
+typedef struct {
+    const float *Wf, *bf, *Wc, *bc;
+    const float *Wn[GNN_GCN_MAX_LAYERS], *bn[GNN_GCN_MAX_LAYERS], *Wg[GNN_GCN_MAX_LAYERS];
+    int32_t dims[GNN_GCN_MAX_LAYERS + 1];
+    int32_t off_n[GNN_GCN_MAX_LAYERS], off_b[GNN_GCN_MAX_LAYERS], off_g[GNN_GCN_MAX_LAYERS];
+    int32_t off_f, off_bf, off_c, off_bc, n_params;
+    int32_t n_dims, F, residual, max_width;
+} gnn_gcn_net_t;
+int gnn_gcn_supported(int32_t N, int32_t F, int32_t max_width, int32_t list_width);
+int gnn_gcn_compress_count(const float *a, int64_t B, int32_t N, int32_t *row_cnt, int32_t *col_cnt, int32_t *info,
+                           void *stream);
+int gnn_gcn_compress_fill(const float *a, int64_t B, int32_t N, int32_t W, int32_t *row_idx, float *row_val,
+                          int32_t *col_idx, float *col_val, void *stream);
+int gnn_gcn_forward(const gnn_gcn_adj_t *adj, const gnn_gcn_net_t *net, const float *x, float *out, float *H_all,
+                    void *stream);
+size_t gnn_gcn_backward_workspace_bytes(int64_t B, int32_t n_params);
+int gnn_gcn_backward(const gnn_gcn_adj_t *adj, const gnn_gcn_net_t *net, const float *x, const float *H_all,
+                     const float *grad_out, float *grads, void *workspace, size_t workspace_bytes, void *stream);
+
 /* bound_out (device, 1 float) = the left side of the GNN_FLAG_EXP_PRODUCT condition;
  * x_absmax (device, [F]) = per-feature max |X|.  Asynchronous on `stream`. */
 int gnn_exp_product_bound(const gnn_params_t *p, const float *x_absmax, float *bound_out,
