@@ -22,8 +22,9 @@
 // so one pulled matrix q serves both the neighbour weights and the input gradient, and A hin is never rebuilt.
 //
 // LDS: two [N][ld] row buffers (ld odd: a thread per row walks its row without bank conflicts) + x [N][F]
-// (+ the layer's weights, transposed, when they fit).  Both in-place row updates (z over h, ghin over gz) are
-// row-local, so a pass owns whole rows: compute - barrier - write.
+// (+ the layer's weights, transposed, when they fit).  The forward, whose rows are F wider, reads x from global
+// memory instead when the row buffers fit and x beside them does not.  Both in-place row updates (z over h, ghin
+// over gz) are row-local, so a pass owns whole rows: compute - barrier - write.
 #include "common.h"
 
 namespace gnn {
@@ -36,7 +37,9 @@ constexpr int kGcnMaxNodes = 4096;
 
 __host__ __device__ inline int gcn_ld(int maxw, int F) { return (maxw + F) | 1; }
 
-inline size_t gcn_fwd_lds(int N, int F, int maxw) { return ((size_t)2 * N * gcn_ld(maxw, F) + (size_t)N * F) * 4; }
+// forward: the two row buffers, which it cannot do without, and x, which it stages beside them when it fits
+inline size_t gcn_fwd_rows_lds(int N, int F, int maxw) { return (size_t)2 * N * gcn_ld(maxw, F) * 4; }
+inline size_t gcn_fwd_lds(int N, int F, int maxw) { return gcn_fwd_rows_lds(N, F, maxw) + (size_t)N * F * 4; }
 inline size_t gcn_bwd_lds(int N, int F, int maxw) { return ((size_t)2 * N * gcn_ld(maxw, 0) + (size_t)N * F + N) * 4; }
 
 // Sums over the nodes of a graph (and over the graphs) run in FOUR interleaved chains, i = 0, 1, 2, 3 mod 4, combined as
@@ -128,6 +131,8 @@ __global__ __launch_bounds__(kBlock) void k_gcn_cols(const float *__restrict__ a
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------
+// XSTAGE: x of the graph is copied to LDS first; without it x is read where it lies (the row buffers left no room)
+template <bool XSTAGE>
 __global__ __launch_bounds__(kBlock) void k_gcn_fwd(gnn_gcn_adj_t adj, gnn_gcn_net_t net, const float *__restrict__ x,
                                                     float *__restrict__ out, float *__restrict__ H_all, int ld,
                                                     int wstage)
@@ -136,15 +141,18 @@ __global__ __launch_bounds__(kBlock) void k_gcn_fwd(gnn_gcn_adj_t adj, gnn_gcn_n
     const int N = adj.N, W = adj.W, F = net.F, L = net.n_dims - 1, maxw = net.max_width;
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    float *hA = lds, *hB = hA + (size_t)N * ld, *xs = hB + (size_t)N * ld, *wl = xs + (size_t)N * F;
+    float *hA = lds, *hB = hA + (size_t)N * ld, *xl = hB + (size_t)N * ld, *wl = xl + (XSTAGE ? (size_t)N * F : 0);
     const int32_t *rcnt = adj.row_cnt + b * N;
     const int32_t *ridx = adj.row_idx + b * N * W;
     const float *rval = adj.row_val + b * N * W;
     float *Hb = H_all ? H_all + b * net.n_dims * N * maxw : nullptr;
 
     x += b * N * F;
-    for (int t = tid; t < N * F; t += kBlock) xs[t] = x[t];
-    __syncthreads();
+    const float *xs = XSTAGE ? xl : x;
+    if (XSTAGE) {
+        for (int t = tid; t < N * F; t += kBlock) xl[t] = x[t];
+        __syncthreads();
+    }
 
     // feature extractor: h0 = relu(x Wf^T + bf)
     {
@@ -341,10 +349,11 @@ int gcn_shape_check(int N, int F, int maxw, int list_width)
     if (list_width < 0 || list_width > N)
         return fail(GNN_ERR_UNSUPPORTED, "gcn: a list width of %d for %d nodes (at most one entry per node)",
                     list_width, N);
-    const size_t need = max(gcn_fwd_lds(N, F, maxw), gcn_bwd_lds(N, F, maxw));
+    const size_t need = max(gcn_fwd_rows_lds(N, F, maxw), gcn_bwd_lds(N, F, maxw));
     if (need > (size_t)kGcnLdsMax)
         return fail(GNN_ERR_UNSUPPORTED, "gcn: %d nodes x (width %d + %d features) needs %zu bytes of LDS for the two "
-                    "row buffers and x, the limit is %d bytes (160 KB per workgroup)", N, maxw, F, need, kGcnLdsMax);
+                    "row buffers of the forward or the backward's two and x, the limit is %d bytes (160 KB per workgroup)",
+                    N, maxw, F, need, kGcnLdsMax);
     return 0;
 }
 
@@ -430,7 +439,8 @@ int gnn_gcn_forward(const gnn_gcn_adj_t *adj, const gnn_gcn_net_t *net, const fl
     if (!x || !out) return fail(GNN_ERR_BADARG, "gnn_gcn_forward: pointer missing");
     const int N = adj->N, F = net->F, maxw = net->max_width;
     const int ld = gcn_ld(maxw, F);
-    size_t lds = gcn_fwd_lds(N, F, maxw);
+    const int xstage = gcn_fwd_lds(N, F, maxw) <= (size_t)kGcnLdsMax;
+    size_t lds = xstage ? gcn_fwd_lds(N, F, maxw) : gcn_fwd_rows_lds(N, F, maxw);
     // the widest layer's two matrices, transposed, beside the row buffers when they fit
     size_t wfl = 0;
     for (int l = 0; l + 1 < net->n_dims; ++l)
@@ -438,10 +448,18 @@ int gnn_gcn_forward(const gnn_gcn_adj_t *adj, const gnn_gcn_net_t *net, const fl
     const int wstage = wfl > 0 && lds + wfl * 4 <= (size_t)kGcnLdsMax;
     if (wstage) lds += wfl * 4;
     static DevOnce attr_done;     // dynamic LDS above 64 KB must be opted into, once per device
-    if (attr_done.need())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gcn_fwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  kGcnLdsMax);
-    GNN_LAUNCH_SH("k_gcn_fwd", k_gcn_fwd, (unsigned)adj->B, kBlock, lds, s, *adj, *net, x, out, H_all, ld, wstage);
+    if (attr_done.need()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gcn_fwd<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kGcnLdsMax);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_gcn_fwd<false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kGcnLdsMax);
+    }
+    if (xstage)
+        GNN_LAUNCH_SH("k_gcn_fwd", k_gcn_fwd<true>, (unsigned)adj->B, kBlock, lds, s, *adj, *net, x, out, H_all, ld,
+                      wstage);
+    else
+        GNN_LAUNCH_SH("k_gcn_fwd", k_gcn_fwd<false>, (unsigned)adj->B, kBlock, lds, s, *adj, *net, x, out, H_all, ld,
+                      wstage);
     return 0;
 }
 

@@ -611,7 +611,8 @@ int gnn_segment_metrics_update(const float *e, const float *y, const int32_t *sr
  *     bn and Wg = linear's bias and weight.  Wf [dims[0]][F], bf: feature_extractor; Wc [dims[last]], bc [1]:
  *     classifier.  off_*: where each gradient starts in the flat grads [n_params] the backward writes.
  *   gnn_gcn_supported(N, F, max_width, list_width): 1 if the kernels take the shape; 0 otherwise, and gnn_last_error
- *     names the limit (the forward keeps two [N][max_width + F] row buffers and x in the 160 KB of LDS).
+ *     names the limit (the forward keeps two [N][max_width + F] row buffers in the 160 KB of LDS, and x beside them
+ *     when it fits; the backward two [N][max_width] row buffers and x).
  *   gnn_gcn_compress_count: row_cnt, col_cnt [B][N] and info [2] (device int32: the widest list; status, bit 0 = a
  *     non-finite entry) from the dense fp32 a [B][N][N]; every entry with a != 0 counts.  The caller reads info back
  *     (the ONE read-back of a compression), sizes the lists (zero-filled) and calls gnn_gcn_compress_fill.

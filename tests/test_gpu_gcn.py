@@ -5,7 +5,8 @@ relative to the tensor's largest entry.  The bound is 4 x the reference's own fp
 (`ref_err_*` of a fixture; the CPU fp32 dense restatement's distance, computed here, for a synthetic case): the kernels
 sum in list order and torch's matmul in its own, two independent fp32 roundings of one value.  Its floor is 16 fp32
 ulp (9.6e-7), for tensors where the reference happens to land exactly.  Every figure is printed before it is
-asserted (run with -s to see them)."""
+asserted (run with -s to see them).  A bound of this kind cannot see ONE dropped, doubled or misindexed list entry where
+the lists are long: tests/test_gpu_gcn_exact.py is the check that does, bit for bit on integer-exact inputs."""
 import numpy as np
 import pytest
 import torch
