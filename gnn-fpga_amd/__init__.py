@@ -5,8 +5,8 @@ ctypes binding, `model.py` the drop-in nn.Module tree, `hitgraph.py` the index-f
 batch/loader, `synth.py` synthetic inputs, `shard.py` event-batch sharding over ranks,
 `graph_build.py` segment graphs from detector hits, `hit_samples.py` the hit classifier's track samples from
 detector hits, `muon_graph.py` the muon trigger graphs from EMTF hits, `event_graphs.py` the ACTS full-event graphs
-from cluster hits, `metrics.py` confusion counts, ROC and AUC, `gcn.py` the toy notebooks' graph-convolution
-classifiers and their compressed adjacency.
+from cluster hits, `select_hits.py` the TrackML barrel hit selection from raw event tables, `metrics.py` confusion
+counts, ROC and AUC, `gcn.py` the toy notebooks' graph-convolution classifiers and their compressed adjacency.
 """
 from .synth import HitGraph  # noqa: F401
 from .hitgraph import HitGraphBatch  # noqa: F401
@@ -15,6 +15,7 @@ from .graph_build import build_graphs  # noqa: F401,E402
 from .hit_samples import HitSamples, build_hit_samples  # noqa: F401,E402
 from .muon_graph import MuonGraphs, build_muon_graphs  # noqa: F401,E402
 from .event_graphs import EventGraphs, build_event_graphs  # noqa: F401,E402
+from .select_hits import BARREL_VLIDS, SelectedHits, select_hits  # noqa: F401,E402
 from .metrics import SegmentMetrics, evaluate  # noqa: F401,E402
 from .gcn import (GraphConv, GraphConvSelfInt, GCNBinaryClassifier, GCRNBinaryClassifier,  # noqa: F401,E402
                   SparseAdjacency, compress_adjacency)

@@ -77,6 +77,10 @@ class GnnEventGraphsSizes(ctypes.Structure):
     _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "n_kept", "n_tasks", "n_tested", "status")]
 
 
+class GnnSelectHitsSizes(ctypes.Structure):
+    _fields_ = [(n, _i64) for n in ("n_kept", "status")]
+
+
 class GnnEmtfHits(ctypes.Structure):
     _fields_ = [(n, _f) for n in ("z", "theta", "phi", "r", "bend", "tp1", "tp2", "station", "ring", "type",
                                   "event_ptr")] + [("n_rows", _i64)]
@@ -192,6 +196,11 @@ SIGNATURES = {
     "gnn_event_graphs_fill": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, ctypes.c_float, ctypes.c_float,
                                              ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                              ctypes.POINTER(GnnEventGraphsSizes), _f, _sz, _f, _f, _f, _f, _f, _f, _f]),
+    "gnn_select_hits_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "gnn_select_hits_sizes": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _f, _f, _f, _i64, _f, _f, _f, _f, _i64, _f, _i64,
+                                             _f, _i32, ctypes.c_float, _i32, _f, _sz, _f, _f, _f]),
+    "gnn_select_hits_fill": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _i64, _i64, _i64, _i32,
+                                            ctypes.POINTER(GnnSelectHitsSizes), _f, _sz, _f, _f, _f, _f, _f, _f, _f, _f]),
     "gnn_metrics_bins": (_i64, [_i32]),
     "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
@@ -1032,6 +1041,53 @@ def event_graphs_fill(ws, sizes, r, phi, z, barcode, n_events, cuts, feature_sca
             *feature_scale, ctypes.byref(sizes), ws.data_ptr(), ws.numel(), X.data_ptr(), src.data_ptr(),
             dst.data_ptr(), y.data_ptr(), hit_index.data_ptr(), layer.data_ptr(), st))
     return X, src, dst, y, hit_index, layer
+
+
+SELECT_HITS_MAX_LAYERS = 64      # include/gnn_hip.h GNN_SELECT_HITS_MAX_LAYERS
+
+
+def select_hits_sizes(hits, truth, particles, event_ptrs, barrel_layers, pt_min, no_missing_hits):
+    """Stage 1 of the hit selection (csrc/select_hits.hip): (workspace, GnnSelectHitsSizes, event_ptr of the selected
+    hits as a host int64 array) - both come back in ONE read-back.  hits: (hit_id int64, x, y, volume_id, layer_id),
+    truth: (hit_id, particle_id), particles: (particle_id, px, py), all device columns; event_ptrs: the three tables'
+    device int64 [E + 1]; barrel_layers: host int32 [L, 2]."""
+    hid, x, y, vol, lay = hits
+    thid, tpid = truth
+    pid, px, py = particles
+    dev, n, nt, npart = x.device, int(x.shape[0]), int(thid.shape[0]), int(pid.shape[0])
+    E = int(event_ptrs[0].shape[0]) - 1
+    tab = np.ascontiguousarray(barrel_layers, dtype=np.int32).reshape(-1, 2)
+    ws = _workspace(dev, load().gnn_select_hits_workspace_bytes(n, nt, npart, E))
+    nw = ctypes.sizeof(GnnSelectHitsSizes) // 8
+    out = torch.empty(nw + E + 1, dtype=torch.int64, device=dev)
+    i64, f32, i32 = torch.int64, torch.float32, torch.int32
+    with _on(x) as st:
+        _check(load().gnn_select_hits_sizes(
+            _dev(hid, i64, "hits hit_id"), _dev(x, f32, "x"), _dev(y, f32, "y"), _dev(vol, i32, "volume_id"),
+            _dev(lay, i32, "layer_id"), n, _dev(event_ptrs[0], i64, "hits event_ptr"),
+            _dev(thid, i64, "truth hit_id"), _dev(tpid, i64, "truth particle_id"), nt,
+            _dev(event_ptrs[1], i64, "truth event_ptr"), _dev(pid, i64, "particles particle_id"), _dev(px, f32, "px"),
+            _dev(py, f32, "py"), npart, _dev(event_ptrs[2], i64, "particles event_ptr"), E, tab.ctypes.data,
+            tab.shape[0], float(pt_min), int(bool(no_missing_hits)), ws.data_ptr(), ws.numel(), out.data_ptr(),
+            out[nw:].data_ptr(), st))
+    sizes, host = _read_back(GnnSelectHitsSizes, out)
+    return ws, sizes, host[nw:].copy()
+
+
+def select_hits_fill(ws, sizes, hid, x, y, z, phi, n_truth, n_particles, n_events, no_missing_hits):
+    """Stage 2: (r, phi, z float32, layer int32, particle_id, hit_id, row int64), n_kept entries each."""
+    dev, K = ws.device, int(sizes.n_kept)
+    f32, i64 = torch.float32, torch.int64
+    r, ophi, oz = (torch.empty(K, dtype=f32, device=dev) for _ in range(3))
+    layer = torch.empty(K, dtype=torch.int32, device=dev)
+    opid, ohid, row = (torch.empty(K, dtype=i64, device=dev) for _ in range(3))
+    with _on(ws) as st:
+        _check(load().gnn_select_hits_fill(
+            _dev(hid, i64, "hits hit_id"), _dev(x, f32, "x"), _dev(y, f32, "y"), _dev(z, f32, "z"),
+            None if phi is None else _dev(phi, f32, "phi"), int(x.shape[0]), n_truth, n_particles, n_events,
+            int(bool(no_missing_hits)), ctypes.byref(sizes), ws.data_ptr(), ws.numel(), r.data_ptr(), ophi.data_ptr(),
+            oz.data_ptr(), layer.data_ptr(), opid.data_ptr(), ohid.data_ptr(), row.data_ptr(), st))
+    return r, ophi, oz, layer, opid, ohid, row
 
 
 def _emtf_hits(cols, n_rows):

@@ -1,5 +1,6 @@
-// builder_common.h - what the GPU builders (graph_build, hit_samples, muon_graph, event_graphs) share: the reference's
-// float32 arithmetic, the event of a row, the hit builders' status bits, workspace carving and argument checks.
+// builder_common.h - what the GPU builders (graph_build, hit_samples, muon_graph, event_graphs, select_hits) share:
+// the reference's float32 arithmetic, the event of a row, the hit builders' status bits, workspace carving and
+// argument checks.
 // Include it AFTER the unit's own `#pragma clang fp contract(off)`: these functions are compiled under the includer's setting.
 #pragma once
 #include "common.h"
@@ -14,8 +15,8 @@ constexpr float kPiF = (float)M_PI;                    // numpy rounds np.pi / 2
 constexpr float kTwoPiF = (float)(2.0 * M_PI);
 constexpr int64_t kInt32End = (int64_t)1 << 31;        // the first count an int32 index cannot hold
 
-// status bits of the three hit builders (GB_ / HS_ / EG_STATUS_* in Python); muon_graph.hip has its own
-constexpr int kStatusLayer = 1, kStatusInt32 = 2, kStatusEvents = 4, kStatusFinite = 8;
+// status bits of the hit builders (GB_ / HS_ / EG_ / SH_STATUS_* in Python); muon_graph.hip has its own
+constexpr int kStatusLayer = 1, kStatusInt32 = 2, kStatusEvents = 4, kStatusFinite = 8, kStatusDup = 16;
 
 // the references' phi wrap (calc_dphi: gnn/graph.py:38-42, gnn/Muon_graph.py:54-58, cell 9 of the hit classifier's
 // notebook, cell 7 of the full-event one), float32

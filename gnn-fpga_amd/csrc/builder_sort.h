@@ -1,4 +1,4 @@
-// builder_sort.h - the stable radix sort of (u64 key, int32 value) pairs of hit_samples.hip and event_graphs.hip, out
+// builder_sort.h - the stable radix sort of (u64 key, int32 value) pairs of hit_samples.hip, event_graphs.hip and select_hits.hip, out
 // of a workspace piece carved beforehand (the only includers of rocprim among the builders).
 #pragma once
 #include <rocprim/rocprim.hpp>

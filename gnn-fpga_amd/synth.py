@@ -359,6 +359,105 @@ def acts_events(n_events, n_tracks, n_noise, seed=0, missing=0.1, dup=0.05, dup_
                        cat("layid", np.int32), cat("barcode", np.int64), event_ptr)
 
 
+# Raw TrackML event tables as gnn/prepareGraphs.py's select_hits (:53-85) takes them from trackml.dataset.load_event:
+# hits (hit_id int32, x, y, z float32, volume_id, layer_id int32), truth (hit_id, particle_id int64) and particles
+# (particle_id int64, px, py float32), each a dict of columns plus event_ptr int64 [n_events + 1].
+TRACKML_OTHER_LAYERS = ((8, 3), (7, 2), (9, 4), (12, 2), (14, 6), (16, 2), (18, 4))     # dropped by the selection
+
+
+def trackml_events(n_events, n_tracks, n_noise, seed=0, missing=0.1, dup=0.05, dup_equal=0.5, other=0.05,
+                   pt_range=(0.1, 3.0), shared_ids=False, extra_particles=0.1):
+    """Seeded raw tables of `n_events` TrackML-like events for select_hits.select_hits: {"hits", "truth", "particles"}.
+
+    Per event `n_tracks` particles (random 48-bit ids, the same in every event with `shared_ids`; pt uniform in
+    `pt_range`) cross the ten barrel layers of ACTS_BARREL_LAYERS as in `barrel_event`; a fraction `missing` of them
+    misses one layer; a fraction `dup` of the track hits has a second hit on the same layer, `dup_equal` of those at
+    exactly the same (x, y), so the same r; `n_noise` noise hits (particle id 0 in truth, no particle row), two of
+    them on each barrel layer first, so that no layer of an event is empty; a fraction `other` of extra rows lies on
+    (volume, layer) pairs the selection drops, half of them noise, half with a truth particle; a fraction
+    `extra_particles` of extra particle rows has no hit.  Hits are shuffled and numbered 1 .. n in the shuffled order
+    (hit_ids restart in every event); truth and particles are shuffled separately."""
+    rng = np.random.default_rng(seed)
+    radii = np.asarray(BARREL_RADII)
+    lay_v = np.asarray([v for v, _ in ACTS_BARREL_LAYERS])
+    lay_l = np.asarray([l for _, l in ACTS_BARREL_LAYERS])
+    oth = np.asarray(TRACKML_OTHER_LAYERS)
+    L = radii.shape[0]
+    H = {k: [] for k in ("hit_id", "x", "y", "z", "volume_id", "layer_id")}
+    T = {k: [] for k in ("hit_id", "particle_id")}
+    P = {k: [] for k in ("particle_id", "px", "py")}
+    ptr = {k: np.zeros(n_events + 1, dtype=np.int64) for k in ("hits", "truth", "particles")}
+    ids0 = None
+    for e in range(n_events):
+        nt = int(n_tracks)
+        ids = rng.permutation(np.unique(rng.integers(1, 2 ** 48, size=2 * nt + 2)))[:nt]
+        if shared_ids:
+            ids0 = ids if ids0 is None else ids0
+            ids = ids0
+        phi0 = rng.uniform(-np.pi, np.pi, size=(nt, 1))
+        k = rng.uniform(-4e-4, 4e-4, size=(nt, 1))
+        z0 = rng.normal(0.0, 40.0, size=(nt, 1))
+        cot = rng.uniform(-1.0, 1.0, size=(nt, 1))
+        r = radii[None, :] + rng.normal(0.0, 0.1, size=(nt, L))
+        phi = phi0 + k * r
+        z = z0 + r * cot + rng.normal(0.0, 0.5, size=(nt, L))
+        lay = np.broadcast_to(np.arange(L), (nt, L))
+        pid = np.broadcast_to(ids[:, None], (nt, L))
+        skip = np.where(rng.random(size=nt) < missing, rng.integers(0, L, size=nt), -1)
+        have = (lay != skip[:, None]).ravel()
+        R, F, Z, Ly, I = (a.ravel()[have] for a in (r, phi, z, lay, pid))
+        d = np.flatnonzero(rng.random(size=R.shape[0]) < dup)
+        same = rng.random(size=d.shape[0]) < dup_equal
+        nn_ = int(n_noise)
+        nl = np.concatenate([np.repeat(np.arange(L), 2), rng.integers(0, L, size=max(nn_ - 2 * L, 0))])[:max(nn_, 0)]
+        R = np.concatenate([R, np.where(same, R[d], R[d] + rng.normal(0.0, 0.3, size=d.shape[0])),
+                            radii[nl] + rng.normal(0.0, 0.1, size=nl.shape[0])])
+        F = np.concatenate([F, np.where(same, F[d], F[d] + rng.normal(0.0, 1e-3, size=d.shape[0])),
+                            rng.uniform(-np.pi, np.pi, size=nl.shape[0])])
+        Z = np.concatenate([Z, Z[d] + rng.normal(0.0, 0.5, size=d.shape[0]),
+                            rng.uniform(-1000.0, 1000.0, size=nl.shape[0])])
+        Ly = np.concatenate([Ly, Ly[d], nl])
+        I = np.concatenate([I, I[d], np.zeros(nl.shape[0], dtype=np.int64)])
+        V, Li = lay_v[Ly], lay_l[Ly]
+        m = int(rng.binomial(max(R.shape[0], 1), other))
+        pick = rng.integers(0, oth.shape[0], size=m)
+        R = np.concatenate([R, rng.uniform(30.0, 1000.0, size=m)])
+        F = np.concatenate([F, rng.uniform(-np.pi, np.pi, size=m)])
+        Z = np.concatenate([Z, rng.uniform(-3000.0, 3000.0, size=m)])
+        V = np.concatenate([V, oth[pick, 0]])
+        Li = np.concatenate([Li, oth[pick, 1]])
+        I = np.concatenate([I, np.where(rng.random(size=m) < 0.5, 0, ids[rng.integers(0, nt, size=m)] if nt else 0)])
+        n = R.shape[0]
+        order = rng.permutation(n)
+        X, Y = (R * np.cos(F))[order], (R * np.sin(F))[order]
+        H["hit_id"].append(np.arange(1, n + 1))
+        for name, v in (("x", X), ("y", Y), ("z", Z[order]), ("volume_id", V[order]), ("layer_id", Li[order])):
+            H[name].append(v)
+        to = rng.permutation(n)
+        T["hit_id"].append(np.arange(1, n + 1)[to])
+        T["particle_id"].append(I[order][to])
+        nx = int(round(extra_particles * nt))
+        extra = -rng.permutation(np.arange(1, nx + 1))                   # (ids no track has)
+        pt = rng.uniform(pt_range[0], pt_range[1], size=nt + nx)
+        ang = rng.uniform(-np.pi, np.pi, size=nt + nx)
+        po = rng.permutation(nt + nx)
+        P["particle_id"].append(np.concatenate([ids, extra])[po])
+        P["px"].append((pt * np.cos(ang))[po])
+        P["py"].append((pt * np.sin(ang))[po])
+        ptr["hits"][e + 1] = ptr["hits"][e] + n
+        ptr["truth"][e + 1] = ptr["truth"][e] + n
+        ptr["particles"][e + 1] = ptr["particles"][e] + nt + nx
+    cat = lambda d, k, dt: (np.concatenate(d[k]) if d[k] else np.zeros(0)).astype(dt)     # noqa: E731
+    hits = {"hit_id": cat(H, "hit_id", np.int32), "x": cat(H, "x", np.float32), "y": cat(H, "y", np.float32),
+            "z": cat(H, "z", np.float32), "volume_id": cat(H, "volume_id", np.int32),
+            "layer_id": cat(H, "layer_id", np.int32), "event_ptr": ptr["hits"]}
+    truth = {"hit_id": cat(T, "hit_id", np.int64), "particle_id": cat(T, "particle_id", np.int64),
+             "event_ptr": ptr["truth"]}
+    particles = {"particle_id": cat(P, "particle_id", np.int64), "px": cat(P, "px", np.float32),
+                 "py": cat(P, "py", np.float32), "event_ptr": ptr["particles"]}
+    return {"hits": hits, "truth": truth, "particles": particles}
+
+
 # ---- the toy notebooks' graphs (gnn/GCN_Seg_Toy2D.ipynb, gnn/GCN_Toy2D.ipynb): straight 2D tracks through ten detector
 # layers, for the graph-convolution classifiers of gcn.py ---------------------------------------------------------------
 TOY_DET_R = (0.0, 1.0, 2.0, 3.0, 5.0, 7.0, 9.0, 11.0, 13.0, 15.0)

@@ -573,6 +573,54 @@ int gnn_event_graphs_fill(const float *r, const float *phi, const float *z, cons
                           size_t workspace_bytes, float *X, int32_t *src, int32_t *dst, float *y, int64_t *hit_index,
                           int32_t *layer, void *stream);
 
+/* ---- TrackML barrel hits selected from raw event tables on the GPU (csrc/select_hits.hip; ABI 7) ---------------------
+ * Replaces select_hits of gnn/prepareGraphs.py:53-85, which runs on the host in pandas: the barrel (volume, layer)
+ * pairs mapped to layers 0 .. 9 (:55-62), pt and its cut (:64-67), truth merged with the kept particles (:68-69), r
+ * and phi (:71-72), hits merged with truth (:74-76), the optional "hits every layer" filter (:77-80) and the
+ * deduplication by groupby(['particle_id', 'layer']).r.idxmin() (:82-84).  gnn-fpga_amd/select_hits.py is the numpy
+ * specification; the output is bit-identical (phi as given; without it, atan2f(y, x)).  Two calls around ONE host
+ * read-back of the sizes:
+ *   gnn_select_hits_workspace_bytes  device scratch both calls need
+ *   gnn_select_hits_sizes  everything but the gather -> *sizes_out and event_ptr_out [n_events + 1] (DEVICE memory,
+ *                          written asynchronously on `stream`)
+ *   gnn_select_hits_fill   the selected hits' columns into arrays of n_kept entries the caller allocated from a HOST
+ *                          copy of the sizes (the same workspace, not touched in between; the same no_missing_hits)
+ * Inputs (DEVICE, but barrel_layers): hits hit_id int64, x, y, z float32, volume_id, layer_id int32 [n_hits]; truth
+ * hit_id, particle_id int64 [n_truth]; particles particle_id int64, px, py float32 [n_particles]; one event_ptr int64
+ * [n_events + 1] per table (event e owns rows [ptr[e], ptr[e+1]) of it); barrel_layers HOST int32 [n_layers, 2],
+ * n_layers <= GNN_SELECT_HITS_MAX_LAYERS; phi float32 [n_hits] or NULL.
+ * layer = the first k with barrel_layers[k] == (volume_id, layer_id), other rows are dropped; float32, every operation
+ * rounded on its own: pt = sqrt(px px + py py), a particle is kept when pt > pt_min (strictly), r = sqrt(x x + y y);
+ * a hit survives when its hit_id has a truth row in its own event whose particle_id is a kept particle of its own
+ * event (ids compared as int64); with no_missing_hits a particle is kept only if its hits cover n_layers distinct
+ * layers; per (event, particle_id, layer) the hit of smallest r is kept, the lowest row on equal r.  Output: within an
+ * event by particle_id ascending (signed), then layer; event e owns entries event_ptr_out[e] .. event_ptr_out[e+1].
+ * sizes.status (0 = fine): bit 4 an event_ptr not non-decreasing from 0 to its table's rows, bit 8 a non-finite x or
+ * y, bit 16 a hit_id twice in an event's hits or truth rows or a particle_id twice in an event's particles;
+ * gnn_select_hits_fill refuses flagged sizes.  GNN_ERR_BADARG: null pointers, negative sizes, n_events < 1, n_layers
+ * outside 1 .. 64, a NaN pt_min; GNN_ERR_UNSUPPORTED: 2^31 - 1 rows or events, or more.  The output is the same in
+ * every run (no order decided by atomics). */
+#define GNN_SELECT_HITS_MAX_LAYERS 64
+
+typedef struct gnn_select_hits_sizes {
+    int64_t n_kept, status;                     /* selected hits; the status word                                   */
+} gnn_select_hits_sizes_t;
+
+size_t gnn_select_hits_workspace_bytes(int64_t n_hits, int64_t n_truth, int64_t n_particles, int64_t n_events);
+int gnn_select_hits_sizes(const int64_t *hit_id, const float *x, const float *y, const int32_t *volume_id,
+                          const int32_t *layer_id, int64_t n_hits, const int64_t *hit_event_ptr,
+                          const int64_t *truth_hit_id, const int64_t *truth_particle_id, int64_t n_truth,
+                          const int64_t *truth_event_ptr, const int64_t *particle_id, const float *px, const float *py,
+                          int64_t n_particles, const int64_t *particle_event_ptr, int64_t n_events,
+                          const int32_t *barrel_layers, int32_t n_layers, float pt_min, int32_t no_missing_hits,
+                          void *workspace, size_t workspace_bytes, gnn_select_hits_sizes_t *sizes_out,
+                          int64_t *event_ptr_out, void *stream);
+int gnn_select_hits_fill(const int64_t *hit_id, const float *x, const float *y, const float *z, const float *phi,
+                         int64_t n_hits, int64_t n_truth, int64_t n_particles, int64_t n_events,
+                         int32_t no_missing_hits, const gnn_select_hits_sizes_t *sizes, void *workspace,
+                         size_t workspace_bytes, float *r_out, float *phi_out, float *z_out, int32_t *layer_out,
+                         int64_t *particle_id_out, int64_t *hit_id_out, int64_t *row_out, void *stream);
+
 /* ---- scoring a classifier: confusion counts, score histograms (csrc/metrics.hip; ABI 7) ----------------------------
  * Stands in for the evaluation cells of the reference's notebooks (gnn/MPNN_Seg_ACTS*.ipynb, makeROC and the
  * per-sample cells), which flatten Estimator.predict's scores (gnn/estimator.py:137-146) and call sklearn.metrics
