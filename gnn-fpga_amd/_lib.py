@@ -205,6 +205,12 @@ SIGNATURES = {
     "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
     "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
                                                   _f]),
+    "gnn_track_build_workspace_bytes": (_sz, [_i64, _i64]),
+    "gnn_track_build_labels": (ctypes.c_int, [_f, _f, _f, _i64, _i64, _f, _i64, ctypes.c_float, _i32, _i32, _f, _sz, _f,
+                                              _f, _f, _f]),
+    "gnn_track_build_lists": (ctypes.c_int, [_f, _i64, _f, _i64, _i64, _i64, _f, _sz, _f, _f, _f, _f, _f]),
+    "gnn_track_match_workspace_bytes": (_sz, [_i64, _i64]),
+    "gnn_track_match": (ctypes.c_int, [_f, _f, _i64, _f, _i64, _f, _i64, _i32, _f, _sz, _f, _f, _f, _f, _f, _f]),
     "gnn_gcn_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "gnn_gcn_compress_count": (ctypes.c_int, [_f, _i64, _i32, _f, _f, _f, _f]),
     "gnn_gcn_compress_fill": (ctypes.c_int, [_f, _i64, _i32, _i32, _f, _f, _f, _f, _f]),
@@ -1222,6 +1228,63 @@ def segment_metrics_update(e, y, src, thresholds, key_shift, counts, hist, statu
             None if seg_ptr is None else _dev(seg_ptr, torch.int64, "seg_ptr"), G,
             None if per_graph is None else _dev(per_graph, torch.int64, "per_graph"),
             _dev(status, torch.int32, "status"), None if ws is None else ws.data_ptr(), need, st))
+
+
+# ---- track candidates and their matching (csrc/track_build.hip) ---------------------------------------------------------
+TRACKS_MODES = {"components": 0, "best": 1}      # include/gnn_hip.h GNN_TRACKS_COMPONENTS / GNN_TRACKS_BEST
+
+
+def track_build_labels(src, dst, scores, n_hits, hit_ptr, threshold, mode, min_hits):
+    """gnn_track_build_labels: (workspace, root [n_hits] int32, track_of_hit [n_hits] int32, sizes [4] int64 =
+    n_tracks, hits in tracks, kept segments, status) - all on the device, asynchronous, nothing read back.
+    hit_ptr: device int64 [G + 1]."""
+    dev, i32 = scores.device, torch.int32
+    E, G = int(scores.numel()), int(hit_ptr.numel()) - 1
+    ws = _workspace(dev, load().gnn_track_build_workspace_bytes(n_hits, E))
+    root = torch.empty(n_hits, dtype=i32, device=dev)
+    track_of_hit = torch.empty(n_hits, dtype=i32, device=dev)
+    sizes = torch.empty(4, dtype=torch.int64, device=dev)
+    with _on(scores) as st:
+        _check(load().gnn_track_build_labels(
+            _dev(src, i32, "src"), _dev(dst, i32, "dst"), _dev(scores, torch.float32, "scores"), E, n_hits,
+            _dev(hit_ptr, torch.int64, "hit_ptr"), G, float(threshold), TRACKS_MODES[mode], int(min_hits),
+            ws.data_ptr(), ws.numel(), root.data_ptr(), track_of_hit.data_ptr(), sizes.data_ptr(), st))
+    return ws, root, track_of_hit, sizes
+
+
+def track_build_lists(ws, track_of_hit, hit_ptr, n_tracks, n_track_hits):
+    """gnn_track_build_lists from the host copy of the sizes: (track_ptr [n_tracks + 1], track_hits [n_track_hits],
+    track_graph [n_tracks], graph_track_ptr [G + 1]), int32."""
+    dev, i32 = track_of_hit.device, torch.int32
+    n, G = int(track_of_hit.numel()), int(hit_ptr.numel()) - 1
+    track_ptr = torch.empty(n_tracks + 1, dtype=i32, device=dev)
+    track_hits = torch.empty(n_track_hits, dtype=i32, device=dev)
+    track_graph = torch.empty(n_tracks, dtype=i32, device=dev)
+    graph_track_ptr = torch.empty(G + 1, dtype=i32, device=dev)
+    with _on(track_of_hit) as st:
+        _check(load().gnn_track_build_lists(
+            _dev(track_of_hit, i32, "track_of_hit"), n, _dev(hit_ptr, torch.int64, "hit_ptr"), G, n_tracks, n_track_hits,
+            ws.data_ptr(), ws.numel(), track_ptr.data_ptr(), track_hits.data_ptr(), track_graph.data_ptr(),
+            graph_track_ptr.data_ptr(), st))
+    return track_ptr, track_hits, track_graph, graph_track_ptr
+
+
+def track_match(track_of_hit, particle_id, hit_ptr, track_ptr, n_tracks, min_hits):
+    """gnn_track_match: (majority_particle int64, majority_hits, particle_hits, matched int32 - [n_tracks] each -
+    counts [4] int64), on the device, asynchronous."""
+    dev, i32, i64 = track_of_hit.device, torch.int32, torch.int64
+    n, G = int(track_of_hit.numel()), int(hit_ptr.numel()) - 1
+    ws = _workspace(dev, load().gnn_track_match_workspace_bytes(n, n_tracks))
+    maj = torch.empty(n_tracks, dtype=i64, device=dev)
+    maj_hits, part_hits, matched = (torch.empty(n_tracks, dtype=i32, device=dev) for _ in range(3))
+    counts = torch.empty(4, dtype=i64, device=dev)
+    with _on(track_of_hit) as st:
+        _check(load().gnn_track_match(
+            _dev(track_of_hit, i32, "track_of_hit"), _dev(particle_id, i64, "particle_id"), n,
+            _dev(hit_ptr, i64, "hit_ptr"), G, _dev(track_ptr, i32, "track_ptr"), n_tracks, int(min_hits), ws.data_ptr(),
+            ws.numel(), maj.data_ptr(), maj_hits.data_ptr(), part_hits.data_ptr(), matched.data_ptr(), counts.data_ptr(),
+            st))
+    return maj, maj_hits, part_hits, matched, counts
 
 
 # ---- graph-convolution classifiers (csrc/gcn.hip) ---------------------------------------------------------------------

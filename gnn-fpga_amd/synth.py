@@ -166,6 +166,15 @@ def barrel_event(n_tracks, n_noise, n_events=1, seed=0):
                       np.concatenate(cols["particle_id"]).astype(np.int64), event_ptr)
 
 
+def scores_from_labels(y, seed=0):
+    """Seeded float32 stand-ins for a trained classifier's scores, from the segment labels y: true segments score
+    0.55 + 0.45 u, fake ones 0.6 u, u uniform in [0, 1) - at threshold 0.5 every true segment passes and one fake
+    segment in six.  The recipe the track builder's tests and probe share."""
+    y = np.asarray(y).reshape(-1)
+    u = np.random.default_rng(seed).random(y.shape[0]).astype(np.float32)
+    return np.where(y > 0, 0.55 + 0.45 * u, 0.6 * u).astype(np.float32)
+
+
 # gnn/MPNN_HitClassifier.ipynb cells 12-15: 10 detector layers x 5 candidate hits per sample (layer-major), the
 # segments of every adjacent-layer pair in np.where order, X = [r, phi, z, seed] / (1000, pi, 1000, 1)
 HitSamples = namedtuple("HitSamples", ["X", "Ri", "Ro", "y", "src", "dst"])

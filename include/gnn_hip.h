@@ -645,6 +645,58 @@ int gnn_segment_metrics_update(const float *e, const float *y, const int32_t *sr
                                const int64_t *seg_ptr, int64_t n_graphs, int64_t *per_graph, int32_t *status,
                                void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- track candidates from scored segments, and their matching to particles (csrc/track_build.hip; ABI 7) ------------
+ * The reference has no counterpart: it ends at one score per segment (Estimator.predict, gnn/estimator.py:137-146) and
+ * its notebooks draw the scored segments (the draw_sample(..., alpha_labels=True) cells); gnn/Graph_dev.ipynb says
+ * that multi-track finding was not tried.  These entry points follow on from there: hits -> tracks -> track-level
+ * efficiency and fake rate, on the device.  gnn-fpga_amd/tracks.py (build_tracks_numpy, match_tracks_numpy) is the
+ * specification of every array; all results are integers, the same in every run (labels are minima and maxima,
+ * integer atomics only, stable sorts).
+ * A batch: src, dst int32 [n_segments] (src < 0: padded segment, skipped), scores float32 [n_segments], hit_ptr int64
+ * [n_graphs + 1] non-decreasing from 0 to n_hits (graph g owns hits [hit_ptr[g], hit_ptr[g+1])); all DEVICE memory.
+ * Segment j is a CANDIDATE when src[j] >= 0, src[j] != dst[j], both ends inside [0, n_hits) and scores[j] > threshold
+ * (strictly; never for NaN).  KEPT: GNN_TRACKS_COMPONENTS every candidate; GNN_TRACKS_BEST the candidates that are both
+ * the best outgoing candidate of their src and the best incoming candidate of their dst (largest score, -0 = +0, ties
+ * to the smallest segment id).  A hit's root is the smallest hit of its component over the kept segments (undirected);
+ * components of at least min_hits hits are the tracks, numbered in ascending order of root.
+ *   gnn_track_build_workspace_bytes  device scratch of labels + lists (0: a size negative or >= 2^31)
+ *   gnn_track_build_labels  gnn/estimator.py:137-146's scores -> root [n_hits] int32, track_of_hit [n_hits] int32
+ *                           (-1: no track) and sizes_out [4] int64 = {n_tracks, hits in tracks, kept segments, status};
+ *                           asynchronous on `stream`, nothing read back.  status bits: 1 a NaN score on a segment with
+ *                           src >= 0, 2 a kept segment whose hits lie in different graphs, 4 an endpoint outside
+ *                           [0, n_hits) (such a segment is no candidate).
+ *   gnn_track_build_lists   from a HOST copy of sizes_out (the same workspace, not touched in between): track_ptr
+ *                           [n_tracks + 1], track_hits [hits in tracks] (a track's hits in ascending hit id),
+ *                           track_graph [n_tracks] (the graph of the root), graph_track_ptr [n_graphs + 1] (graph g
+ *                           owns tracks [ptr[g], ptr[g+1])); all int32.
+ *   gnn_track_match_workspace_bytes  device scratch of gnn_track_match (0: bad sizes)
+ *   gnn_track_match         what the draw_sample cells leave to the eye: particle_id int64 [n_hits] (ids <= 0: no
+ *                           particle; a particle is a (graph, id) pair) -> per track majority_particle int64 (most
+ *                           hits in the track, ties to the smallest id, 0: noise only), majority_hits, particle_hits
+ *                           (that particle's hits in its graph), matched (2 majority_hits > track size and
+ *                           2 majority_hits > particle_hits), int32 each, and counts [4] int64 WRITTEN with {tracks,
+ *                           matched tracks, particles with >= min_hits hits, those of them that are the majority of a
+ *                           matched track}.
+ * GNN_ERR_BADARG names the argument: sizes negative or >= 2^31, a threshold that is not finite, an unknown mode,
+ * min_hits < 1, n_tracks / n_track_hits that cannot be this workspace's, a missing pointer; a null or short workspace
+ * is GNN_ERR_WORKSPACE. */
+#define GNN_TRACKS_COMPONENTS 0
+#define GNN_TRACKS_BEST 1
+size_t gnn_track_build_workspace_bytes(int64_t n_hits, int64_t n_segments);
+int gnn_track_build_labels(const int32_t *src, const int32_t *dst, const float *scores, int64_t n_segments,
+                           int64_t n_hits, const int64_t *hit_ptr, int64_t n_graphs, float threshold, int32_t mode,
+                           int32_t min_hits, void *workspace, size_t workspace_bytes, int32_t *root,
+                           int32_t *track_of_hit, int64_t *sizes_out, void *stream);
+int gnn_track_build_lists(const int32_t *track_of_hit, int64_t n_hits, const int64_t *hit_ptr, int64_t n_graphs,
+                          int64_t n_tracks, int64_t n_track_hits, void *workspace, size_t workspace_bytes,
+                          int32_t *track_ptr, int32_t *track_hits, int32_t *track_graph, int32_t *graph_track_ptr,
+                          void *stream);
+size_t gnn_track_match_workspace_bytes(int64_t n_hits, int64_t n_tracks);
+int gnn_track_match(const int32_t *track_of_hit, const int64_t *particle_id, int64_t n_hits, const int64_t *hit_ptr,
+                    int64_t n_graphs, const int32_t *track_ptr, int64_t n_tracks, int32_t min_hits, void *workspace,
+                    size_t workspace_bytes, int64_t *majority_particle, int32_t *majority_hits, int32_t *particle_hits,
+                    int32_t *matched, int64_t *counts, void *stream);
+
 /* ---- graph-convolution classifiers (csrc/gcn.hip; ABI 7) ------------------------------------------------------------
  * Stand in for GraphConv / GraphConvSelfInt (gnn/GCN_Seg_Toy2D.ipynb cell 20, gnn/GCN_Toy2D.ipynb cell 11),
  * GCNBinaryClassifier (Seg cell 21, Toy2D cell 13) and GCRNBinaryClassifier (Toy2D cell 14), which multiply a dense

@@ -11,7 +11,7 @@ LIB=gnn-fpga_amd/libgnn_hip.so
 cp $LIB /tmp/ab_a.so
 trap 'cp /tmp/ab_a.so $LIB' EXIT
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Iinclude $FLAG -c -o /tmp/sell_ab.o gnn-fpga_amd/csrc/sell_pipeline.hip 2>/dev/null
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/ab_b.so build/gnn_kernels.o /tmp/sell_ab.o build/backward.o build/plan_build.o build/csr_build.o build/graph_build.o build/metrics.o build/hit_samples.o build/muon_graph.o build/event_graphs.o build/gcn.o build/select_hits.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/ab_b.so build/gnn_kernels.o /tmp/sell_ab.o build/backward.o build/plan_build.o build/csr_build.o build/graph_build.o build/metrics.o build/hit_samples.o build/muon_graph.o build/event_graphs.o build/gcn.o build/select_hits.o build/track_build.o
 for i in 1 2 3; do
   for v in a b; do
     cp /tmp/ab_$v.so $LIB
