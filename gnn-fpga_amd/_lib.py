@@ -218,6 +218,10 @@ SIGNATURES = {
     "gnn_gcn_backward_workspace_bytes": (_sz, [_i64, _i32]),
     "gnn_gcn_backward": (ctypes.c_int, [ctypes.POINTER(GnnGcnAdj), ctypes.POINTER(GnnGcnNet), _f, _f, _f, _f, _f, _sz,
                                         _f]),
+    "gnn_toy_graphs_list_width": (_i32, [_i32, _i32, _i32, _i32]),
+    "gnn_toy_segment_graphs": (ctypes.c_int, [_f, _f, _f, _i64, _i32, _i32, ctypes.c_float, _f, _f, _f, _f, _f, _f]),
+    "gnn_toy_hit_graphs": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _i32, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _f, _f,
+                                          _f, _f, _f, _f]),
     "gnn_profile_begin": (ctypes.c_int, [_i32]),
     "gnn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p),
                                        ctypes.POINTER(ctypes.c_float), _i32]),
@@ -1393,6 +1397,58 @@ def gcn_backward(adj, net, x, H_all, grad_out):
                                     _dev(H_all, torch.float32, "H_all"), _dev(grad_out, torch.float32, "grad_out"),
                                     grads.data_ptr(), ws.data_ptr(), ws.numel(), st))
     return grads
+
+
+GNN_TOY_SEGMENTS, GNN_TOY_HITS = 0, 1
+GNN_TOY_NORMS = {None: 0, "row": 1, "kw": 2}
+
+
+def toy_list_width(kind, L, T, norm=None):
+    """The list width of a toy builder, min(2 T [+ 1 for "kw"], nodes); raises with the limit the shape misses."""
+    lib = load()
+    W = int(lib.gnn_toy_graphs_list_width(kind, L, T, GNN_TOY_NORMS[norm]))
+    if W == 0:
+        raise GnnHipError("no HIP kernels for this shape: %s" % lib.gnn_last_error().decode())
+    return W
+
+
+def toy_segment_graphs(hit_x, hit_y, det_r, L, T, two_sigma2):
+    """gnn_toy_segment_graphs: (X [E, S, 5], y [E, S], row_cnt [E, S], row_idx, row_val [E, S, W]); one launch, nothing
+    read back.  hit_x float32 [E, L T], hit_y int32 [E, L T], det_r float32 [L], all on one device."""
+    E, dev = int(hit_x.shape[0]), hit_x.device
+    S, W = T * T * (L - 1), toy_list_width(GNN_TOY_SEGMENTS, L, T)
+    with _on(hit_x) as st:
+        X = torch.empty((E, S, 5), dtype=torch.float32, device=dev)
+        y = torch.empty((E, S), dtype=torch.float32, device=dev)
+        cnt = torch.empty((E, S), dtype=torch.int32, device=dev)
+        idx = torch.empty((E, S, W), dtype=torch.int32, device=dev)
+        val = torch.empty((E, S, W), dtype=torch.float32, device=dev)
+        _check(load().gnn_toy_segment_graphs(_dev(hit_x, torch.float32, "hit_x"), _dev(hit_y, torch.int32, "hit_y"),
+                                             _dev(det_r, torch.float32, "det_r"), E, L, T, two_sigma2, X.data_ptr(),
+                                             y.data_ptr(), cnt.data_ptr(), idx.data_ptr(), val.data_ptr(), st))
+    return X, y, cnt, idx, val
+
+
+def toy_hit_graphs(hit_x, hit_y, det_r, r_norm, table, L, T, seed_size, norm, target):
+    """gnn_toy_hit_graphs: (X [E, N, 3], y0 [E, N], row_cnt, row_idx, row_val, col_cnt, col_idx, col_val, n_isolated
+    int64 [1] on the device); one launch, nothing read back.  hit_x, det_r float64, r_norm float32 [L], table float64
+    [2 T + 2] (None for norm None)."""
+    E, dev = int(hit_x.shape[0]), hit_x.device
+    N, W = L * T, toy_list_width(GNN_TOY_HITS, L, T, norm)
+    with _on(hit_x) as st:
+        X = torch.empty((E, N, 3), dtype=torch.float32, device=dev)
+        y0 = torch.empty((E, N), dtype=torch.float32, device=dev)
+        cnt = torch.empty((2, E, N), dtype=torch.int32, device=dev)
+        idx = torch.empty((2, E, N, W), dtype=torch.int32, device=dev)
+        val = torch.empty((2, E, N, W), dtype=torch.float32, device=dev)
+        n_iso = torch.empty(1, dtype=torch.int64, device=dev)
+        _check(load().gnn_toy_hit_graphs(_dev(hit_x, torch.float64, "hit_x"), _dev(hit_y, torch.int32, "hit_y"),
+                                         _dev(det_r, torch.float64, "det_r"), _dev(r_norm, torch.float32, "r_norm"),
+                                         None if table is None else _dev(table, torch.float64, "norm_table"), E, L, T,
+                                         seed_size, GNN_TOY_NORMS[norm], target, X.data_ptr(), y0.data_ptr(),
+                                         cnt[0].data_ptr(), idx[0].data_ptr(), val[0].data_ptr(), cnt[1].data_ptr(),
+                                         idx[1].data_ptr(), val[1].data_ptr(), n_iso.data_ptr(), st))
+    return X, y0, cnt[0], idx[0], val[0], cnt[1], idx[1], val[1], n_iso
 
 
 class profile:

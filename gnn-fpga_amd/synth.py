@@ -506,7 +506,7 @@ def toy_segment_graphs_from_hits(hit_x, hit_y, det_r=TOY_DET_R, sigma=0.01):
     dslope = slope[:, None, :] - slope[:, :, None]
     kern = np.exp(-(dslope ** 2) / np.float32(2 * sigma ** 2)).astype(np.float32)
     X = np.concatenate([seg_x, seg_r, slope[:, :, None]], axis=-1).astype(np.float32)
-    return X, (adj[None] * kern).astype(np.float32), y.reshape(E, -1)
+    return X, (adj[None] * kern).astype(np.float32), y.reshape(E, h0.shape[0])
 
 
 def toy_segment_graphs(n_events, seed=0, n_tracks=5, det_r=TOY_DET_R, sigma=0.01):
@@ -519,6 +519,40 @@ def toy_segment_graphs(n_events, seed=0, n_tracks=5, det_r=TOY_DET_R, sigma=0.01
     order = np.argsort(tracks, axis=-1)
     x = np.take_along_axis(tracks, order, axis=-1)
     return toy_segment_graphs_from_hits(x.reshape(n_events, -1), order.reshape(n_events, -1), det_r, sigma)
+
+
+def toy_hit_graphs_from_hits(hit_x, hit_y, det_r=TOY_DET_R, seed_size=3, norm="row", target=0):
+    """The hit graphs of GCN_Toy2D.ipynb (cells 8 and 17 with cell 4's calc_adjacency, norm_adjacency and
+    kwnorm_adjacency) from hits sorted within each layer: hit_x float64 (float32 is widened exactly), hit_y
+    [n_events, n_layers * n_tracks] (layer-major; positions and track labels).  Returns what `toy_hit_graphs`
+    documents, with track `target` as the target track: (X, A, y0)."""
+    if norm not in (None, "row", "kw"):
+        raise ValueError("norm must be None, 'row' or 'kw'")
+    det = np.asarray(det_r, dtype=np.float64)
+    L = det.shape[0]
+    x = np.asarray(hit_x).astype(np.float64)
+    y = np.asarray(hit_y)
+    n_tracks = x.shape[1] // L
+    r = np.broadcast_to(np.repeat(det, n_tracks)[None], x.shape)
+    lay = np.broadcast_to(np.repeat(np.arange(L), n_tracks)[None], x.shape)
+    y0 = (y == target).astype(np.float32)
+    X = np.stack([x, r / det.max(), np.where(lay < seed_size, y0, 0.0)], axis=-1).astype(np.float32)
+    adj_l = np.abs(lay[:, None, :] - lay[:, :, None]) == 1
+    dx = x[:, None, :] - x[:, :, None]
+    dr = r[:, None, :] - r[:, :, None]
+    dr = np.where(dr == 0, 1e-7, dr)
+    slope = dx / dr
+    x0 = x[:, None, :] - slope * r[:, None, :]
+    xn = x[:, None, :] + slope * (det.max() - r[:, None, :])
+    a = (adj_l & (x0 < 1) & (x0 > 0) & (xn < 1) & (xn > 0)).astype(np.float64)
+    if norm == "row":
+        s = a.sum(axis=1)
+        a = np.where(s > 0, 1.0 / np.where(s > 0, s, 1.0), 0.0)[:, :, None] * a
+    elif norm == "kw":
+        ahat = np.eye(a.shape[1])[None] + a
+        d = 1.0 / np.sqrt(ahat.sum(axis=1))
+        a = d[:, :, None] * ahat * d[:, None, :]
+    return X, a.astype(np.float32), y0
 
 
 def toy_hit_graphs(n_events, seed=0, n_tracks=4, seed_size=3, norm="row", det_r=TOY_DET_R):
@@ -534,28 +568,13 @@ def toy_hit_graphs(n_events, seed=0, n_tracks=4, seed_size=3, norm="row", det_r=
         raise ValueError("norm must be None, 'row' or 'kw'")
     rng = np.random.default_rng(seed)
     det = np.asarray(det_r, dtype=np.float64)
-    L = det.shape[0]
     tracks = _toy_tracks(rng, n_events, n_tracks, det.astype(np.float32)).astype(np.float64).transpose(0, 2, 1)
     order = np.argsort(tracks, axis=-1)
     x = np.take_along_axis(tracks, order, axis=-1).reshape(n_events, -1)
-    y = order.reshape(n_events, -1)
-    r = np.broadcast_to(np.repeat(det, n_tracks)[None], x.shape)
-    lay = np.broadcast_to(np.repeat(np.arange(L), n_tracks)[None], x.shape)
-    y0 = (y == 0).astype(np.float32)
-    X = np.stack([x, r / r.max(), np.where(lay < seed_size, y0, 0.0)], axis=-1).astype(np.float32)
-    adj_l = np.abs(lay[:, None, :] - lay[:, :, None]) == 1
-    dx = x[:, None, :] - x[:, :, None]
-    dr = r[:, None, :] - r[:, :, None]
-    dr = np.where(dr == 0, 1e-7, dr)
-    slope = dx / dr
-    x0 = x[:, None, :] - slope * r[:, None, :]
-    xn = x[:, None, :] + slope * (r.max() - r[:, None, :])
-    a = (adj_l & (x0 < 1) & (x0 > 0) & (xn < 1) & (xn > 0)).astype(np.float64)
-    if norm == "row":
-        s = a.sum(axis=1)
-        a = np.where(s > 0, 1.0 / np.where(s > 0, s, 1.0), 0.0)[:, :, None] * a
-    elif norm == "kw":
-        ahat = np.eye(a.shape[1])[None] + a
-        d = 1.0 / np.sqrt(ahat.sum(axis=1))
-        a = d[:, :, None] * ahat * d[:, None, :]
-    return X, a.astype(np.float32), y0
+    return toy_hit_graphs_from_hits(x, order.reshape(n_events, -1), det_r, seed_size, norm)
+
+
+def toy_tracks(n_events, n_tracks, seed=0, det_r=TOY_DET_R):
+    """Seeded [n_events, n_tracks, n_layers] float32 positions of straight tracks (gen_tracks of both notebooks' cell
+    3 / 4, with numpy's Generator): what toy_graphs.sort_toy_tracks starts from."""
+    return _toy_tracks(np.random.default_rng(seed), n_events, n_tracks, np.asarray(det_r, dtype=np.float32))

@@ -750,6 +750,46 @@ size_t gnn_gcn_backward_workspace_bytes(int64_t B, int32_t n_params);
 int gnn_gcn_backward(const gnn_gcn_adj_t *adj, const gnn_gcn_net_t *net, const float *x, const float *H_all,
                      const float *grad_out, float *grads, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the toy notebooks' graphs, built into compressed adjacencies (csrc/toy_graphs.hip; ABI 7) ----------------------
+ * Stand in for the data cells of gnn/GCN_Seg_Toy2D.ipynb (cells 10-17 and 24: cell 12 is a Python triple loop over
+ * events x segments x segments into a dense fp64 [E, S, S] array) and gnn/GCN_Toy2D.ipynb (cells 8 and 17 with cell
+ * 4's calc_adjacency, norm_adjacency and kwnorm_adjacency: three dense fp64 [E, N, N] arrays).  Both builders take an
+ * event's n_layers x n_tracks hits - hit_x [E][L T] positions, layer-major and sorted within a layer, hit_y int32
+ * [E][L T] the sort index (track label) - and write gnn_gcn_adj_t's lists directly: ONE launch each, no dense tensor,
+ * nothing read back.  The list contract is gnn_gcn_compress_fill's: an entry is listed if and only if its fp32 value
+ * is != 0, indices ascend, lists are zero-padded, one width W for the whole tensor.  gnn-fpga_amd/synth.py
+ * (toy_segment_graphs_from_hits, toy_hit_graphs_from_hits) is the specification of every array.  All DEVICE memory.
+ *   gnn_toy_graphs_list_width(kind, L, T, norm): W = min(2 T, nodes), one more with GNN_TOY_NORM_KW's diagonal; 0 when
+ *     the kernels do not take the shape (gnn_last_error names the limit: L >= 2, 1 <= T <= 16, at most 4096 segments
+ *     S = T^2 (L - 1) or hits N = L T per event).
+ *   gnn_toy_segment_graphs: det_r float32 [L]; two_sigma2 = float32(2 sigma^2).  Segment (l, a, b) = hit a of layer l
+ *     to hit b of layer l + 1 has index (l T + a) T + b.  X [E][S][5] = (x0, x1, r0, r1, slope), y [E][S] = the two
+ *     hits share a label, row_cnt [E][S], row_idx / row_val [E][S][W]: the segments that end where this one starts or
+ *     start where it ends, weighted exp(-(slope_j - slope_i)^2 / two_sigma2) in fp32.  The matrix is symmetric bit for
+ *     bit: the column lists are the row lists.
+ *   gnn_toy_hit_graphs: hit_x and det_r fp64; r_norm float32 [L] = det_r / det_r[L - 1]; norm_table fp64 [2 T + 2]
+ *     indexed by a count: GNN_TOY_NORM_ROW {0, 1/1, 1/2, ...}, GNN_TOY_NORM_KW {0, 1/sqrt(1), 1/sqrt(2), ...}, made on
+ *     the host (NULL for GNN_TOY_NORM_NONE).  X [E][N][3] = (x, r_norm, label == target on the first seed_size
+ *     layers), y0 [E][N] = label == target, the row lists and, computed entry by entry and never mirrored, the column
+ *     lists of calc_adjacency's matrix under `norm`; a hit whose column of the binary matrix is empty (the notebook's
+ *     1 / 0) gets a zero row and counts into n_isolated (device int64, WRITTEN; the one atomic counter).
+ * GNN_ERR_BADARG names the argument: an unknown kind or norm, n_events negative or 2^31 and more, two_sigma2 not
+ * positive and finite, a missing pointer; GNN_ERR_UNSUPPORTED names the shape limit. */
+#define GNN_TOY_SEGMENTS 0
+#define GNN_TOY_HITS 1
+#define GNN_TOY_NORM_NONE 0
+#define GNN_TOY_NORM_ROW 1
+#define GNN_TOY_NORM_KW 2
+int32_t gnn_toy_graphs_list_width(int32_t kind, int32_t n_layers, int32_t n_tracks, int32_t norm);
+int gnn_toy_segment_graphs(const float *hit_x, const int32_t *hit_y, const float *det_r, int64_t n_events,
+                           int32_t n_layers, int32_t n_tracks, float two_sigma2, float *X, float *y, int32_t *row_cnt,
+                           int32_t *row_idx, float *row_val, void *stream);
+int gnn_toy_hit_graphs(const double *hit_x, const int32_t *hit_y, const double *det_r, const float *r_norm,
+                       const double *norm_table, int64_t n_events, int32_t n_layers, int32_t n_tracks,
+                       int32_t seed_size, int32_t norm, int32_t target, float *X, float *y0, int32_t *row_cnt,
+                       int32_t *row_idx, float *row_val, int32_t *col_cnt, int32_t *col_idx, float *col_val,
+                       int64_t *n_isolated, void *stream);
+
 /* bound_out (device, 1 float) = the left side of the GNN_FLAG_EXP_PRODUCT condition;
  * x_absmax (device, [F]) = per-feature max |X|.  Asynchronous on `stream`. */
 int gnn_exp_product_bound(const gnn_params_t *p, const float *x_absmax, float *bound_out,
