@@ -7,7 +7,8 @@ batch/loader, `synth.py` synthetic inputs, `shard.py` event-batch sharding over 
 detector hits, `muon_graph.py` the muon trigger graphs from EMTF hits, `event_graphs.py` the ACTS full-event graphs
 from cluster hits, `select_hits.py` the TrackML barrel hit selection from raw event tables, `metrics.py` confusion
 counts, ROC and AUC, `tracks.py` track candidates from scored segments and their matching to particles, `gcn.py` the toy notebooks' graph-convolution classifiers and their compressed adjacency,
-`toy_graphs.py` the toy notebooks' segment and hit graphs built straight into that compressed adjacency.
+`toy_graphs.py` the toy notebooks' segment and hit graphs built straight into that compressed adjacency,
+`cut_study.py` the all-pair histograms and the layer census that choose `build_graphs`' arguments.
 """
 from .synth import HitGraph  # noqa: F401
 from .hitgraph import HitGraphBatch  # noqa: F401
@@ -23,3 +24,4 @@ from .gcn import (GraphConv, GraphConvSelfInt, GCNBinaryClassifier, GCRNBinaryCl
                   SparseAdjacency, compress_adjacency)
 from .toy_graphs import (ToyHitGraphs, ToySegmentGraphs, build_toy_hit_graphs,  # noqa: F401,E402
                          build_toy_segment_graphs, sort_toy_tracks)
+from .cut_study import SegmentCutStudy, count_layer_transitions, study_segment_cuts  # noqa: F401,E402

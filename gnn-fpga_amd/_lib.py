@@ -222,6 +222,11 @@ SIGNATURES = {
     "gnn_toy_segment_graphs": (ctypes.c_int, [_f, _f, _f, _i64, _i32, _i32, ctypes.c_float, _f, _f, _f, _f, _f, _f]),
     "gnn_toy_hit_graphs": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _i32, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _f, _f,
                                           _f, _f, _f, _f]),
+    "gnn_cut_study_workspace_bytes": (_sz, [_i64, _i64, _f, _i32, _i32, _i32, _i32, _i32]),
+    "gnn_cut_study": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _f, _i64, _f, _i32, _i32, _i32, _f, _i32, _f, _i32, _f, _sz,
+                                     _f, _f, _f]),
+    "gnn_layer_census_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "gnn_layer_census": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i64, _i32, _i32, _i64, _f, _sz, _f, _f, _f]),
     "gnn_profile_begin": (ctypes.c_int, [_i32]),
     "gnn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p),
                                        ctypes.POINTER(ctypes.c_float), _i32]),
@@ -1289,6 +1294,41 @@ def track_match(track_of_hit, particle_id, hit_ptr, track_ptr, n_tracks, min_hit
             ws.numel(), maj.data_ptr(), maj_hits.data_ptr(), part_hits.data_ptr(), matched.data_ptr(), counts.data_ptr(),
             st))
     return maj, maj_hits, part_hits, matched, counts
+
+
+# ---- choosing the graph builder's arguments (csrc/graph_build.hip gnn_cut_study, csrc/layer_census.hip) -----------------
+def cut_study(r, phi, z, layer, particle_id, event_ptr, pairs, n_layers, n_phi_sectors, slope_edges, z0_edges):
+    """gnn_cut_study: int64 [P * 2 * (NS + 1) * (NZ + 1) + 1] on the device, the counts and then the status word;
+    asynchronous, nothing read back.  pairs: host int32 [P, 2]; the edges: device float32."""
+    dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32)
+    pp = pairs.ctypes.data if pairs.size else None
+    NS, NZ = int(slope_edges.numel()), int(z0_edges.numel())
+    ws = _workspace(dev, load().gnn_cut_study_workspace_bytes(n, E, pp, pairs.shape[0], n_layers, n_phi_sectors, NS, NZ))
+    m = pairs.shape[0] * 2 * (NS + 1) * (NZ + 1)
+    out = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    with _on(r) as st:
+        _check(load().gnn_cut_study(
+            *_rphiz(r, phi, z), _dev(layer, torch.int32, "layer"), _dev(particle_id, torch.int64, "particle_id"), n,
+            _dev(event_ptr, torch.int64, "event_ptr"), E, pp, pairs.shape[0], n_layers, n_phi_sectors,
+            _dev(slope_edges, torch.float32, "phi_slope_edges"), NS, _dev(z0_edges, torch.float32, "z0_edges"), NZ,
+            ws.data_ptr(), ws.numel(), out.data_ptr(), out[m:].data_ptr(), st))
+    return out
+
+
+def layer_census(r, layer, particle_id, event_ptr, n_layers, skip_particle_id):
+    """gnn_layer_census: int64 [L * L + 1] on the device, the table and then the status word; asynchronous."""
+    dev, n, E = r.device, int(r.shape[0]), int(event_ptr.shape[0]) - 1
+    ws = _workspace(dev, load().gnn_layer_census_workspace_bytes(n, E, n_layers))
+    m = n_layers * n_layers
+    out = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    with _on(r) as st:
+        _check(load().gnn_layer_census(
+            _dev(r, torch.float32, "r"), _dev(layer, torch.int32, "layer"),
+            _dev(particle_id, torch.int64, "particle_id"), n, _dev(event_ptr, torch.int64, "event_ptr"), E, n_layers,
+            int(skip_particle_id is not None), int(skip_particle_id or 0), ws.data_ptr(), ws.numel(), out.data_ptr(),
+            out[m:].data_ptr(), st))
+    return out
 
 
 # ---- graph-convolution classifiers (csrc/gcn.hip) ---------------------------------------------------------------------

@@ -27,15 +27,23 @@ __device__ __forceinline__ float wrap_dphi(float d)
     return d;
 }
 
-// the phi-slope and z0 cut of gnn/graph.py:43-66 and gnn/Muon_graph.py:60-83, float32, in the references' order of
-// operations
-__device__ __forceinline__ bool keep_pair(float r1, float p1, float z1, float r2, float p2, float z2, float slope_max,
-                                          float z0_max)
+// phi_slope and z0 of a hit pair (gnn/graph.py:57-62, gnn/Muon_graph.py:75-80), float32, in the references' order of
+// operations; dr = 0 gives inf or NaN
+__device__ __forceinline__ void pair_slope_z0(float r1, float p1, float z1, float r2, float p2, float z2, float &slope,
+                                              float &z0)
 {
     const float dphi = wrap_dphi(p2 - p1);
     const float dz = z2 - z1, dr = r2 - r1;
-    const float slope = dphi / dr;
-    const float z0 = z1 - (r1 * dz) / dr;
+    slope = dphi / dr;
+    z0 = z1 - (r1 * dz) / dr;
+}
+
+// the phi-slope and z0 cut of gnn/graph.py:43-66 and gnn/Muon_graph.py:60-83
+__device__ __forceinline__ bool keep_pair(float r1, float p1, float z1, float r2, float p2, float z2, float slope_max,
+                                          float z0_max)
+{
+    float slope, z0;
+    pair_slope_z0(r1, p1, z1, r2, p2, z2, slope, z0);
     return fabsf(slope) < slope_max && fabsf(z0) < z0_max;   // NaN (dr = 0, dphi = 0) compares false
 }
 

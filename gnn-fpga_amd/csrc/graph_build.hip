@@ -25,6 +25,14 @@
 //     k_gb_features  one lane per hit: its position in its graph (frame order: a binary search per layer bucket),
 //                    X = float32(float64(v) / scale), hit_index
 //     k_gb_pairs<1>  the same pair test again; each lane writes its row's src, dst, y from the row's offset
+//   gnn_cut_study  (the all-pair histograms of gnn/GraphConstructionDev.ipynb cell 20 and
+//                   gnn/GraphConstructionDev_mu200.ipynb cell 18; gnn-fpga_amd/cut_study.py is the specification)
+//     the staging of gnn_graph_build_sizes, unchanged: k_gb_key .. k_gb_tasks and both scans (stage_gb)
+//     k_cs_pairs     the task loop of k_gb_pairs with a histogram where the cut test is: the l2 tiles carry the
+//                    particle id, each pair's (|phi_slope| bin, |z0| bin) cell of its class (fake / true) is counted in
+//                    an LDS table of 32-bit counters (LDS atomics), the last-by-last cell - where an all-pairs loop puts
+//                    most pairs - in a register and reduced over the wave; the table is added to the int64 counts with
+//                    64-bit atomics when the task ends.  Integer sums only: every run gives the same bits.
 // Nothing is ordered by atomics: two builds of one input give the same bits.
 #include "common.h"
 
@@ -41,6 +49,8 @@ constexpr int kMaxPairs = 128;
 constexpr int kRows = 128;                             // l1 hits per task (one per lane)
 constexpr int kTile = 512;                             // l2 hits per LDS tile
 constexpr int kTaskWgPerCu = 8;
+constexpr int kMaxCells = 4096;                        // (NS + 1) * (NZ + 1) histogram cells per class: 32 KB of LDS
+constexpr int64_t kStudyHitsEnd = (int64_t)1 << 25;    // kRows * (hits of one layer) must fit a 32-bit LDS counter
 
 struct PairTab {                                       // by value: layer_pairs and the cut each pair takes
     int32_t l1[kMaxPairs], l2[kMaxPairs];
@@ -271,6 +281,109 @@ __global__ __launch_bounds__(kRows) void k_gb_pairs(int64_t GP, int P, int L, Pa
     }
 }
 
+// the number of edges <= v (np.searchsorted(edges, v, side="right")); NaN counts as above every edge
+__device__ __forceinline__ int bin_of(const float *edges, int n, float v)
+{
+    if (v != v) return n;
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (edges[mid] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// the histogram twin of k_gb_pairs<0>: the same tasks, rows and tiles; counts [P][2][NS + 1][NZ + 1] (zeroed before)
+__global__ __launch_bounds__(kRows) void k_cs_pairs(int64_t GP, int P, int L, PairTab pt,
+                                                    const int32_t *__restrict__ tbase,
+                                                    const int32_t *__restrict__ bcnt, const int32_t *__restrict__ boff,
+                                                    const float *__restrict__ lr, const float *__restrict__ lphi,
+                                                    const float *__restrict__ lz, const int32_t *__restrict__ lrow,
+                                                    const int64_t *__restrict__ pid,
+                                                    const float *__restrict__ slope_edges, int NS,
+                                                    const float *__restrict__ z0_edges, int NZ,
+                                                    unsigned long long *__restrict__ counts)
+{
+    __shared__ float sr[kTile], sp[kTile], sz[kTile];
+    __shared__ int64_t sid[kTile];
+    extern __shared__ unsigned int cs_dyn[];           // sized by the launch: the table, then the edges
+    const int WZ = NZ + 1, cells = (NS + 1) * WZ;
+    unsigned int *hist = cs_dyn;                       // [class][slope bin][z0 bin]
+    float *sedge = reinterpret_cast<float *>(cs_dyn + 2 * cells);   // [slope edges | z0 edges]
+    const float *es = sedge, *ez = sedge + NS;
+    for (int k = threadIdx.x; k < NS + NZ; k += kRows) sedge[k] = k < NS ? slope_edges[k] : z0_edges[k - NS];
+    for (int k = threadIdx.x; k < 2 * cells; k += kRows) hist[k] = 0;
+    __syncthreads();
+    const float last_s = es[NS - 1], last_z = ez[NZ - 1];
+    const int n_tasks = tbase[GP];
+    for (int t = blockIdx.x; t < n_tasks; t += gridDim.x) {
+        const int64_t gp = last_le(tbase, GP, t), g = gp / P;   // the (graph, pair) of the task
+        const int p = (int)(gp - g * P);
+        const int k1 = (int)(g * L + pt.l1[p]), k2 = (int)(g * L + pt.l2[p]);
+        const int n1 = bcnt[k1], n2 = bcnt[k2], b1 = boff[k1], b2 = boff[k2];
+        const int j = (t - tbase[gp]) * kRows + (int)threadIdx.x;
+        const bool valid = j < n1;
+        float r1 = 0.f, p1 = 0.f, z1 = 0.f;
+        int64_t id1 = 0;
+        if (valid) {
+            r1 = lr[b1 + j];
+            p1 = lphi[b1 + j];
+            z1 = lz[b1 + j];
+            id1 = pid[lrow[b1 + j]];
+        }
+        unsigned int far_fake = 0, far_true = 0;       // the last-by-last cell: both cuts failed
+        for (int t0 = 0; t0 < n2; t0 += kTile) {
+            const int m = min(kTile, n2 - t0);
+            __syncthreads();                           // the previous tile has been read
+            for (int k = threadIdx.x; k < m; k += kRows) {
+                sr[k] = lr[b2 + t0 + k];
+                sp[k] = lphi[b2 + t0 + k];
+                sz[k] = lz[b2 + t0 + k];
+                sid[k] = pid[lrow[b2 + t0 + k]];
+            }
+            __syncthreads();
+            if (valid) {
+                for (int k = 0; k < m; ++k) {
+                    float slope, z0;
+                    pair_slope_z0(r1, p1, z1, sr[k], sp[k], sz[k], slope, z0);   // gnn/graph.py:57-62
+                    const float a = fabsf(slope), b = fabsf(z0);
+                    const bool same = id1 == sid[k];
+                    if (!(a < last_s) && !(b < last_z)) {                        // NaN too
+                        far_true += same;
+                        far_fake += !same;
+                    } else {
+                        atomicAdd(&hist[(same ? cells : 0) + bin_of(es, NS, a) * WZ + bin_of(ez, NZ, b)], 1u);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            far_fake += __shfl_xor(far_fake, s, 64);
+            far_true += __shfl_xor(far_true, s, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            if (far_fake) atomicAdd(&hist[cells - 1], far_fake);
+            if (far_true) atomicAdd(&hist[2 * cells - 1], far_true);
+        }
+        __syncthreads();
+        // (a task sees at most kRows * n2 pairs and check_study keeps n2 below 2^25: 32 bits hold them)
+        for (int k = threadIdx.x; k < 2 * cells; k += kRows) {
+            const unsigned int c = hist[k];
+            if (c) {
+                atomicAdd(counts + (int64_t)p * 2 * cells + k, (unsigned long long)c);
+                hist[k] = 0;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void k_cs_final(const int32_t *__restrict__ status, int64_t *__restrict__ status_out)
+{
+    *status_out = *status;
+}
+
 __global__ __launch_bounds__(kBlock) void k_gb_final(int64_t G, int P, int L, const int32_t *__restrict__ boff,
                                                      const int32_t *__restrict__ rbase, const int32_t *__restrict__ tbase,
                                                      const int32_t *__restrict__ roff, const int32_t *__restrict__ status,
@@ -358,6 +471,44 @@ PairTab pair_tab(const int32_t *pairs, int n_pairs, float psm, float pso)
     return pt;
 }
 
+int check_study(const char *who, int64_t n_hits, int32_t n_slope_edges, int32_t n_z0_edges)
+{
+    if (n_slope_edges < 1 || n_z0_edges < 1)
+        return fail(GNN_ERR_BADARG, "%s: each axis needs at least one edge (got %d and %d)", who, n_slope_edges,
+                    n_z0_edges);
+    if (((int64_t)n_slope_edges + 1) * ((int64_t)n_z0_edges + 1) > kMaxCells)
+        return fail(GNN_ERR_UNSUPPORTED, "%s: (%d + 1) x (%d + 1) histogram cells, at most %d fit the LDS table", who,
+                    n_slope_edges, n_z0_edges, kMaxCells);
+    if (n_hits >= kStudyHitsEnd)
+        return fail(GNN_ERR_UNSUPPORTED, "%s: %lld hits, a study call takes fewer than 2^25 (study the data in chunks "
+                    "and add the counts)", who, (long long)n_hits);
+    return 0;
+}
+
+// the staging the sizes pass and the cut study share: sectors, the (graph, layer) buckets in frame order with r, centred
+// phi and z staged in that order, and the (graph, pair) rows and tasks
+int stage_gb(const char *who, const GbWs &w, const PairTab &pt, const float *r, const float *phi, const float *z,
+             const int32_t *layer, int64_t n, const int64_t *event_ptr, int64_t n_events, int n_pairs, int n_layers,
+             int n_phi_sectors, hipStream_t s)
+{
+    const double step = (M_PI - -M_PI) / n_phi_sectors;
+    const float half = (float)(step / 2);
+    const hipError_t err = hipMemsetAsync(w.status, 0, (size_t)w.head_bytes, s);
+    if (err != hipSuccess) return fail(-(int)err, "%s: memset failed: %s", who, hipGetErrorString(err));
+    GNN_LAUNCH("k_gb_key", k_gb_key, max(grid_for(max(n, n_events)), 1u), kBlock, s, phi, layer, n, event_ptr, n_events,
+               n_phi_sectors, n_layers, step, w.hkey, w.bcnt, w.status);
+    if (int rc = scan_counts(w.bcnt, 0, 1, w.boff, nullptr, w.B, w.sums, s)) return rc;
+    if (n > 0) {
+        GNN_LAUNCH("k_gb_scatter", k_gb_scatter, grid_for(n), kBlock, s, w.hkey, n, w.boff, w.bfill, w.unsorted);
+        GNN_LAUNCH("k_gb_rank", k_gb_rank, grid_for(n), kBlock, s, r, phi, z, n, w.hkey, w.boff, w.bcnt, w.B,
+                   n_phi_sectors, n_layers, step, half, w.unsorted, w.lrow, w.lr, w.lphi, w.lz);
+    }
+    if (w.GP > 0)
+        GNN_LAUNCH("k_gb_tasks", k_gb_tasks, grid_for(w.GP), kBlock, s, w.bcnt, w.GP, n_pairs, n_layers, pt, w.gpc,
+                   w.gp_stride);
+    return scan_counts(w.gpc, w.gp_stride, 2, w.rbase, w.tbase, w.GP, w.sums, s);
+}
+
 }  // namespace
 }  // namespace gnn
 
@@ -394,25 +545,12 @@ int gnn_graph_build_sizes(const float *r, const float *phi, const float *z, cons
         return rc;
     GbWs w = carve_gb(align_ws(workspace), n_hits, n_events, n_layers, n_pairs, n_phi_sectors, rb);
     const PairTab pt = pair_tab(layer_pairs, n_pairs, phi_slope_max, phi_slope_outer_max);
-    const double step = (M_PI - -M_PI) / n_phi_sectors;
-    const float half = (float)(step / 2);
-    hipError_t err = hipMemsetAsync(w.status, 0, (size_t)w.head_bytes, s);
-    if (err == hipSuccess) err = hipMemsetAsync(sizes_out, 0, sizeof(gnn_graph_build_sizes_t), s);
+    hipError_t err = hipMemsetAsync(sizes_out, 0, sizeof(gnn_graph_build_sizes_t), s);
     if (err == hipSuccess && rb > 0) err = hipMemsetAsync(w.rcnt, 0, (size_t)rb * 4, s);
     if (err != hipSuccess) return fail(-(int)err, "gnn_graph_build_sizes: memset failed: %s", hipGetErrorString(err));
-    const int64_t n = n_hits;
-    GNN_LAUNCH("k_gb_key", k_gb_key, max(grid_for(max(n, n_events)), 1u), kBlock, s, phi, layer, n, event_ptr, n_events,
-               n_phi_sectors, n_layers, step, w.hkey, w.bcnt, w.status);
-    if (int rc = scan_counts(w.bcnt, 0, 1, w.boff, nullptr, w.B, w.sums, s)) return rc;
-    if (n > 0) {
-        GNN_LAUNCH("k_gb_scatter", k_gb_scatter, grid_for(n), kBlock, s, w.hkey, n, w.boff, w.bfill, w.unsorted);
-        GNN_LAUNCH("k_gb_rank", k_gb_rank, grid_for(n), kBlock, s, r, phi, z, n, w.hkey, w.boff, w.bcnt, w.B,
-                   n_phi_sectors, n_layers, step, half, w.unsorted, w.lrow, w.lr, w.lphi, w.lz);
-    }
-    if (w.GP > 0)
-        GNN_LAUNCH("k_gb_tasks", k_gb_tasks, grid_for(w.GP), kBlock, s, w.bcnt, w.GP, n_pairs, n_layers, pt, w.gpc,
-                   w.gp_stride);
-    if (int rc = scan_counts(w.gpc, w.gp_stride, 2, w.rbase, w.tbase, w.GP, w.sums, s)) return rc;
+    if (int rc = stage_gb("gnn_graph_build_sizes", w, pt, r, phi, z, layer, n_hits, event_ptr, n_events, n_pairs,
+                          n_layers, n_phi_sectors, s))
+        return rc;
     const int64_t task_bound = rb / kRows + w.GP;
     if (task_bound > 0) {
         const unsigned grid = (unsigned)min(task_bound, (int64_t)device_cus() * kTaskWgPerCu);
@@ -458,6 +596,57 @@ int gnn_graph_build_fill(const int64_t *particle_id, int64_t n_hits, int64_t n_e
                    w.bcnt, w.boff, w.lr, w.lphi, w.lz, nullptr, nullptr, w.roff, w.lout, w.lrow,
                    y ? particle_id : nullptr, src, dst, particle_id ? y : nullptr);
     }
+    return 0;
+}
+
+size_t gnn_cut_study_workspace_bytes(int64_t n_hits, int64_t n_events, const int32_t *layer_pairs, int32_t n_pairs,
+                                     int32_t n_layers, int32_t n_phi_sectors, int32_t n_slope_edges, int32_t n_z0_edges)
+{
+    int64_t rb = 0;
+    if (check_common("gnn_cut_study_workspace_bytes", n_hits, n_events, layer_pairs, n_pairs, n_layers, n_phi_sectors,
+                     &rb) ||
+        check_study("gnn_cut_study_workspace_bytes", n_hits, n_slope_edges, n_z0_edges))
+        return 0;
+    return carve_gb(nullptr, n_hits, n_events, n_layers, n_pairs, n_phi_sectors, 0).bytes;   // no per-row counts
+}
+
+int gnn_cut_study(const float *r, const float *phi, const float *z, const int32_t *layer, const int64_t *particle_id,
+                  int64_t n_hits, const int64_t *event_ptr, int64_t n_events, const int32_t *layer_pairs, int32_t n_pairs,
+                  int32_t n_layers, int32_t n_phi_sectors, const float *phi_slope_edges, int32_t n_slope_edges,
+                  const float *z0_edges, int32_t n_z0_edges, void *workspace, size_t workspace_bytes, int64_t *counts,
+                  int64_t *status, void *stream)
+{
+    ProfChain chain_;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int64_t rb = 0;
+    if (int rc = check_common("gnn_cut_study", n_hits, n_events, layer_pairs, n_pairs, n_layers, n_phi_sectors, &rb))
+        return rc;
+    if (int rc = check_study("gnn_cut_study", n_hits, n_slope_edges, n_z0_edges)) return rc;
+    if ((n_hits > 0 && (!r || !phi || !z || !layer || !particle_id)) || !event_ptr || !phi_slope_edges || !z0_edges ||
+        (n_pairs > 0 && !counts) || !status)
+        return fail(GNN_ERR_BADARG, "gnn_cut_study: pointer missing");
+    if (int rc = check_workspace(workspace, workspace_bytes,
+                                 carve_gb(nullptr, n_hits, n_events, n_layers, n_pairs, n_phi_sectors, 0).bytes))
+        return rc;
+    GbWs w = carve_gb(align_ws(workspace), n_hits, n_events, n_layers, n_pairs, n_phi_sectors, 0);
+    const PairTab pt = pair_tab(layer_pairs, n_pairs, 0.f, 0.f);
+    const int64_t cells = ((int64_t)n_slope_edges + 1) * (n_z0_edges + 1);
+    if (n_pairs > 0) {
+        const hipError_t err = hipMemsetAsync(counts, 0, (size_t)n_pairs * 2 * cells * sizeof(int64_t), s);
+        if (err != hipSuccess) return fail(-(int)err, "gnn_cut_study: memset failed: %s", hipGetErrorString(err));
+    }
+    if (int rc = stage_gb("gnn_cut_study", w, pt, r, phi, z, layer, n_hits, event_ptr, n_events, n_pairs, n_layers,
+                          n_phi_sectors, s))
+        return rc;
+    const int64_t task_bound = rb / kRows + w.GP;
+    if (n_hits > 0 && task_bound > 0) {
+        const unsigned grid = (unsigned)min(task_bound, (int64_t)device_cus() * kTaskWgPerCu);
+        const size_t lds = (size_t)(2 * cells + n_slope_edges + n_z0_edges) * 4;   // at most 40 KB beside the tiles
+        GNN_LAUNCH_SH("k_cs_pairs", k_cs_pairs, grid, kRows, lds, s, w.GP, n_pairs, n_layers, pt, w.tbase, w.bcnt, w.boff, w.lr,
+                   w.lphi, w.lz, w.lrow, particle_id, phi_slope_edges, n_slope_edges, z0_edges, n_z0_edges,
+                   reinterpret_cast<unsigned long long *>(counts));
+    }
+    GNN_LAUNCH("k_cs_final", k_cs_final, 1, 1, s, w.status, status);
     return 0;
 }
 

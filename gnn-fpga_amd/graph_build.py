@@ -139,6 +139,19 @@ def build_graphs(r, phi, z, layer, layer_pairs, *, particle_id=None, event_ptr=N
     return build_graphs_numpy(*cols, pairs, pid, ep, int(n_phi_sectors), cuts, feature_scale)
 
 
+def pair_values(rr, pp, zz, i, j):
+    """gnn/graph.py:57-62 for the hit pairs (i[k], j[k]): (phi_slope, z0), float32, in the reference's order of
+    operations.  The one numpy statement of csrc/builder_common.h's pair_slope_z0; r2 == r1 gives inf or NaN."""
+    dphi = wrap_dphi32(pp[j] - pp[i])
+    dz = zz[j] - zz[i]
+    dr = rr[j] - rr[i]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        slope = dphi / dr
+        z0 = zz[i] - rr[i] * dz / dr
+    assert dphi.dtype == slope.dtype == z0.dtype == np.float32
+    return slope, z0
+
+
 def _segments(rr, pp, zz, lay, pairs, cut_inner, cut_outer, z0_cut):
     """One graph's segments in the reference's order: (start positions, end positions)."""
     starts, ends = [], []
@@ -149,13 +162,7 @@ def _segments(rr, pp, zz, lay, pairs, cut_inner, cut_outer, z0_cut):
             continue
         i = np.repeat(a, b.size)                # the merge's order: left rows, then right rows, in frame order
         j = np.tile(b, a.size)
-        dphi = wrap_dphi32(pp[j] - pp[i])
-        dz = zz[j] - zz[i]
-        dr = rr[j] - rr[i]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            slope = dphi / dr
-            z0 = zz[i] - rr[i] * dz / dr
-        assert dphi.dtype == slope.dtype == z0.dtype == np.float32
+        slope, z0 = pair_values(rr, pp, zz, i, j)
         cut = cut_inner if l1 < INNER_LAYERS else cut_outer
         keep = (np.abs(slope) < cut) & (np.abs(z0) < z0_cut)
         starts.append(i[keep])
