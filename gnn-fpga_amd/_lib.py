@@ -161,6 +161,8 @@ SIGNATURES = {
                                                      _f, _f, _f, _f, _f, _sz, _f]),
     "gnn_plan_shape_supported": (ctypes.c_int, [_i32, _i32]),
     "gnn_plan_limits": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_i32)]),
+    "gnn_plan_route": (ctypes.c_int, [ctypes.POINTER(GnnPlan), ctypes.POINTER(GnnParams), _i32, _i32,
+                                      ctypes.POINTER(_i32)]),
     "gnn_exp_product_bound": (ctypes.c_int, [ctypes.POINTER(GnnParams), _f, _f, _f]),
     "gnn_csr_build_workspace_bytes": (_sz, [_i64, _i64]),
     "gnn_csr_build": (ctypes.c_int, [_f, _f, _i64, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f]),
@@ -827,6 +829,36 @@ def plan_limits(F, D):
     _check(load().gnn_plan_limits(F, D, out))
     return {"tile_hits": out[0], "iter_records": out[1], "chunk_segments": out[2],
             "edge_records": out[3]}
+
+
+# gnn_plan_route: the names of the GNN_ROUTE_* fields, in order, and of the codes of the first, second, third and
+# fifth (include/gnn_hip.h)
+ROUTE_FIELDS = ("records", "input", "family", "fuse_first", "edge", "pack", "iter_lds", "iter2_lds", "cap_a", "cap_b",
+                "edge_lds", "wide_window")
+ROUTE_NAMES = {"records": ("fp32", "bf16", "exact"),
+               "input": (None, "k_input4", "k_input4_bf", "k_input4_x"),
+               "family": ("k_iter", "k_iter2", "k_iter_w", "k_iter_wx"),
+               "edge": ("k_edge", "k_edge_w")}
+
+
+def plan_route(plan, F, D, n_iters, flags=0, training=False):
+    """The kernels the fused forward (`training`: the fused training forward) takes for this plan - a GnnPlan, or a
+    plan object on the GPU -, shape, flags and the route switches of the environment, as the library decides them
+    (gnn_plan_route; no GPU needed for a GnnPlan).  A dict over ROUTE_FIELDS: kernel choices by name, `fuse_first`
+    and `pack` as bools, sizes as ints.  None: the shape has no fused training forward."""
+    g = plan if isinstance(plan, GnnPlan) else plan_struct(plan)
+    p = GnnParams()
+    p.F, p.D, p.flags = F, D, flags
+    out = (_i32 * len(ROUTE_FIELDS))()
+    rc = load().gnn_plan_route(ctypes.byref(g), ctypes.byref(p), n_iters, int(training), out)
+    if rc == GNN_ERR_UNSUPPORTED and training and plan_shape_supported(F, D):
+        return None
+    _check(rc)
+    route = dict(zip(ROUTE_FIELDS, out))
+    for k, names in ROUTE_NAMES.items():
+        route[k] = names[route[k]]
+    route["fuse_first"], route["pack"] = bool(route["fuse_first"]), bool(route["pack"])
+    return route
 
 
 def plan_struct(plan):

@@ -1,6 +1,5 @@
 // builder_common.h - what the GPU builders (graph_build, hit_samples, muon_graph, event_graphs, select_hits) share:
-// the reference's float32 arithmetic, the event of a row, the hit builders' status bits, workspace carving and
-// argument checks.
+// the reference's float32 arithmetic, the event of a row, the hit builders' status bits and argument checks.
 // Include it AFTER the unit's own `#pragma clang fp contract(off)`: these functions are compiled under the includer's setting.
 #pragma once
 #include "common.h"
@@ -84,28 +83,6 @@ __device__ __forceinline__ void check_event_ptr(const int64_t *ep, int64_t E, in
 __device__ __forceinline__ bool event_owns(const int64_t *ep, int64_t e, int64_t i)
 {
     return ep[e] <= i && i < ep[e + 1];
-}
-
-inline char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
-
-// hands out a workspace piece by piece, each piece 256-byte aligned; a null base only adds up the sizes
-struct Carver {
-    char *base;
-    size_t off = 0;
-    template <typename T>
-    T *take(size_t count)
-    {
-        char *p = base ? base + off : nullptr;
-        off += align256(count * sizeof(T));
-        return reinterpret_cast<T *>(p);
-    }
-    size_t bytes() const { return off + 256; }         // + what align_ws may skip
-};
-
-inline int check_workspace(const void *ws, size_t have, size_t need)
-{
-    if (!ws || have < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
-    return 0;
 }
 
 inline int check_scales(const char *who, double scale_r, double scale_phi, double scale_z)

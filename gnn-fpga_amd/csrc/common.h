@@ -103,6 +103,29 @@ __device__ __forceinline__ int64_t xcd_block()
 }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// workspaces: the caller's pointer rounded up to 256 bytes, then carved
+inline char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
+
+// hands out a workspace piece by piece, each piece 256-byte aligned; a null base only adds up the sizes
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <typename T>
+    T *take(size_t count)
+    {
+        char *p = base ? base + off : nullptr;
+        off += align256(count * sizeof(T));
+        return reinterpret_cast<T *>(p);
+    }
+    size_t bytes() const { return off + 256; }         // + what align_ws may skip
+};
+
+inline int check_workspace(const void *ws, size_t have, size_t need)
+{
+    if (!ws || have < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
+    return 0;
+}
+
 // tanh(x) = 1 - 2 / (2^(2 log2(e) x) + 1): v_exp_f32 + v_rcp_f32 (1 ulp each), absolute error
 // ~1e-7 everywhere (the score tolerance is absolute, 1e-5).  Saturates correctly at +-inf.
 __device__ __forceinline__ float tanh_f(float x)
@@ -168,6 +191,7 @@ int sell_forward_train(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters,
 size_t sell_workspace_bytes(int64_t n_hits, int64_t n_segments, int F, int D);
 int sell_shape_supported(int F, int D);
 int sell_limits(int F, int D, int32_t *out4);
+int sell_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, int training, int32_t *out);
 
 // backward.hip
 int bce_loss(const float *e, const float *y, int64_t n, float scale, float *loss, float *grad_e,

@@ -1568,6 +1568,14 @@ int gnn_plan_limits(int32_t F, int32_t D, int32_t *out4)
     return sell_limits(F, D, out4);
 }
 
+int gnn_plan_route(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters, int32_t training, int32_t *out)
+{
+    if (!pl || !p || !out || n_iters < 0 || pl->n_pad < 0 || pl->n_tiles < 0 || pl->iter_lds_records < 0 ||
+        pl->edge_lds_rows < 0 || pl->iter_lds_in < 0 || pl->iter_lds_out < 0)
+        return fail(GNN_ERR_BADARG, "gnn_plan_route: bad argument");
+    return sell_route(pl, p, n_iters, training, out);
+}
+
 int gnn_segclf_forward_plan(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters,
                             float *e_out, void *workspace, size_t workspace_bytes, void *stream)
 {

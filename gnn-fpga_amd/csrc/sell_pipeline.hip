@@ -51,6 +51,7 @@
 
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace {
 using namespace gnn;
@@ -3100,31 +3101,6 @@ __global__ __launch_bounds__(256) void k_edge_w(const int32_t *__restrict__ src,
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct Ws {
-    float *table, *PRa, *PRb, *QSa, *QSb, *U, *Pc, *Qc;
-    unsigned *t16;               // bf16 A fragments + biases of the matrix-core hit update (BL)
-    size_t bytes;
-};
-
-Ws carve(char *b, int64_t n_pad, int table_floats, int D, int t16_words = 0)
-{
-    Ws w;
-    size_t off = 0;
-    auto take = [&](size_t nfloat) {
-        float *p = reinterpret_cast<float *>(b + off);
-        off += align256(nfloat * sizeof(float));
-        return p;
-    };
-    // + 64 rows: the LDS-DMA staging of k_iter2 reads whole 1-KiB pieces past a window's end
-    const size_t rec = (size_t)(n_pad + 1 + 64) * 2 * D, vec = (size_t)(n_pad + 1) * D;
-    w.table = take((size_t)table_floats);
-    w.PRa = take(rec); w.PRb = take(rec); w.QSa = take(rec); w.QSb = take(rec);
-    w.U = take(vec); w.Pc = take(vec); w.Qc = take(vec);
-    w.t16 = reinterpret_cast<unsigned *>(take((size_t)t16_words));
-    w.bytes = off;
-    return w;
-}
-
 template <int F, int D>
 constexpr int t16_words()      // fragment tables of the wide kernels: bf16 (BL) or exact fp32 (BX), one buffer
 {
@@ -3133,10 +3109,32 @@ constexpr int t16_words()      // fragment tables of the wide kernels: bf16 (BL)
     else if constexpr (D % 16 == 0 && F <= 4) return BX<F, D>::total;      // D = 16: exact fp32 fragments only
     else return 0;
 }
+
+struct Ws {
+    float *table, *PRa, *PRb, *QSa, *QSb, *U, *Pc, *Qc;
+    unsigned *t16;               // bf16 A fragments + biases of the matrix-core hit update (BL)
+    size_t bytes;
+};
+
 template <int F, int D>
-constexpr bool can_exact_wide() { return D % 16 == 0 && F <= 4; }
+Ws carve(char *b, int64_t n_pad)          // b = nullptr: only the size
+{
+    Carver c{b};
+    // + 64 rows: the LDS-DMA staging of k_iter2 reads whole 1-KiB pieces past a window's end
+    const size_t rec = (size_t)(n_pad + 1 + 64) * 2 * D, vec = (size_t)(n_pad + 1) * D;
+    Ws w;
+    w.table = c.take<float>(TL<F, D>::total);
+    w.PRa = c.take<float>(rec); w.PRb = c.take<float>(rec); w.QSa = c.take<float>(rec); w.QSb = c.take<float>(rec);
+    w.U = c.take<float>(vec); w.Pc = c.take<float>(vec); w.Qc = c.take<float>(vec);
+    w.t16 = c.take<unsigned>(t16_words<F, D>());
+    w.bytes = c.bytes();
+    return w;
+}
+
 // k_iter_wx (sweep waves + matrix-core waves) from this many padded hits on; below it k_iter_w (round barriers).
 // GNN_WIDE_LOCKSTEP=1 / GNN_WIDE_ROLES=1 force one or the other (A / B runs, tests).
+// (small batches - a workgroup gets a handful of slices - keep the barrier kernel: the ring's polls and its
+// end-of-work detection cost more than they hide there, 1k hits at D = 32: 137 vs 159 us per forward)
 constexpr int64_t kRoleSplitMinHits = 32768;
 
 // k_iter_w's group bound: records of one table an XCD's 4 MB L2 can keep while a group's hits stream
@@ -3149,358 +3147,338 @@ inline int wide_window_records(int row_bytes)
     return (int)(r < 0 ? 0 : r > 0x3FFFFFFF ? 0x3FFFFFFF : r);
 }
 
+// The environment switches of the route (A / B runs, tests).  This is their one reader, called once per library
+// call and not cached: tests flip them inside one process.
+struct Switches {
+    bool no_iter2, no_fuse_first, no_wide_exact, wide_lockstep, wide_roles;
+    int ablate;                  // GNN_ABLATE: timing diagnostics only (results invalid), diag builds
+};
+
+Switches read_switches()
+{
+    const auto set = [](const char *name) { return getenv(name) != nullptr; };
+    Switches sw{set("GNN_NO_ITER2"), set("GNN_NO_FUSE_FIRST"), set("GNN_NO_WIDE_EXACT"), set("GNN_WIDE_LOCKSTEP"),
+                set("GNN_WIDE_ROLES"), 0};                       // the shipped library never skips work
+#ifdef GNN_DIAG
+    if (const char *ab = getenv("GNN_ABLATE")) sw.ablate = atoi(ab);
+#endif
+    return sw;
+}
+
+// Which kernels a planned batch takes (the codes: GNN_ROUTE_* in gnn_hip.h; gnn_plan_route hands them out).
+struct Route {
+    bool supported;              // false: the training forward of a shape that has none
+    int rec;                     // record form
+    int input;                   // input stage
+    int family;                  // the kernel of every iteration
+    bool fuse_first;             // k_iter2 only: the first launch runs the input network too
+    int edge;                    // final edge pass
+    bool pack;                   // k_pack runs
+    int64_t it_lds;              // dynamic LDS bytes of k_iter: weight table + record windows
+    int64_t it2_lds;             // ... of k_iter2: table + both windows + matrix-core tables
+    int64_t capA, capB;          // k_iter2's window buffers, in records
+    int64_t ed_lds;              // dynamic LDS bytes of k_edge
+    int wmax;                    // k_iter_w / k_iter_wx: records of a group (wide_window_records)
+};
+
+// The one place where the route of a forward is decided, before its first launch: from the shape, the flags, the
+// plan's scalars (and which of its arrays exist) and the switches.  Touches no device.
 template <int F, int D, bool XP>
-int forward_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, float *e_out, char *ws,
-              hipStream_t s)
+Route choose_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const Switches &sw, bool training = false)
 {
     using L = TL<F, D>;
     using G = Cfg<F, D>;
-    const int64_t Np = pl->n_pad, E = pl->n_segments;
-    Ws w = carve(ws, Np, L::total, D, t16_words<F, D>());
-    constexpr bool can_bf = D % 32 == 0 && F <= 8;
+    const int64_t Np = pl->n_pad, nt = pl->n_tiles;
+    Route r{};
+    // training: the general tile kernel keeps what the backward needs; the other families do not
+    r.supported = !training || (D <= 16 && !G::wide16);
+    if (!r.supported) return r;
+    // wide hidden layers on bf16 records (opt-in) ...
     // (k_iter_w addresses record rows and list steps with 32-bit byte offsets)
-    const bool bf = can_bf && (p->flags & GNN_FLAG_BF16_MLP) && n_iters > 0 &&
+    constexpr bool can_bf = D % 32 == 0 && F <= 8;
+    const bool bf = !training && can_bf && (p->flags & GNN_FLAG_BF16_MLP) && n_iters > 0 && Np > 0 &&
                     (uint64_t)(Np + 2) * D * 4 < (1ull << 32);
-    if constexpr (can_bf)
-        if (bf && Np > 0)
-            GNN_LAUNCH("k_pack16", (k_pack16<F, D>), 64, 256, s, *p, w.t16, w.PRa, w.PRb, w.QSa, w.QSb, Np,
-                       XP ? 1 : 0);
-    // hidden_dim 16 (F <= 4) takes the 16-lanes-per-hit kernel too - one dim per lane, the hit update (1776
-    // multiply-adds per hit on the vector pipe before, with its weights read from LDS) on the fp32
-    // matrix-core instruction - where its two 128 KB record windows per 1000-hit level never fitted
-    // the LDS of k_iter; GNN_NO_WIDE_EXACT=1 keeps the general kernel
-    constexpr bool can_ex = can_exact_wide<F, D>();
-    const bool ex = can_ex && !bf && n_iters > 0 && Np > 0 && (uint64_t)(Np + 2) * D * 8 < (1ull << 32) &&
-                    !getenv("GNN_NO_WIDE_EXACT");
-    if (Np == 0 || G::pack_first || ex)   // no hits (nothing for k_input4 to do), a big table, or k_input4_x reads it
-        GNN_LAUNCH("k_pack", (k_pack<F, D, XP>), (L::total + 255) / 256, 256, s, *p, w.table, w.PRa, w.PRb,
-                   w.QSa, w.QSb, w.U, w.Pc, w.Qc, Np);
-    // wide hidden layers in exact fp32 (the default): 16 lanes per hit over fp32 record rows, hit
-    // update on v_mfma_f32_16x16x4_f32 (BX).  k_pack32 runs after k_pack: its NULL rows use k_iter_w's
-    // row order and replace the general kernels'.
-    if constexpr (can_ex)
-        if (ex)
-            GNN_LAUNCH("k_pack32", (k_pack32<F, D>), 64, 256, s, *p, reinterpret_cast<float *>(w.t16), w.PRa, w.PRb,
-                       w.QSa, w.QSb, Np, XP ? 1 : 0);
-    float *PR = w.PRa, *PRn = w.PRb, *QS = w.QSa, *QSn = w.QSb;
-    if (Np > 0) {
-        const int nt = (int)pl->n_tiles;
-        const int tpx = (nt + 7) / 8;
-        const size_t it_lds = (size_t)(L::total + (G::it_rec > 0 ? pl->iter_lds_records : 0) * 2 * D + 4) * sizeof(float);
-        static DevOnce attr_done;     // dynamic LDS above 64 KB must be opted into, once per device
-        if (attr_done.need()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter<F, D, true, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter<F, D, false, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-        }
-#ifdef GNN_DIAG
-        const char *ab = getenv("GNN_ABLATE");   // timing diagnostics only (results invalid): diag builds
-        const int ablate = ab ? atoi(ab) : 0;
-#else
-        const int ablate = 0;                    // the shipped library never skips work
-#endif
-        // persistent phase-split kernel when every tile runs in LDS mode and both windows fit LDS;
-        // otherwise the general kernel
-        bool use2 = false, fuse_first = false;
-        size_t it2_lds = 0, it2_lds_first = 0;
-        int capA = 0, capB = 0, grid2 = 0, xbuf_floats = 0;
-        if constexpr (G::iter2) {
-            // window buffers in whole 1-KiB DMA pieces (= 128 / D records) plus one piece that
-            // holds the NULL record and absorbs the last piece's overrun
-            const int64_t rpp = 128 / D;                       // records per piece
-            const int64_t capa = (pl->iter_lds_in + rpp - 1) / rpp * rpp + rpp;
-            const int64_t capb = (pl->iter_lds_out + rpp - 1) / rpp * rpp + rpp;
-            use2 = !getenv("GNN_NO_ITER2") && nt > 0 && pl->n_lds_tiles == nt &&
-                   pl->in_nbr16 && pl->out_nbr16 && pl->in_off16 && pl->out_off16 && pl->sched_a && pl->sched_b;
-            capA = (int)capa;
-            capB = (int)capb;
-            constexpr int mt_floats = mt_total<F, D>();
-            it2_lds = (size_t)(L::total + (capa + capb) * 2 * D + 4 + mt_floats) * sizeof(float);
-            if (it2_lds > (size_t)G::lds_bytes) use2 = false;
-            // first iteration fused with the input network: + one buffer of X rows (256-byte pieces)
-            xbuf_floats = 0;     // (the X rows of a window are staged inside the window buffer itself)
-            // + the fp32 A fragments / biases of the matrix-core window products (D = 8)
-            it2_lds_first = it2_lds;
-            // (exp-product mode only: the plain-exp variant of the fused kernel does not fit the
-            // register budget without spills, and it is the rarely taken fallback anyway)
-            fuse_first = G::fuse_first && XP && use2 && n_iters >= 2 && it2_lds_first <= (size_t)G::lds_bytes &&
-                         !getenv("GNN_NO_FUSE_FIRST");
-            const int n_cu = device_cus();
-            static DevOnce it2_attr;
-            if (it2_attr.need()) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter2<F, D, true, XP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter2<F, D, false, XP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                if constexpr (XP && G::fuse_first)
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter2<F, D, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-            }
-            grid2 = nt < n_cu ? nt : n_cu;
-        }
-        bool input_done = false;
-        if constexpr (can_bf) {
-            if (bf && G::pack_first) {      // records of iteration 0 on the matrix cores too
-                using B = BL<F, D>;
-                const size_t lds_in = (size_t)(B::template tm_words<false>() + 5 * D + 4 * 16 * B::tr_stride) * 4;
-                static DevOnce in_attr;
-                if (in_attr.need())
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_input4_bf<F, D, false, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                const int64_t g_need = (Np * 4 + 255) / 256;
-                GNN_LAUNCH_SH("k_input4", (k_input4_bf<F, D, false, XP>), (unsigned)(g_need < 512 ? g_need : 512), 256,
-                              lds_in, s, pl->X, w.table, w.t16, PR, QS, w.U, w.Pc, w.Qc, Np);
-                input_done = true;
-            }
-        }
-        if constexpr (can_ex) {
-            if (ex) {
-                using B = BX<F, D>;
-                const size_t lds_in = (size_t)(B::template tm_words<false>() + 5 * D + 16 * 16 * B::tr_stride) * 4;
-                static DevOnce inx_attr;
-                if (inx_attr.need())
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_input4_x<F, D, false, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                const int64_t g_need = (Np * 4 + 1023) / 1024;
-                const int64_t g_cap = device_cus();
-                GNN_LAUNCH_SH("k_input4", (k_input4_x<F, D, false, XP>), (unsigned)(g_need < g_cap ? g_need : g_cap), 1024,
-                              lds_in, s, pl->X, w.table, reinterpret_cast<const float *>(w.t16), PR, QS, w.U, w.Pc, w.Qc, Np);
-                input_done = true;
-            }
-        }
-        if (!fuse_first && !input_done) {
-            const int64_t g_need = (Np * 4 + 255) / 256;
-            const unsigned g = (unsigned)(g_need < 4096 ? g_need : 4096);   // 16 workgroups per CU, grid-stride
-            if (n_iters == 0)
-                GNN_LAUNCH("k_input4", (k_input4<F, D, true, XP>), g, 256, s, pl->X, *p, w.table, PR, QS,
-                           PRn, QSn, w.U, w.Pc, w.Qc, Np);
-            else
-                GNN_LAUNCH("k_input4", (k_input4<F, D, false, XP>), g, 256, s, pl->X, *p, w.table, PR, QS,
-                           PRn, QSn, w.U, w.Pc, w.Qc, Np);
-        }
-        for (int t = 0; t < n_iters; ++t) {
-            if constexpr (G::iter2) {
-                if (use2) {
-#define GNN_IT2(LAST_, FIRST_, LDS_)                                                                   \
-    GNN_LAUNCH_SH("k_iter2", (k_iter2<F, D, LAST_, XP, FIRST_>), grid2, 1024, LDS_, s, pl->X, w.table, *p, \
-                  w.table, pl->tiles, pl->in_off, pl->in_off16, pl->in_nbr16, pl->out_off,             \
-                  pl->out_off16, pl->out_nbr16, pl->sched_a, pl->sched_b, PR, QS, w.U, PRn, QSn, w.Pc,  \
-                  w.Qc, Np, nt, capA, capB, xbuf_floats)
-                    if (XP && t == 0 && fuse_first) {
-                        if constexpr (XP && G::fuse_first) GNN_IT2(false, true, it2_lds_first);
-                    } else if (t + 1 == n_iters)
-                        GNN_IT2(true, false, it2_lds);
-                    else
-                        GNN_IT2(false, false, it2_lds);
-#undef GNN_IT2
-                    float *t1 = PR; PR = PRn; PRn = t1;
-                    float *t2 = QS; QS = QSn; QSn = t2;
-                    continue;
-                }
-            }
-            bool launched = false;
-            if constexpr (can_bf) {
-                if (bf) {           // wide hidden layers on bf16 records: k_iter_w (16 lanes per hit)
-                    using B = BL<F, D>;
-                    static DevOnce bf_attr;
-                    if (bf_attr.need()) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_w<F, D, true, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_w<F, D, false, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                    }
-                    const int ncu = device_cus();
-                    const unsigned wgs = (unsigned)(((nt < ncu ? nt : ncu) + 7) / 8 * 8);   // persistent, 8 | grid
-                    const size_t trw = (size_t)2 * 4 * 16 * B::tr_stride + 4;  // double-buffered scratch of the 4 teams + the group word
-                    const int wmax = wide_window_records(4 * D);
-                    const unsigned *PRh = reinterpret_cast<const unsigned *>(PR), *QSh = reinterpret_cast<const unsigned *>(QS);
-                    // (small batches - a workgroup gets a handful of slices - keep the barrier kernel: the ring's polls and its
-                    // end-of-work detection cost more than they hide there, 1k hits at D = 32: 137 vs 159 us per forward)
-                    const bool lockstep_bf = getenv("GNN_WIDE_LOCKSTEP") != nullptr || (Np < kRoleSplitMinHits && !getenv("GNN_WIDE_ROLES"));
-                    if (!lockstep_bf) {             // sweep waves + matrix-core waves (k_iter_wx)
-                        static DevOnce wxb_attr;
-                        if (wxb_attr.need()) {
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_wx<F, D, true, XP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_wx<F, D, false, XP, false>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                        }
-                        const size_t ringw = (size_t)12 * 16 * B::tr_stride + 40;
-                        if (t + 1 == n_iters)
-                            GNN_LAUNCH_SH("k_iter_wx", (k_iter_wx<F, D, true, XP, false>), wgs, 1024,
-                                          (B::template lds_words<true>() + ringw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                          pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, PRn, QSn,
-                                          w.Pc, w.Qc, Np, tpx, nt, wmax);
-                        else
-                            GNN_LAUNCH_SH("k_iter_wx", (k_iter_wx<F, D, false, XP, false>), wgs, 1024,
-                                          (B::template lds_words<false>() + ringw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                          pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, PRn, QSn,
-                                          w.Pc, w.Qc, Np, tpx, nt, wmax);
-                        float *t1 = PR; PR = PRn; PRn = t1;
-                        float *t2 = QS; QS = QSn; QSn = t2;
-                        continue;
-                    }
-                    if (t + 1 == n_iters)
-                        GNN_LAUNCH_SH("k_iter_w", (k_iter_w<F, D, true, XP>), wgs, 1024,
-                                      (B::template lds_words<true>() + trw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                      pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, PRn, QSn,
-                                      w.Pc, w.Qc, Np, tpx, nt, wmax);
-                    else
-                        GNN_LAUNCH_SH("k_iter_w", (k_iter_w<F, D, false, XP>), wgs, 1024,
-                                      (B::template lds_words<false>() + trw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                      pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, PRn, QSn,
-                                      w.Pc, w.Qc, Np, tpx, nt, wmax);
-                    launched = true;
-                }
-            }
-            if constexpr (can_ex) {
-                if (ex) {           // the same kernel on fp32 record rows, exact fp32 matrix-core tail
-                    using B = BX<F, D>;
-                    static DevOnce ex_attr;
-                    if (ex_attr.need()) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_w<F, D, true, XP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_w<F, D, false, XP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                    }
-                    const int ncu = device_cus() * (D == 16 ? 2 : 1);      // D = 16: two workgroups per CU
-                    const unsigned wgs = (unsigned)(((nt < ncu ? nt : ncu) + 7) / 8 * 8);
-                    if constexpr (D >= 16) {       // sweep waves + matrix-core waves (k_iter_wx)
-                        const bool lockstep = getenv("GNN_WIDE_LOCKSTEP") != nullptr || (Np < kRoleSplitMinHits && !getenv("GNN_WIDE_ROLES"));
-                        if (!lockstep) {
-                            static DevOnce wx_attr;
-                            if (wx_attr.need()) {
-                                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_wx<F, D, true, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_wx<F, D, false, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                            }
-                            const size_t ringw = (size_t)12 * 16 * B::tr_stride + 40;      // 12 slots + the counters (38 words)
-                            const unsigned *PRx = reinterpret_cast<const unsigned *>(PR), *QSx = reinterpret_cast<const unsigned *>(QS);
-                            const int wmx = wide_window_records(8 * D);
-                            if (t + 1 == n_iters)
-                                GNN_LAUNCH_SH("k_iter_wx", (k_iter_wx<F, D, true, XP>), wgs, 1024,
-                                              (B::template lds_words<true>() + ringw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                              pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRx, QSx, w.U, PRn, QSn,
-                                              w.Pc, w.Qc, Np, tpx, nt, wmx);
-                            else
-                                GNN_LAUNCH_SH("k_iter_wx", (k_iter_wx<F, D, false, XP>), wgs, 1024,
-                                              (B::template lds_words<false>() + ringw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                              pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRx, QSx, w.U, PRn, QSn,
-                                              w.Pc, w.Qc, Np, tpx, nt, wmx);
-                            launched = true;
-                            float *t1 = PR; PR = PRn; PRn = t1;
-                            float *t2 = QS; QS = QSn; QSn = t2;
-                            continue;
-                        }
-                    }
-                    const size_t trw = (size_t)(2 * 4 + 4) * 16 * B::tr_stride + 4;   // double-buffered q scratch + hl scratch + the group word
-                    const int wmax = wide_window_records(8 * D);
-                    const unsigned *PRh = reinterpret_cast<const unsigned *>(PR), *QSh = reinterpret_cast<const unsigned *>(QS);
-                    if (t + 1 == n_iters)
-                        GNN_LAUNCH_SH("k_iter_w", (k_iter_w<F, D, true, XP, true>), wgs, 1024,
-                                      (B::template lds_words<true>() + trw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                      pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, PRn, QSn,
-                                      w.Pc, w.Qc, Np, tpx, nt, wmax);
-                    else
-                        GNN_LAUNCH_SH("k_iter_w", (k_iter_w<F, D, false, XP, true>), wgs, 1024,
-                                      (B::template lds_words<false>() + trw) * 4, s, pl->X, w.table, w.t16, pl->tiles,
-                                      pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, PRn, QSn,
-                                      w.Pc, w.Qc, Np, tpx, nt, wmax);
-                    launched = true;
-                }
-            }
-            if (launched) {
-            } else if (t + 1 == n_iters)
-                GNN_LAUNCH_SH("k_iter", (k_iter<F, D, true, XP>), 8 * tpx, G::NT, it_lds, s, pl->X, w.table,
-                           pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PR, QS, w.U,
-                           PRn, QSn, w.Pc, w.Qc, Np, tpx, nt, ablate);
-            else
-                GNN_LAUNCH_SH("k_iter", (k_iter<F, D, false, XP>), 8 * tpx, G::NT, it_lds, s, pl->X, w.table,
-                           pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PR, QS, w.U,
-                           PRn, QSn, w.Pc, w.Qc, Np, tpx, nt, ablate);
-            float *t1 = PR; PR = PRn; PRn = t1;
-            float *t2 = QS; QS = QSn; QSn = t2;
-        }
+    // ... or in exact fp32 (the default): 16 lanes per hit over fp32 record rows, hit update on
+    // v_mfma_f32_16x16x4_f32 (BX).  hidden_dim 16 (F <= 4) takes it too - one dim per lane, the hit update (1776
+    // multiply-adds per hit on the vector pipe before, with its weights read from LDS) on the fp32 matrix-core
+    // instruction - where its two 128 KB record windows per 1000-hit level never fitted the LDS of k_iter;
+    // GNN_NO_WIDE_EXACT=1 keeps the general kernel
+    constexpr bool can_ex = D % 16 == 0 && F <= 4;
+    const bool ex = !training && can_ex && !bf && n_iters > 0 && Np > 0 && (uint64_t)(Np + 2) * D * 8 < (1ull << 32) &&
+                    !sw.no_wide_exact;
+    r.rec = bf ? GNN_REC_BF16 : ex ? GNN_REC_EXACT : GNN_REC_FP32;
+    r.pack = Np == 0 || G::pack_first || ex;   // no hits (nothing for k_input4 to do), a big table, or k_input4_x reads it
+    // wide rows, no LDS windows: every chunk is in global mode (absolute ids; padded segments point at the NULL
+    // rows), so k_edge_w needs no chunk descriptors
+    r.edge = (!training && G::ed_rec == 0 && D % 16 == 0) ? GNN_EDGE_K_EDGE_W : GNN_EDGE_K_EDGE;
+    r.ed_lds = (int64_t)(((G::ed_rec > 0 ? pl->edge_lds_rows : 0) * D + 4) * sizeof(float));
+    r.input = GNN_INPUT_NONE;
+    r.family = GNN_FAMILY_K_ITER;
+    if (Np == 0) return r;       // nothing but k_pack runs
+    r.it_lds = (int64_t)((L::total + (G::it_rec > 0 ? pl->iter_lds_records : 0) * 2 * D + 4) * sizeof(float));
+    // persistent phase-split kernel when every tile runs in LDS mode and both windows fit LDS; otherwise the
+    // general kernel
+    bool use2 = false;
+    if constexpr (G::iter2) {
+        // window buffers in whole 1-KiB DMA pieces (= 128 / D records) plus one piece that holds the NULL record
+        // and absorbs the last piece's overrun (the X rows of a fused first launch are staged inside them)
+        const int64_t rpp = 128 / D;
+        r.capA = (pl->iter_lds_in + rpp - 1) / rpp * rpp + rpp;
+        r.capB = (pl->iter_lds_out + rpp - 1) / rpp * rpp + rpp;
+        // + the fp32 A fragments / biases of the matrix-core window products (D = 8)
+        r.it2_lds = (int64_t)((L::total + (r.capA + r.capB) * 2 * D + 4 + mt_total<F, D>()) * sizeof(float));
+        use2 = !training && !sw.no_iter2 && nt > 0 && pl->n_lds_tiles == nt && pl->in_nbr16 && pl->out_nbr16 &&
+               pl->in_off16 && pl->out_off16 && pl->sched_a && pl->sched_b && r.it2_lds <= G::lds_bytes;
+        // (exp-product mode only: the plain-exp variant of the fused kernel does not fit the register budget
+        // without spills, and it is the rarely taken fallback anyway)
+        r.fuse_first = G::fuse_first && XP && use2 && n_iters >= 2 && !sw.no_fuse_first;
     }
-    if (E > 0) {
-        const int nc = (int)pl->n_chunks;
-        const int cpx = (nc + 7) / 8;
-        const size_t ed_lds = (size_t)((G::ed_rec > 0 ? pl->edge_lds_rows : 0) * D + 4) * sizeof(float);
-        static DevOnce edge_attr;
-        if (edge_attr.need())
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_edge<F, D, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-        if constexpr (G::ed_rec == 0 && D % 16 == 0) {
-            // wide rows, no LDS windows: every chunk is in global mode (absolute ids; padded
-            // segments point at the NULL rows), so the chunk descriptors are not needed
-            const int64_t waves = (E + 15) / 16;                          // 16 segments per wave trip
-            int64_t wg = (waves + 3) / 4;
-            const int64_t cap = (int64_t)device_cus() * 8;                // 8 workgroups of 256 per CU
-            wg = wg < cap ? wg : cap;
-            GNN_LAUNCH("k_edge", (k_edge_w<F, D, XP>), (unsigned)((wg + 7) / 8 * 8), 256, s, pl->src, pl->dst, w.Pc, w.Qc,
-                       w.table, e_out, E);
-        } else {
-            GNN_LAUNCH_SH("k_edge", (k_edge<F, D, XP>), 8 * cpx, G::NT, ed_lds, s, pl->chunks, pl->src, pl->dst, pl->sd16, w.Pc,
-                       w.Qc, w.table, e_out, Np, cpx, nc);
+    const bool lockstep = sw.wide_lockstep || (Np < kRoleSplitMinHits && !sw.wide_roles);
+    r.family = (bf || ex) ? (lockstep ? GNN_FAMILY_K_ITER_W : GNN_FAMILY_K_ITER_WX) : use2 ? GNN_FAMILY_K_ITER2 : GNN_FAMILY_K_ITER;
+    r.wmax = bf ? wide_window_records(4 * D) : ex ? wide_window_records(8 * D) : 0;
+    r.input = r.fuse_first ? GNN_INPUT_NONE
+              : (bf && G::pack_first) ? GNN_INPUT_K_INPUT4_BF        // records of iteration 0 on the matrix cores too
+              : ex ? GNN_INPUT_K_INPUT4_X : GNN_INPUT_K_INPUT4;
+    return r;
+}
+
+// a run-time flag as a template argument: fn(std::true_type{}) or fn(std::false_type{})
+template <typename Fn>
+int with_flag(bool flag, Fn &&fn)
+{
+    return flag ? fn(std::true_type{}) : fn(std::false_type{});
+}
+
+// dynamic LDS above 64 KB must be opted into, once per device and kernel
+template <auto Kernel>
+void lds_opt_in(int bytes)
+{
+    static DevOnce once;
+    if (once.need())
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+
+// what the training forward keeps besides the scores (forward_t<.., TR = true>; see TrainOut)
+struct TrainArgs {
+    const int32_t *seg_ptr, *tw_src, *tw_dst;
+    float *e_all, *H_all, *Q_all;
+    int ldh;
+};
+
+// one forward in flight: what its launchers share
+struct Run {
+    const gnn_plan_t *pl;
+    const gnn_params_t *p;
+    Route r;
+    Ws w;
+    hipStream_t s;
+    int ablate;
+    float *PR, *PRn, *QS, *QSn;          // the records an iteration reads / writes
+};
+
+// the input network and the records of iteration 0 (`last`: there is no iteration); H0: the training forward's H_0
+template <int F, int D, bool XP, bool TR>
+int launch_input(const Run &c, bool last, float *H0, int ldh)
+{
+    using G = Cfg<F, D>;
+    const int64_t Np = c.pl->n_pad;
+    const Ws &w = c.w;
+    if (c.r.input == GNN_INPUT_K_INPUT4_BF) {
+        if constexpr (D % 32 == 0 && F <= 8) {
+            using B = BL<F, D>;
+            const size_t lds_in = (size_t)(B::template tm_words<false>() + 5 * D + 4 * 16 * B::tr_stride) * 4;
+            lds_opt_in<&k_input4_bf<F, D, false, XP>>(G::lds_bytes);
+            const int64_t g_need = (Np * 4 + 255) / 256;
+            GNN_LAUNCH_SH("k_input4", (k_input4_bf<F, D, false, XP>), (unsigned)(g_need < 512 ? g_need : 512), 256,
+                          lds_in, c.s, c.pl->X, w.table, w.t16, c.PR, c.QS, w.U, w.Pc, w.Qc, Np);
         }
+    } else if (c.r.input == GNN_INPUT_K_INPUT4_X) {
+        if constexpr (D % 16 == 0 && F <= 4) {
+            using B = BX<F, D>;
+            const size_t lds_in = (size_t)(B::template tm_words<false>() + 5 * D + 16 * 16 * B::tr_stride) * 4;
+            lds_opt_in<&k_input4_x<F, D, false, XP>>(G::lds_bytes);
+            const int64_t g_need = (Np * 4 + 1023) / 1024;
+            const int64_t g_cap = device_cus();
+            GNN_LAUNCH_SH("k_input4", (k_input4_x<F, D, false, XP>), (unsigned)(g_need < g_cap ? g_need : g_cap), 1024,
+                          lds_in, c.s, c.pl->X, w.table, reinterpret_cast<const float *>(w.t16), c.PR, c.QS, w.U, w.Pc,
+                          w.Qc, Np);
+        }
+    } else if (c.r.input == GNN_INPUT_K_INPUT4) {
+        const int64_t g_need = (Np * 4 + 255) / 256;
+        const unsigned g = (unsigned)(g_need < 4096 ? g_need : 4096);   // 16 workgroups per CU, grid-stride
+        return with_flag(last, [&](auto last_c) {
+            GNN_LAUNCH("k_input4", (k_input4<F, D, decltype(last_c)::value, XP, TR>), g, 256, c.s, c.pl->X, *c.p, w.table,
+                       c.PR, c.QS, c.PRn, c.QSn, w.U, w.Pc, w.Qc, Np, H0, ldh);
+            return 0;
+        });
     }
     return 0;
 }
 
-// The TRAINING forward on a planned batch (gnn_segclf_forward_train_plan): the fused tile kernels, keeping what
-// the backward needs (TrainOut) - instead of the per-module kernels' k_input + T x (k_pq, k_edge, k_node), whose
-// node pass walks both segment lists through the L2 (0.31 ms of a 0.97 ms step at c3 x 32; this: 0.2).
-// e_all [(T + 1), E]: rows 0 .. T-1 in the order of the hits' in-lists (segments sorted by end hit, stable),
-// valid segments only; row T is NOT written here (the final scores come back in e_out, the plan's segment
-// order).  H_all [(T + 1), n_pad, ldh], Q_all [T, n_pad, D].  Shapes on the general tile kernel only (D <= 16
-// without the wide route); others: GNN_ERR_UNSUPPORTED (the caller keeps the per-module route).
-template <int F, int D, bool XP>
-int forward_train_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const int32_t *seg_ptr,
-                    const int32_t *tw_src, const int32_t *tw_dst, float *e_all, float *H_all, float *Q_all, int ldh,
-                    float *e_out, char *ws, hipStream_t s)
+// k_iter: the general iteration kernel, one workgroup per tile
+template <int F, int D, bool XP, bool TR>
+int launch_iter(const Run &c, bool last, const TrainOut &tro)
 {
-    using L = TL<F, D>;
     using G = Cfg<F, D>;
-    if constexpr (D > 16 || G::wide16) {
+    const gnn_plan_t *pl = c.pl;
+    const Ws &w = c.w;
+    const int nt = (int)pl->n_tiles, tpx = (nt + 7) / 8;
+    return with_flag(last, [&](auto last_c) {
+        constexpr bool LAST = decltype(last_c)::value;
+        lds_opt_in<&k_iter<F, D, LAST, XP, TR>>(G::lds_bytes);
+        GNN_LAUNCH_SH("k_iter", (k_iter<F, D, LAST, XP, TR>), 8 * tpx, G::NT, (size_t)c.r.it_lds, c.s, pl->X, w.table,
+                      pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, c.PR, c.QS, w.U, c.PRn, c.QSn, w.Pc,
+                      w.Qc, pl->n_pad, tpx, nt, c.ablate, tro);
+        return 0;
+    });
+}
+
+// k_iter2: the persistent phase-split kernel; `first`: with the input network fused in
+template <int F, int D, bool XP>
+int launch_iter2(const Run &c, bool first, bool last)
+{
+    using G = Cfg<F, D>;
+    const gnn_plan_t *pl = c.pl;
+    const Ws &w = c.w;
+    const int nt = (int)pl->n_tiles, n_cu = device_cus();
+    const int grid = nt < n_cu ? nt : n_cu;
+    const auto launch = [&](auto last_c, auto first_c) {
+        constexpr bool LAST = decltype(last_c)::value, FIRST = decltype(first_c)::value;
+        lds_opt_in<&k_iter2<F, D, LAST, XP, FIRST>>(G::lds_bytes);
+        GNN_LAUNCH_SH("k_iter2", (k_iter2<F, D, LAST, XP, FIRST>), grid, 1024, (size_t)c.r.it2_lds, c.s, pl->X, w.table,
+                      *c.p, w.table, pl->tiles, pl->in_off, pl->in_off16, pl->in_nbr16, pl->out_off, pl->out_off16,
+                      pl->out_nbr16, pl->sched_a, pl->sched_b, c.PR, c.QS, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, nt,
+                      (int)c.r.capA, (int)c.r.capB, 0);
+        return 0;
+    };
+    if constexpr (XP && G::fuse_first)       // (choose_route asks for `first` on these shapes only)
+        if (first) return launch(std::false_type{}, std::true_type{});
+    return with_flag(last, [&](auto last_c) { return launch(last_c, std::false_type{}); });
+}
+
+// k_iter_w (every round behind barriers) / k_iter_wx (sweep waves + matrix-core waves): 16 lanes per hit, on
+// bf16 records (EX = false) or fp32 record rows with the exact fp32 matrix-core tail (EX = true)
+template <int F, int D, bool XP, bool EX>
+int launch_wide(const Run &c, bool last)
+{
+    using G = Cfg<F, D>;
+    using B = std::conditional_t<EX, BX<F, D>, BL<F, D>>;
+    const gnn_plan_t *pl = c.pl;
+    const Ws &w = c.w;
+    const int nt = (int)pl->n_tiles, tpx = (nt + 7) / 8;
+    const int ncu = device_cus() * (EX && D == 16 ? 2 : 1);      // exact, D = 16: two workgroups per CU
+    const unsigned wgs = (unsigned)(((nt < ncu ? nt : ncu) + 7) / 8 * 8);   // persistent, 8 | grid
+    const unsigned *PRh = reinterpret_cast<const unsigned *>(c.PR), *QSh = reinterpret_cast<const unsigned *>(c.QS);
+    return with_flag(last, [&](auto last_c) {
+        constexpr bool LAST = decltype(last_c)::value;
+        if (c.r.family == GNN_FAMILY_K_ITER_WX) {
+            const size_t ringw = (size_t)12 * 16 * B::tr_stride + 40;      // 12 slots + the counters (38 words)
+            lds_opt_in<&k_iter_wx<F, D, LAST, XP, EX>>(G::lds_bytes);
+            GNN_LAUNCH_SH("k_iter_wx", (k_iter_wx<F, D, LAST, XP, EX>), wgs, 1024,
+                          (B::template lds_words<LAST>() + ringw) * 4, c.s, pl->X, w.table, w.t16, pl->tiles, pl->in_off,
+                          pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, tpx,
+                          nt, c.r.wmax);
+        } else {
+            // double-buffered q scratch of the 4 teams (+ the hl scratch: exact) + the group word
+            const size_t trw = (size_t)(EX ? 2 * 4 + 4 : 2 * 4) * 16 * B::tr_stride + 4;
+            lds_opt_in<&k_iter_w<F, D, LAST, XP, EX>>(G::lds_bytes);
+            GNN_LAUNCH_SH("k_iter_w", (k_iter_w<F, D, LAST, XP, EX>), wgs, 1024,
+                          (B::template lds_words<LAST>() + trw) * 4, c.s, pl->X, w.table, w.t16, pl->tiles, pl->in_off,
+                          pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, tpx,
+                          nt, c.r.wmax);
+        }
+        return 0;
+    });
+}
+
+// the final edge pass: e_out in the plan's segment order
+template <int F, int D, bool XP>
+int launch_edge(const Run &c, float *e_out)
+{
+    using G = Cfg<F, D>;
+    const gnn_plan_t *pl = c.pl;
+    const Ws &w = c.w;
+    const int64_t E = pl->n_segments;
+    lds_opt_in<&k_edge<F, D, XP>>(G::lds_bytes);
+    if (c.r.edge == GNN_EDGE_K_EDGE_W) {
+        if constexpr (G::ed_rec == 0 && D % 16 == 0) {
+            const int64_t waves = (E + 15) / 16;                          // 16 segments per wave trip
+            int64_t wg = (waves + 3) / 4;
+            const int64_t cap = (int64_t)device_cus() * 8;                // 8 workgroups of 256 per CU
+            wg = wg < cap ? wg : cap;
+            GNN_LAUNCH("k_edge", (k_edge_w<F, D, XP>), (unsigned)((wg + 7) / 8 * 8), 256, c.s, pl->src, pl->dst, w.Pc,
+                       w.Qc, w.table, e_out, E);
+        }
+    } else {
+        const int nc = (int)pl->n_chunks, cpx = (nc + 7) / 8;
+        GNN_LAUNCH_SH("k_edge", (k_edge<F, D, XP>), 8 * cpx, G::NT, (size_t)c.r.ed_lds, c.s, pl->chunks, pl->src, pl->dst,
+                      pl->sd16, w.Pc, w.Qc, w.table, e_out, pl->n_pad, cpx, nc);
+    }
+    return 0;
+}
+
+// The forward on a planned batch: the route, then its launches.
+// TR: the TRAINING forward (gnn_segclf_forward_train_plan) - the general route, keeping what the backward needs
+// (TrainOut) - instead of the per-module kernels' k_input + T x (k_pq, k_edge, k_node), whose node pass walks both
+// segment lists through the L2 (0.31 ms of a 0.97 ms step at c3 x 32; this: 0.2).
+// e_all [(T + 1), E]: rows 0 .. T-1 in the order of the hits' in-lists (segments sorted by end hit, stable),
+// valid segments only; row T by k_edge_tw in the backward's own segment order, when tw_src is given (the final
+// scores also come back in e_out, the plan's segment order).  H_all [(T + 1), n_pad, ldh], Q_all [T, n_pad, D].
+// Shapes on the general tile kernel only (D <= 16 without the wide route); others: GNN_ERR_UNSUPPORTED (the caller
+// keeps the per-module route).
+template <int F, int D, bool XP, bool TR>
+int forward_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const Switches &sw, const TrainArgs &tr,
+              float *e_out, char *ws, hipStream_t s)
+{
+    using G = Cfg<F, D>;
+    if constexpr (TR && (D > 16 || G::wide16)) {
         return fail(GNN_ERR_UNSUPPORTED, "no fused training forward for input_dim=%d hidden_dim=%d", F, D);
     } else {
         const int64_t Np = pl->n_pad, E = pl->n_segments;
-        Ws w = carve(ws, Np, L::total, D, t16_words<F, D>());
-        if (Np == 0 || G::pack_first)
-            GNN_LAUNCH("k_pack", (k_pack<F, D, XP>), (L::total + 255) / 256, 256, s, *p, w.table, w.PRa, w.PRb,
+        const Ws w = carve<F, D>(ws, Np);
+        Run c{pl, p, choose_route<F, D, XP>(pl, p, n_iters, sw, TR), w, s, TR ? 0 : sw.ablate, w.PRa, w.PRb, w.QSa, w.QSb};
+        if constexpr (D % 32 == 0 && F <= 8)
+            if (c.r.rec == GNN_REC_BF16)
+                GNN_LAUNCH("k_pack16", (k_pack16<F, D>), 64, 256, s, *p, w.t16, w.PRa, w.PRb, w.QSa, w.QSb, Np, XP ? 1 : 0);
+        if (c.r.pack)
+            GNN_LAUNCH("k_pack", (k_pack<F, D, XP>), (TL<F, D>::total + 255) / 256, 256, s, *p, w.table, w.PRa, w.PRb,
                        w.QSa, w.QSb, w.U, w.Pc, w.Qc, Np);
-        float *PR = w.PRa, *PRn = w.PRb, *QS = w.QSa, *QSn = w.QSb;
+        // k_pack32 runs after k_pack: its NULL rows use k_iter_w's row order and replace the general kernels'
+        if constexpr (D % 16 == 0 && F <= 4)
+            if (c.r.rec == GNN_REC_EXACT)
+                GNN_LAUNCH("k_pack32", (k_pack32<F, D>), 64, 256, s, *p, reinterpret_cast<float *>(w.t16), w.PRa, w.PRb,
+                           w.QSa, w.QSb, Np, XP ? 1 : 0);
         if (Np > 0) {
-            const int nt = (int)pl->n_tiles;
-            const int tpx = (nt + 7) / 8;
-            const size_t it_lds = (size_t)(L::total + (G::it_rec > 0 ? pl->iter_lds_records : 0) * 2 * D + 4) * sizeof(float);
-            static DevOnce attr_done;
-            if (attr_done.need()) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter<F, D, true, XP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter<F, D, false, XP, true>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-            }
-            const int64_t g_need = (Np * 4 + 255) / 256;
-            const unsigned g = (unsigned)(g_need < 4096 ? g_need : 4096);
-            if (n_iters == 0)
-                GNN_LAUNCH("k_input4", (k_input4<F, D, true, XP, true>), g, 256, s, pl->X, *p, w.table, PR, QS,
-                           PRn, QSn, w.U, w.Pc, w.Qc, Np, H_all, ldh);
-            else
-                GNN_LAUNCH("k_input4", (k_input4<F, D, false, XP, true>), g, 256, s, pl->X, *p, w.table, PR, QS,
-                           PRn, QSn, w.U, w.Pc, w.Qc, Np, H_all, ldh);
+            if (int rc = launch_input<F, D, XP, TR>(c, n_iters == 0, tr.H_all, tr.ldh)) return rc;
             for (int t = 0; t < n_iters; ++t) {
-                const TrainOut tro{seg_ptr, e_all + (size_t)t * E, Q_all + (size_t)t * Np * D,
-                                   H_all + (size_t)(t + 1) * Np * ldh, ldh};
-                if (t + 1 == n_iters)
-                    GNN_LAUNCH_SH("k_iter", (k_iter<F, D, true, XP, true>), 8 * tpx, G::NT, it_lds, s, pl->X, w.table,
-                                  pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PR, QS, w.U,
-                                  PRn, QSn, w.Pc, w.Qc, Np, tpx, nt, 0, tro);
-                else
-                    GNN_LAUNCH_SH("k_iter", (k_iter<F, D, false, XP, true>), 8 * tpx, G::NT, it_lds, s, pl->X, w.table,
-                                  pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PR, QS, w.U,
-                                  PRn, QSn, w.Pc, w.Qc, Np, tpx, nt, 0, tro);
-                float *t1 = PR; PR = PRn; PRn = t1;
-                float *t2 = QS; QS = QSn; QSn = t2;
+                const bool last = t + 1 == n_iters;
+                int rc = 0;
+                if (c.r.family == GNN_FAMILY_K_ITER) {
+                    TrainOut tro{};
+                    if constexpr (TR)
+                        tro = TrainOut{tr.seg_ptr, tr.e_all + (size_t)t * E, tr.Q_all + (size_t)t * Np * D,
+                                       tr.H_all + (size_t)(t + 1) * Np * tr.ldh, tr.ldh};
+                    rc = launch_iter<F, D, XP, TR>(c, last, tro);
+                } else if constexpr (!TR) {
+                    if (c.r.family == GNN_FAMILY_K_ITER2) {
+                        if constexpr (G::iter2) rc = launch_iter2<F, D, XP>(c, t == 0 && c.r.fuse_first, last);
+                    } else if (c.r.rec == GNN_REC_BF16) {
+                        if constexpr (D % 32 == 0 && F <= 8) rc = launch_wide<F, D, XP, false>(c, last);
+                    } else {
+                        if constexpr (D % 16 == 0 && F <= 4) rc = launch_wide<F, D, XP, true>(c, last);
+                    }
+                }
+                if (rc) return rc;
+                std::swap(c.PR, c.PRn);
+                std::swap(c.QS, c.QSn);
             }
         }
-        if (E > 0 && e_out) {
-            const int nc = (int)pl->n_chunks;
-            const int cpx = (nc + 7) / 8;
-            const size_t ed_lds = (size_t)((G::ed_rec > 0 ? pl->edge_lds_rows : 0) * D + 4) * sizeof(float);
-            static DevOnce edge_attr;
-            if (edge_attr.need())
-                (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_edge<F, D, XP>), hipFuncAttributeMaxDynamicSharedMemorySize, G::lds_bytes);
-            GNN_LAUNCH_SH("k_edge", (k_edge<F, D, XP>), 8 * cpx, G::NT, ed_lds, s, pl->chunks, pl->src, pl->dst, pl->sd16, w.Pc,
-                          w.Qc, w.table, e_out, Np, cpx, nc);
-        }
-        if (E > 0 && tw_src)      // row T of e_all: the final scores in the backward's own segment order
-            GNN_LAUNCH("k_edge_tw", (k_edge_tw<F, D, XP>), grid_for(E), 256, s, tw_src, tw_dst, w.Pc, w.Qc, w.table,
-                       e_all + (size_t)n_iters * E, Np, E);
+        if (E > 0 && (!TR || e_out))
+            if (int rc = launch_edge<F, D, XP>(c, e_out)) return rc;
+        if constexpr (TR)
+            if (E > 0 && tr.tw_src)      // row T of e_all: the final scores in the backward's own segment order
+                GNN_LAUNCH("k_edge_tw", (k_edge_tw<F, D, XP>), grid_for(E), 256, s, tr.tw_src, tr.tw_dst, w.Pc, w.Qc,
+                           w.table, tr.e_all + (size_t)n_iters * E, Np, E);
         return 0;
     }
 }
@@ -3518,6 +3496,25 @@ int forward_train_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, co
     X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) \
     X_(11, 4) X_(11, 8) X_(11, 16)
 #endif
+
+// what sell_forward and sell_forward_train share: the workspace check, the switches, the shape dispatch
+template <bool TR>
+int forward_any(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const TrainArgs &tr, float *e_out, void *ws,
+                size_t ws_bytes, hipStream_t s)
+{
+    ProfChain chain_;      // (profiling runs: one event per kernel boundary of this call)
+    const size_t need = sell_workspace_bytes(pl->n_pad, pl->n_segments, p->F, p->D);
+    if (need == 0) return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
+    const Switches sw = read_switches();
+#define X_(F_, D_)                                                                                            \
+    if (p->F == F_ && p->D == D_)                                                                            \
+        return (p->flags & GNN_FLAG_EXP_PRODUCT) ? forward_t<F_, D_, true, TR>(pl, p, n_iters, sw, tr, e_out, align_ws(ws), s) \
+                                                 : forward_t<F_, D_, false, TR>(pl, p, n_iters, sw, tr, e_out, align_ws(ws), s);
+    SELL_FOR_EACH_SHAPE(X_)
+#undef X_
+    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+}
 
 }  // namespace
 
@@ -3549,9 +3546,30 @@ int sell_limits(int F, int D, int32_t *out4)
 size_t sell_workspace_bytes(int64_t n_pad, int64_t n_segments, int F, int D)
 {
     (void)n_segments;
-#define X_(F_, D_) if (F == F_ && D == D_) return carve(nullptr, n_pad, TL<F_, D_>::total, D, t16_words<F_, D_>()).bytes + 256;
+#define X_(F_, D_) if (F == F_ && D == D_) return carve<F_, D_>(nullptr, n_pad).bytes;
     SELL_FOR_EACH_SHAPE(X_)
 #undef X_
+    return 0;
+}
+
+// gnn_plan_route: choose_route's answer as GNN_ROUTE_FIELDS small integers
+int sell_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, int training, int32_t *out)
+{
+    const Switches sw = read_switches();
+    Route r{};
+#define X_(F_, D_)                                                                                       \
+    if (p->F == F_ && p->D == D_)                                                                       \
+        r = (p->flags & GNN_FLAG_EXP_PRODUCT) ? choose_route<F_, D_, true>(pl, p, n_iters, sw, training != 0) \
+                                              : choose_route<F_, D_, false>(pl, p, n_iters, sw, training != 0);
+    SELL_FOR_EACH_SHAPE(X_)
+#undef X_
+    if (!sell_shape_supported(p->F, p->D))
+        return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    if (!r.supported)
+        return fail(GNN_ERR_UNSUPPORTED, "no fused training forward for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const int64_t f[GNN_ROUTE_FIELDS] = {r.rec, r.input, r.family, r.fuse_first, r.edge, r.pack, r.it_lds, r.it2_lds,
+                                         r.capA, r.capB, r.ed_lds, r.wmax};      // the order of GNN_ROUTE_* in gnn_hip.h
+    for (int i = 0; i < GNN_ROUTE_FIELDS; ++i) out[i] = (int32_t)(f[i] > INT32_MAX ? INT32_MAX : f[i]);
     return 0;
 }
 
@@ -3559,36 +3577,14 @@ int sell_forward_train(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters,
                        const int32_t *tw_src, const int32_t *tw_dst, float *e_all, float *H_all, float *Q_all, int ldh,
                        float *e_out, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    ProfChain chain_;
-    const size_t need = sell_workspace_bytes(pl->n_pad, pl->n_segments, p->F, p->D);
-    if (need == 0) return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    if (!ws || ws_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_)                                                                                        \
-    if (p->F == F_ && p->D == D_)                                                                        \
-        return (p->flags & GNN_FLAG_EXP_PRODUCT)                                                         \
-                   ? forward_train_t<F_, D_, true>(pl, p, n_iters, seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh, e_out, base, s)  \
-                   : forward_train_t<F_, D_, false>(pl, p, n_iters, seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh, e_out, base, s);
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    return forward_any<true>(pl, p, n_iters, TrainArgs{seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh}, e_out, ws,
+                             ws_bytes, s);
 }
 
 int sell_forward(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, float *e_out, void *ws,
                  size_t ws_bytes, hipStream_t s)
 {
-    ProfChain chain_;      // (profiling runs: one event per kernel boundary of this call)
-    const size_t need = sell_workspace_bytes(pl->n_pad, pl->n_segments, p->F, p->D);
-    if (need == 0) return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    if (!ws || ws_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_)                                                                              \
-    if (p->F == F_ && p->D == D_)                                                              \
-        return (p->flags & GNN_FLAG_EXP_PRODUCT) ? forward_t<F_, D_, true>(pl, p, n_iters, e_out, base, s) \
-                                                 : forward_t<F_, D_, false>(pl, p, n_iters, e_out, base, s);
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    return forward_any<false>(pl, p, n_iters, TrainArgs{}, e_out, ws, ws_bytes, s);
 }
 
 }  // namespace gnn

@@ -280,6 +280,34 @@ int gnn_plan_shape_supported(int32_t F, int32_t D);
  * edge_records } - the tile / chunk sizes and the LDS window budgets (in records of 2D floats
  * for the iteration kernel, rows of D floats for the edge kernel). */
 int gnn_plan_limits(int32_t F, int32_t D, int32_t *out4);
+/* Which kernels gnn_segclf_forward_plan (training = 0) or gnn_segclf_forward_train_plan (training = 1) launches
+ * for this plan, these flags and n_iters, decided by the very function the forward calls (choose_route in
+ * csrc/sell_pipeline.hip).  Reads the plan's scalars, which of its pointers are NULL, p->F, p->D, p->flags and
+ * the GNN_NO_ITER2 / GNN_NO_FUSE_FIRST / GNN_NO_WIDE_EXACT / GNN_WIDE_LOCKSTEP / GNN_WIDE_ROLES switches of the
+ * environment; dereferences no device pointer and needs no GPU.  out [GNN_ROUTE_FIELDS]:
+ *   GNN_ROUTE_REC         record form: 0 fp32 (general kernels), 1 bf16 rows (after k_pack16), 2 exact fp32 rows of
+ *                         the 16-lanes-per-hit kernels (after k_pack32)
+ *   GNN_ROUTE_INPUT       input stage: 0 none (no hits, or fused into the first k_iter2), 1 k_input4,
+ *                         2 k_input4_bf, 3 k_input4_x
+ *   GNN_ROUTE_FAMILY      the kernel of each of the n_iters iterations: 0 k_iter, 1 k_iter2, 2 k_iter_w, 3 k_iter_wx
+ *   GNN_ROUTE_FUSE_FIRST  1: the first k_iter2 launch runs the input network too
+ *   GNN_ROUTE_EDGE        final edge pass (n_segments > 0): 0 k_edge, 1 k_edge_w
+ *   GNN_ROUTE_PACK        1: k_pack runs first
+ *   GNN_ROUTE_ITER_LDS, GNN_ROUTE_ITER2_LDS, GNN_ROUTE_EDGE_LDS   dynamic LDS bytes of k_iter, k_iter2 (0: the
+ *                         shape has none) and k_edge; GNN_ROUTE_CAP_A / _B: k_iter2's window buffers in records
+ *   GNN_ROUTE_WIDE_WINDOW records per group of k_iter_w / k_iter_wx (0: another family)
+ * (sizes beyond INT32_MAX are reported as INT32_MAX).  GNN_ERR_UNSUPPORTED: no fused kernels for (F, D), or
+ * training = 1 for a shape without a fused training forward. */
+enum {
+    GNN_ROUTE_REC, GNN_ROUTE_INPUT, GNN_ROUTE_FAMILY, GNN_ROUTE_FUSE_FIRST, GNN_ROUTE_EDGE, GNN_ROUTE_PACK,
+    GNN_ROUTE_ITER_LDS, GNN_ROUTE_ITER2_LDS, GNN_ROUTE_CAP_A, GNN_ROUTE_CAP_B, GNN_ROUTE_EDGE_LDS,
+    GNN_ROUTE_WIDE_WINDOW, GNN_ROUTE_FIELDS
+};
+enum { GNN_REC_FP32, GNN_REC_BF16, GNN_REC_EXACT };
+enum { GNN_INPUT_NONE, GNN_INPUT_K_INPUT4, GNN_INPUT_K_INPUT4_BF, GNN_INPUT_K_INPUT4_X };
+enum { GNN_FAMILY_K_ITER, GNN_FAMILY_K_ITER2, GNN_FAMILY_K_ITER_W, GNN_FAMILY_K_ITER_WX };
+enum { GNN_EDGE_K_EDGE, GNN_EDGE_K_EDGE_W };
+int gnn_plan_route(const gnn_plan_t *plan, const gnn_params_t *p, int32_t n_iters, int32_t training, int32_t *out);
 
 /* The reference's dense input contract -> index form, on the device: Ri, Ro [B, N, E] float32 with one
  * non-zero per real column and all-zero padded columns (gnn/graph.py:28-35,

@@ -39,7 +39,7 @@ What the kernels round (sell_pipeline.hip line numbers), each point emulated bel
                where R = S = 0 makes the step add nothing: the node sums here run over the valid segments only.
                Padded segments (src = dst = -1) are scored by k_edge_w from the fp32 NULL rows of Pc / Qc
                (write_null_rows 169-174): P = kTwoLog2e b1 (2^that in XP mode), Q = 0 (1).
-  route        forward_t (3160-3166): bf16 only for D in {32, 64}, F <= 8, n_iters > 0 and (Np + 2) D 4 < 2^32;
+  route        choose_route: bf16 only for D in {32, 64}, F <= 8, n_iters > 0 and (Np + 2) D 4 < 2^32;
                n_iters = 0 declines it (the fp32 path runs)
 
 Arguments of `segment_classifier`:

@@ -6,7 +6,7 @@ copies of a small pool of distinct seeded layered graphs, each with an ODD hit c
 order (no period that a power-of-two wrap distance could map onto an identical row), and every copy's scores are
 checked against its own pool graph's reference.
 
-The wide kernels (k_iter_w, k_iter_wx) address record rows with 32-bit byte offsets; forward_t
+The wide kernels (k_iter_w, k_iter_wx) address record rows with 32-bit byte offsets; choose_route
 (csrc/sell_pipeline.hip) takes them only while the table stays below 4 GiB:
 
   bf16 records        (n_pad + 2) * D * 4 < 2^32
@@ -34,7 +34,7 @@ RECORD_BYTES = {"bf16": 4, "exact": 8}        # bytes per hidden dim of one reco
 
 
 def guard_ok(n_pad, D, B, limit=GUARD_BYTES):
-    """forward_t's condition for the wide kernels: (n_pad + 2) * D * B < 2^32."""
+    """choose_route's condition for the wide kernels: (n_pad + 2) * D * B < 2^32."""
     return (n_pad + 2) * D * B < limit
 
 

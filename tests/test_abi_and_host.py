@@ -290,3 +290,151 @@ def test_event_route_decision_is_pinned():
     assert not _lib.events_preferred(2, 32, lay(40, 144))             # wide hidden layers: tiled
     assert not _lib.events_preferred(3, 8, None)                      # not block-diagonal
     assert not _lib.events_preferred(3, 8, lay(40000, 1000))          # does not fit the LDS of one workgroup
+
+
+_ROUTE_SWITCHES = ("GNN_NO_ITER2", "GNN_NO_FUSE_FIRST", "GNN_NO_WIDE_EXACT", "GNN_WIDE_LOCKSTEP", "GNN_WIDE_ROLES")
+_LISTS16 = ("in_off16", "in_nbr16", "out_off16", "out_nbr16", "sched_a", "sched_b")
+XP, BF = 1, 2          # GNN_FLAG_EXP_PRODUCT, GNN_FLAG_BF16_MLP
+
+
+def _route_plan(n_pad=1024, n_tiles=4, n_lds_tiles=None, lds_in=100, lds_out=100, missing=()):
+    """A gnn_plan_t as gnn_plan_route reads it: scalars, and pointers that are only NULL or not."""
+    from gnn_fpga_amd import _lib
+    g = _lib.GnnPlan()
+    for name, kind in _lib.GnnPlan._fields_:
+        if kind is ctypes.c_void_p and name not in missing:
+            setattr(g, name, 0x1000)
+    g.n_pad, g.n_segments, g.n_tiles, g.n_chunks = n_pad, 5000, n_tiles, 1
+    g.n_lds_tiles = n_tiles if n_lds_tiles is None else n_lds_tiles
+    g.iter_lds_in, g.iter_lds_out, g.iter_lds_records, g.edge_lds_rows = lds_in, lds_out, 204, 300
+    return g
+
+
+def test_plan_route_is_pinned(monkeypatch):
+    """gnn_plan_route: which kernels the fused forward takes, on both sides of every condition.  The expected routes
+    were written down from forward_t / forward_train_t as they stood BEFORE the route decision was gathered into
+    choose_route (csrc/sell_pipeline.hip): (records, input stage, iteration kernel, fused first launch, edge kernel,
+    k_pack).  The GPU twin (test_gpu_plan_route.py) checks the kernels that ran."""
+    from gnn_fpga_amd import _lib
+    for k in _ROUTE_SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+
+    def route(F, D, T=3, flags=XP, training=False, **plan):
+        r = _lib.plan_route(_route_plan(**plan), F, D, T, flags=flags, training=training)
+        return r and (r["records"], r["input"], r["family"], r["fuse_first"], r["edge"], r["pack"])
+
+    fused = ("fp32", None, "k_iter2", True, "k_edge", False)            # T x k_iter2, the first with the input network
+    iter2 = ("fp32", "k_input4", "k_iter2", False, "k_edge", False)
+    general = ("fp32", "k_input4", "k_iter", False, "k_edge", False)
+    exact16 = ("exact", "k_input4_x", "k_iter_w", False, "k_edge", True)
+    exact = ("exact", "k_input4_x", "k_iter_w", False, "k_edge_w", True)
+    exact_wx = ("exact", "k_input4_x", "k_iter_wx", False, "k_edge_w", True)
+    bf16 = ("bf16", "k_input4_bf", "k_iter_w", False, "k_edge_w", True)
+    bf16_wx = ("bf16", "k_input4_bf", "k_iter_wx", False, "k_edge_w", True)
+    general_wide = ("fp32", "k_input4", "k_iter", False, "k_edge_w", True)     # big table: k_pack; wide rows: k_edge_w
+    # every shape of SELL_FOR_EACH_SHAPE: 3 iterations, exp-product on, every tile in LDS mode, 1024 padded hits
+    default = {(2, 4): fused, (2, 8): iter2, (2, 16): exact16, (2, 32): exact, (3, 4): fused, (3, 8): fused,
+               (3, 16): exact16, (3, 32): exact, (3, 64): exact, (11, 4): iter2, (11, 8): iter2, (11, 16): general}
+    trains = {(2, 4), (2, 8), (3, 4), (3, 8), (11, 4), (11, 8), (11, 16)}     # D <= 16 without the wide route
+    for (F, D), want in default.items():
+        assert _lib.plan_shape_supported(F, D)
+        assert route(F, D) == want, (F, D)
+        # n_pad = 0: k_pack and nothing else before the edge pass
+        assert route(F, D, n_pad=0) == ("fp32", None, "k_iter", False, want[4], True), (F, D)
+        # the fused training forward: the general route where it exists (whatever the flags say), refused elsewhere
+        for flags in (0, XP | BF):
+            assert route(F, D, flags=flags, training=True) == (general if (F, D) in trains else None), (F, D)
+    assert len(default) == 12 and not _lib.plan_shape_supported(5, 7)
+    with pytest.raises(_lib.GnnHipError, match="input_dim=5"):
+        route(5, 7)
+    # exp-product off: no fused first launch
+    assert route(3, 8, flags=0) == iter2 and route(2, 4, flags=0) == iter2 and route(3, 64, flags=0) == exact
+    # n_iters 2 / 1 / 0: the fused first launch needs two iterations, the wide record forms one
+    assert route(3, 8, T=2) == fused and route(3, 8, T=1) == iter2 and route(3, 8, T=0) == iter2
+    assert route(3, 64, T=1) == exact and route(3, 64, T=0) == general_wide
+    assert route(3, 64, T=1, flags=XP | BF) == bf16 and route(3, 64, T=0, flags=XP | BF) == general_wide
+    assert route(3, 16, T=0) == general
+    # k_iter2 needs every tile in LDS mode, tiles at all, and all six 16-bit lists / schedules
+    assert route(3, 8, n_lds_tiles=3) == general and route(3, 8, n_tiles=0) == general
+    for name in _LISTS16:
+        assert route(3, 8, missing=(name,)) == general, name
+    assert route(3, 8, missing=("in_nbr", "out_nbr")) == fused            # (k_iter2 reads the 16-bit lists only)
+    # ... and both windows inside the 160 KB of LDS: (652 table + 848 matrix-core + 4 + 16 (cap_a + cap_b)) floats
+    r = _lib.plan_route(_route_plan(lds_in=1216, lds_out=1216), 3, 8, 3, flags=XP)
+    assert (r["family"], r["fuse_first"], r["cap_a"], r["cap_b"], r["iter2_lds"]) == ("k_iter2", True, 1232, 1232, 163712)
+    r = _lib.plan_route(_route_plan(lds_in=1217, lds_out=1216), 3, 8, 3, flags=XP)
+    assert (r["family"], r["input"], r["cap_a"], r["cap_b"], r["iter2_lds"]) == ("k_iter", "k_input4", 1248, 1232, 164736)
+    assert route(3, 8, lds_in=1216, lds_out=1217) == general
+    # the sizes of a small plan: k_iter (652 + 16 x 204 records + 4) floats, k_iter2 (1504 + 16 x 256), k_edge (8 x 300 + 4)
+    r = _lib.plan_route(_route_plan(), 3, 8, 3, flags=XP)
+    assert (r["iter_lds"], r["iter2_lds"], r["cap_a"], r["cap_b"], r["edge_lds"], r["wide_window"]) == \
+        (15680, 22400, 128, 128, 9616, 0)
+    # bf16 flag: hidden_dim 32 / 64 up to input_dim 8 only
+    assert route(3, 32, flags=XP | BF) == bf16 and route(2, 32, flags=BF) == bf16 and route(3, 64, flags=XP | BF) == bf16
+    assert route(3, 16, flags=XP | BF) == exact16 and route(11, 16, flags=XP | BF) == general
+    assert route(3, 8, flags=XP | BF) == fused
+    # groups of k_iter_w / k_iter_wx: 3 MB of record rows (8 D bytes exact, 4 D bytes bf16); no LDS windows
+    for F, D, flags, window in ((3, 64, XP, 6144), (3, 64, XP | BF, 12288), (3, 32, XP, 12288), (3, 32, XP | BF, 24576),
+                                (3, 16, XP, 24576)):
+        r = _lib.plan_route(_route_plan(), F, D, 3, flags=flags)
+        assert (r["wide_window"], r["iter2_lds"], r["cap_a"]) == (window, 0, 0), (F, D, flags)
+    assert _lib.plan_route(_route_plan(), 3, 64, 3)["edge_lds"] == 16
+    assert _lib.plan_route(_route_plan(), 3, 16, 3)["iter_lds"] == (2004 + 4) * 4        # wide16: no record windows
+    # the role-split kernel from 32768 padded hits on
+    for F, D, flags, small, large in ((3, 64, XP, exact, exact_wx), (3, 64, XP | BF, bf16, bf16_wx),
+                                      (2, 32, 0, exact, exact_wx)):
+        assert route(F, D, flags=flags, n_pad=32767) == small and route(F, D, flags=flags, n_pad=32768) == large
+    assert route(3, 16, n_pad=32767) == exact16 and route(3, 16, n_pad=32768) == exact16[:2] + ("k_iter_wx",) + exact16[3:]
+    # 32-bit record offsets, D = 64: (n_pad + 2) rows of 512 bytes (exact) / 256 bytes (bf16) below 4 GiB
+    assert route(3, 64, n_pad=8388605) == exact_wx and route(3, 64, n_pad=8388606) == general_wide
+    assert route(3, 64, flags=XP | BF, n_pad=16777213) == bf16_wx
+    assert route(3, 64, flags=XP | BF, n_pad=16777214) == general_wide
+    assert route(3, 64, flags=XP | BF, n_pad=8388606) == bf16_wx
+    # the switches, one at a time
+    monkeypatch.setenv("GNN_NO_ITER2", "1")
+    assert route(3, 8) == general and route(2, 8) == general and route(3, 64) == exact
+    monkeypatch.delenv("GNN_NO_ITER2")
+    monkeypatch.setenv("GNN_NO_FUSE_FIRST", "1")
+    assert route(3, 8) == iter2 and route(2, 4) == iter2 and route(3, 64) == exact
+    monkeypatch.delenv("GNN_NO_FUSE_FIRST")
+    monkeypatch.setenv("GNN_NO_WIDE_EXACT", "1")
+    assert route(3, 64) == general_wide and route(3, 32) == general_wide and route(3, 16) == general
+    assert route(3, 64, flags=XP | BF) == bf16 and route(3, 8) == fused
+    monkeypatch.delenv("GNN_NO_WIDE_EXACT")
+    monkeypatch.setenv("GNN_WIDE_ROLES", "1")
+    assert route(3, 64) == exact_wx and route(3, 32, flags=XP | BF) == bf16_wx and route(3, 8) == fused
+    monkeypatch.setenv("GNN_WIDE_LOCKSTEP", "1")                        # both: the barrier kernel
+    assert route(3, 64) == exact and route(3, 64, n_pad=40000) == exact
+    monkeypatch.delenv("GNN_WIDE_ROLES")
+    assert route(3, 64, n_pad=40000) == exact and route(3, 64, flags=XP | BF, n_pad=40000) == bf16
+    monkeypatch.delenv("GNN_WIDE_LOCKSTEP")
+    assert route(3, 64, n_pad=40000) == exact_wx
+    # bad arguments are refused before anything is read
+    lib, out = _lib.load(), (ctypes.c_int32 * len(_lib.ROUTE_FIELDS))()
+    assert lib.gnn_plan_route(None, None, 1, 0, out) == _lib.GNN_ERR_BADARG
+    P = _lib.GnnParams()
+    P.F, P.D = 3, 8
+    assert lib.gnn_plan_route(ctypes.byref(_route_plan()), ctypes.byref(P), -1, 0, out) == _lib.GNN_ERR_BADARG
+    assert lib.gnn_plan_route(ctypes.byref(_route_plan()), ctypes.byref(P), 1, 0, None) == _lib.GNN_ERR_BADARG
+
+
+def test_plan_workspace_bytes_are_pinned():
+    """gnn_plan_workspace_bytes per shape at n_pad 0, 1, 255, 256 and 100000, as recorded from the build before the
+    workspace was carved with common.h's Carver."""
+    from gnn_fpga_amd import _lib
+    recorded = {
+        (2, 4): [11520, 11520, 54784, 56576, 17611520],
+        (2, 8): [21248, 21248, 109568, 111360, 35221248],
+        (2, 16): [52992, 52992, 231424, 233216, 70452992],
+        (2, 32): [132608, 133632, 491264, 493056, 140932608],
+        (3, 4): [11520, 11520, 54784, 56576, 17611520],
+        (3, 8): [21248, 21248, 109568, 111360, 35221248],
+        (3, 16): [53504, 53504, 231936, 233728, 70453504],
+        (3, 32): [133376, 134400, 492032, 493824, 140933376],
+        (3, 64): [379904, 382720, 1097984, 1100800, 281979904],
+        (11, 4): [12288, 12288, 55552, 57344, 17612288],
+        (11, 8): [22784, 22784, 111104, 112896, 35222784],
+        (11, 16): [46080, 46080, 224512, 226304, 70446080],
+    }
+    for (F, D), want in recorded.items():
+        assert [_lib.plan_workspace_bytes(n, 0, F, D) for n in (0, 1, 255, 256, 100000)] == want, (F, D)

@@ -260,12 +260,8 @@ def test_new_symbols_are_declared_bound_and_exported():
 
 
 def test_units_name_event_graphs():
-    with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "Makefile")) as fh:
-        units = re.search(r"^UNITS\s*:=\s*(.*)$", fh.read(), flags=re.M).group(1).split()
-    assert "event_graphs" in units
-    for tool in ("ab_build.sh", "ablate_build.sh"):
-        with open(os.path.join(REPO, "tools", tool)) as fh:
-            assert "build/event_graphs.o" in fh.read()
+    from variant_scripts import assert_variant_libraries_link
+    assert_variant_libraries_link("event_graphs")
 
 
 def test_new_kernels_have_no_scratch():

@@ -292,7 +292,7 @@ def test_bf16_route_against_its_emulation(hip, refs, case, monkeypatch):
 
 @pytest.mark.parametrize("F,D", [(2, 32), (3, 64)])
 def test_bf16_declined_without_iterations(hip, F, D):
-    """n_iters = 0 with mlp_bf16: the route needs an iteration (forward_t), so the fp32 path runs - same bits, no
+    """n_iters = 0 with mlp_bf16: the route needs an iteration (choose_route), so the fp32 path runs - same bits, no
     k_pack16."""
     from gnn_fpga_amd.model import SegmentClassifier
     torch.manual_seed(D)

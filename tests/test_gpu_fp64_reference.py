@@ -133,7 +133,7 @@ def refs():
 # ---- training -----------------------------------------------------------------------------------------------------
 # (family, F, D, T, loss, masked, weight seed, routes, what it is there for)
 ALL = ("pass", "twin", "twin_pp")
-WIDE = ("pass", "twin_pp")         # no fused training forward: forward_train_t declines D > 16 and D = 16 with F <= 4
+WIDE = ("pass", "twin_pp")         # no fused training forward: choose_route declines D > 16 and D = 16 with F <= 4
 TRAIN_CASES = [
     ("c3x4", 3, 8, 3, "torch", False, 1, ALL, "the headline shape; 1 % padded segments scattered through the order"),
     ("c3x4", 2, 4, 1, "fused_mean", False, 2, ALL, "narrowest shape, one iteration"),

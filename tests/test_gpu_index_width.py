@@ -5,7 +5,7 @@ tests/big_graphs.py from copies of a pool of distinct odd-sized graphs in a seed
 scores are compared with its own pool graph's reference (index_c in fp64; oracle.bf16_torch for the bf16 route).
 The worst copy is reported with the plan rows it occupies.
 
-  wide guard     forward_t (csrc/sell_pipeline.hip) runs the wide kernels (k_iter_w / k_iter_wx, 32-bit byte offsets
+  wide guard     choose_route (csrc/sell_pipeline.hip) picks the wide kernels (k_iter_w / k_iter_wx, 32-bit byte offsets
                  off a wave-uniform base) only while (n_pad + 2) * D * B < 2^32, B = 4 (bf16) or 8 (exact fp32).
                  Each shape runs once with n_pad within 1 MiB of rows below the guard and once within 1 MiB above
                  it, and asserts from the kernel names which route ran on each side.

@@ -248,12 +248,8 @@ def test_new_symbols_are_declared_bound_and_exported():
 
 
 def test_units_name_select_hits():
-    with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "Makefile")) as fh:
-        units = re.search(r"^UNITS\s*:=\s*(.*)$", fh.read(), flags=re.M).group(1).split()
-    assert "select_hits" in units
-    for tool in ("ab_build.sh", "ablate_build.sh"):
-        with open(os.path.join(REPO, "tools", tool)) as fh:
-            assert "build/select_hits.o" in fh.read()
+    from variant_scripts import assert_variant_libraries_link
+    assert_variant_libraries_link("select_hits")
     with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "select_hits.hip")) as fh:
         src = fh.read()
     assert "#pragma clang fp contract(off)" in src and '#include "builder_sort.h"' in src
