@@ -1778,16 +1778,18 @@ struct RecW {                   // one step group (4 list steps): this lane's pi
 
 // score the 4 segments of a group for the 4 hits of this wave pass and add their weighted R / S;
 // dimension pairs run on packed fp32 (v_pk_fma_f32 / v_pk_mul_f32: two lanes of math per issue slot)
-template <int D, bool XP, bool EX = false>
+// REM < 4 (a list's last group, see sweep_w): only records 0 .. REM-1 of the group were gathered; lanes q >= REM of
+// a quad then hold a score of nothing, which no lane picks up
+template <int D, bool XP, bool EX = false, int REM = 4>
 __device__ __forceinline__ void score_w(const RecW<D, EX> &g, const float *own, const float *w2, float b2, int p,
                                         float *acc)
 {
     constexpr int DL = D / 16;
     static_assert(DL == 1 || DL % 2 == 0, "one dimension per lane, or dimension pairs");
     const f2_t one2 = {1.0f, 1.0f};
-    float part[4];
+    float part[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < REM; ++j) {
         float P[DL];
         g.r[j].first(P);
         if constexpr (DL == 1) {
@@ -1824,7 +1826,7 @@ __device__ __forceinline__ void score_w(const RecW<D, EX> &g, const float *own, 
     const float e = r_f(mine + b2);
     const float e4[4] = {quad_bcast_f<0>(e), quad_bcast_f<1>(e), quad_bcast_f<2>(e), quad_bcast_f<3>(e)};
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < REM; ++j) {
         float R[DL];
         g.r[j].second(R);
         if constexpr (DL == 1) {
@@ -1843,7 +1845,8 @@ __device__ __forceinline__ void score_w(const RecW<D, EX> &g, const float *own, 
 
 // walk one hit's list (all 16 lanes of the hit together); `lst` = nbr + the slice's list base
 // (wave-uniform), `i16` the hit's index in the slice; two record groups in flight
-template <int D, bool XP, bool EX = false>
+// TRIM: the last group's real records only, see below (off where the caller has no register to spare for it)
+template <int D, bool XP, bool EX = false, bool TRIM = true>
 __device__ __forceinline__ void sweep_w(const int32_t *__restrict__ lst, int i16, int len, int null_idx,
                                         const void *__restrict__ REC, int p, const float *own, const float *w2,
                                         float b2, float *acc)
@@ -1859,16 +1862,54 @@ __device__ __forceinline__ void sweep_w(const int32_t *__restrict__ lst, int i16
         return 4 * c + (p & 3) < len ? cur : null_idx;   // (up to 3 steps past the end: plan.py pads the arrays)
     };
     RecW<D, EX> a, b;
+#ifdef GNN_NO_TRIM
+    constexpr bool trim = false;               // (A / B builds: every group whole)
+#else
+    constexpr bool trim = TRIM;
+#endif
     int ia = index_of(0), ib = ng > 1 ? index_of(1) : 0;
-    a.read(ia, REC, lane_off);
-    for (int c = 0; c < ng; c += 2) {
-        if (c + 1 < ng) b.read(ib, REC, lane_off);
-        if (c + 2 < ng) ia = index_of(c + 2);
-        score_w<D, XP, EX>(a, own, w2, b2, p, acc);
-        if (c + 1 < ng) {
-            if (c + 2 < ng) a.read(ia, REC, lane_off);
-            if (c + 3 < ng) ib = index_of(c + 3);
-            score_w<D, XP, EX>(b, own, w2, b2, p, acc);
+    if constexpr (!trim) {
+        a.read(ia, REC, lane_off);
+        for (int c = 0; c < ng; c += 2) {
+            if (c + 1 < ng) b.read(ib, REC, lane_off);
+            if (c + 2 < ng) ia = index_of(c + 2);
+            score_w<D, XP, EX>(a, own, w2, b2, p, acc);
+            if (c + 1 < ng) {
+                if (c + 2 < ng) a.read(ia, REC, lane_off);
+                if (c + 3 < ng) ib = index_of(c + 3);
+                score_w<D, XP, EX>(b, own, w2, b2, p, acc);
+            }
+        }
+    } else {
+        // Group c has n = len - 4 c steps left: the last group gathers and scores only its 1 to 4 real records (the
+        // steps behind them are NULL for every hit of the slice, a gathered NULL row is a row from L2 or HBM, and its
+        // share of the sum is e * 0).  `len` is wave-uniform (the slice's step count): scalar branches, no predication.
+        // (k_iter2's sweep16 scores whole groups: its padding steps are LDS reads - profiles/trim_walk_ab.txt.)
+        auto read_n = [&](RecW<D, EX> &g, int idx, int n) {
+            const int nb[4] = {quad_bcast_i<0>(idx), quad_bcast_i<1>(idx), quad_bcast_i<2>(idx), quad_bcast_i<3>(idx)};
+            const char *base = reinterpret_cast<const char *>(REC);
+            constexpr unsigned rb = RecW<D, EX>::row_bytes;
+            g.r[0].load(base + ((unsigned)nb[0] * rb + lane_off));
+            if (n > 1) g.r[1].load(base + ((unsigned)nb[1] * rb + lane_off));
+            if (n > 2) g.r[2].load(base + ((unsigned)nb[2] * rb + lane_off));
+            if (n > 3) g.r[3].load(base + ((unsigned)nb[3] * rb + lane_off));
+        };
+        auto score_n = [&](const RecW<D, EX> &g, int n) {
+            if (n >= 4) score_w<D, XP, EX>(g, own, w2, b2, p, acc);
+            else if (n == 3) score_w<D, XP, EX, 3>(g, own, w2, b2, p, acc);
+            else if (n == 2) score_w<D, XP, EX, 2>(g, own, w2, b2, p, acc);
+            else score_w<D, XP, EX, 1>(g, own, w2, b2, p, acc);
+        };
+        read_n(a, ia, len);
+        for (int c = 0; c < ng; c += 2) {
+            if (c + 1 < ng) read_n(b, ib, len - 4 * (c + 1));
+            if (c + 2 < ng) ia = index_of(c + 2);
+            score_n(a, len - 4 * c);
+            if (c + 1 < ng) {
+                if (c + 2 < ng) read_n(a, ia, len - 4 * (c + 2));
+                if (c + 3 < ng) ib = index_of(c + 3);
+                score_n(b, len - 4 * (c + 1));
+            }
         }
     }
 }
@@ -1898,6 +1939,9 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
     const unsigned *__restrict__ QS, float *__restrict__ U, float *__restrict__ PRn, float *__restrict__ QSn,
     float *__restrict__ Pc, float *__restrict__ Qc, int64_t n_pad, int tiles_per_xcd, int n_tiles, int wmax)
 {
+    // exact fp32 rows at D = 64 use every register this kernel has (126 - 128 VGPRs): with a trimmed tail group the
+    // compiler's resource remarks show 12 bytes of scratch per lane, so this shape keeps whole groups
+    constexpr bool TRIMW = !(EX && D == 64);
     using L = TL<F, D>;
     using B = std::conditional_t<EX, BX<F, D>, BL<F, D>>;      // EX: exact fp32 fragments and fp32 record rows
     static_assert(D % 16 == 0, "16 lanes x D / 16 dims per hit, matrix-core tail");
@@ -1993,7 +2037,7 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
             load_vec<DL>(U + n * D + DL * p, acc);
             load_own_w<D, EX>(QS, n, p, ownQ);
 #ifndef GNN_ABLATE_W_SWEEP
-            sweep_w<D, XP, EX>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
+            sweep_w<D, XP, EX, TRIMW>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
 #endif
             store_vec<DL>(U + n * D + DL * p, acc);    // (re-read by this same lane in phase B)
         }
@@ -2015,12 +2059,12 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
                     float ownQ[DL];
                     load_own_w<D, EX>(QS, n, p, ownQ);
                     load_own_w<D, EX>(PR, n, p, ownP);
-                    sweep_w<D, XP, EX>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
+                    sweep_w<D, XP, EX, TRIMW>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
                 } else {
                     load_own_w<D, EX>(PR, n, p, ownP);
                 }
 #ifndef GNN_ABLATE_W_SWEEP
-                sweep_w<D, XP, EX>(out_nbr + ob, i16, ol, (int)n_pad, QS, p, ownP, w2, b2, acc);
+                sweep_w<D, XP, EX, TRIMW>(out_nbr + ob, i16, ol, (int)n_pad, QS, p, ownP, w2, b2, acc);
 #endif
 #pragma unroll
                 for (int i = 0; i < DL; ++i) acc[i] = tanh_f(acc[i]);
@@ -2401,7 +2445,7 @@ __global__ __launch_bounds__(1024) void k_iter2(
     const int32_t *__restrict__ sched_b, const float *__restrict__ PR,
     const float *__restrict__ QS, float *__restrict__ U, float *__restrict__ PRn,
     float *__restrict__ QSn, float *__restrict__ Pc, float *__restrict__ Qc, int64_t n_pad,
-    int n_tiles, int capA, int capB, int xbuf_floats)
+    int n_tiles, int capA, int capB, int xbuf_floats, int backward)
 {
     using L = TL<F, D>;
     constexpr int d4 = L::d4, NT = 1024, NWV = NT / 64, NC = 3;   // NC words = 24 list steps
@@ -2436,9 +2480,13 @@ __global__ __launch_bounds__(1024) void k_iter2(
                                : (int)((blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3));
     if (tile >= n_tiles) return;
 
+    // `tile` and its successors are positions of the walk; `backward` walks the same positions from the batch's
+    // other end (position l = tile n_tiles - 1 - l; neighbours in the walk stay neighbours in memory and in an
+    // XCD).  The launches of a forward alternate, so what one launch wrote last - still in the Infinity Cache -
+    // is what the next one reads first (launch_iter2).
     struct Desc { int s_begin, s_end, in_lo, in_cnt, out_lo, out_cnt, sbase; };
     auto load_desc = [&](int t) {
-        const int32_t *td = tiles + (int64_t)t * DESC;
+        const int32_t *td = tiles + (int64_t)(backward ? n_tiles - 1 - t : t) * DESC;
         Desc d;
         d.s_begin = td[0]; d.s_end = td[1]; d.in_lo = td[2]; d.in_cnt = td[3];
         d.out_lo = td[4]; d.out_cnt = td[5]; d.sbase = td[7];
@@ -2961,14 +3009,15 @@ __global__ __launch_bounds__((Cfg<F, D>::NT)) void k_edge(
     const int32_t *__restrict__ dst, const int32_t *__restrict__ sd16,
     const float *__restrict__ Pc, const float *__restrict__ Qc,
     const float *__restrict__ table, float *__restrict__ e, int64_t n_pad, int chunks_per_xcd,
-    int n_chunks)
+    int n_chunks, int backward)
 {
     using G = Cfg<F, D>;
     const float *__restrict__ W2 = table + TL<F, D>::o_flat;   // wave-uniform: scalar loads
     constexpr int NT = G::NT;
     extern __shared__ __attribute__((aligned(16))) float win[];    // sized from the plan
-    const int chunk = (blockIdx.x & 7) * chunks_per_xcd + (blockIdx.x >> 3);
-    if (chunk >= n_chunks) return;
+    const int pos = (blockIdx.x & 7) * chunks_per_xcd + (blockIdx.x >> 3);
+    if (pos >= n_chunks) return;
+    const int chunk = backward ? n_chunks - 1 - pos : pos;        // (as k_iter2's tile walk)
     const int32_t *cd = chunks + (int64_t)chunk * DESC;
     const int e0 = cd[0], e1 = cd[1], s_lo = cd[2], s_cnt = cd[3], d_lo = cd[4], d_cnt = cd[5],
               mode = cd[6];
@@ -3242,6 +3291,30 @@ Route choose_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, con
     return r;
 }
 
+// The direction in which launch t of the k_iter2 route walks the batch: forward, backward, forward, ...; k_edge then
+// walks against the last of them.  A launch moves more bytes than the Infinity Cache keeps (256 MiB), so with every
+// launch walking the same way nothing a launch wrote is still there when the next one comes to read it; walking
+// back, the next launch starts on the tiles written last.  The other families walk forward only (their launchers
+// take no direction), and so does every k_edge behind them.
+inline bool walks_backward(const Route &r, int t)
+{
+#ifdef GNN_FORWARD_WALK
+    (void)r; (void)t;
+    return false;                // (A / B builds)
+#else
+    return r.family == GNN_FAMILY_K_ITER2 && (t & 1);
+#endif
+}
+inline bool edge_walks_backward(const Route &r, int n_iters)
+{
+#ifdef GNN_FORWARD_WALK
+    (void)r; (void)n_iters;
+    return false;
+#else
+    return r.family == GNN_FAMILY_K_ITER2 && n_iters > 0 && !walks_backward(r, n_iters - 1);
+#endif
+}
+
 // a run-time flag as a template argument: fn(std::true_type{}) or fn(std::false_type{})
 template <typename Fn>
 int with_flag(bool flag, Fn &&fn)
@@ -3335,7 +3408,7 @@ int launch_iter(const Run &c, bool last, const TrainOut &tro)
 
 // k_iter2: the persistent phase-split kernel; `first`: with the input network fused in
 template <int F, int D, bool XP>
-int launch_iter2(const Run &c, bool first, bool last)
+int launch_iter2(const Run &c, bool first, bool last, bool backward)
 {
     using G = Cfg<F, D>;
     const gnn_plan_t *pl = c.pl;
@@ -3348,7 +3421,7 @@ int launch_iter2(const Run &c, bool first, bool last)
         GNN_LAUNCH_SH("k_iter2", (k_iter2<F, D, LAST, XP, FIRST>), grid, 1024, (size_t)c.r.it2_lds, c.s, pl->X, w.table,
                       *c.p, w.table, pl->tiles, pl->in_off, pl->in_off16, pl->in_nbr16, pl->out_off, pl->out_off16,
                       pl->out_nbr16, pl->sched_a, pl->sched_b, c.PR, c.QS, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, nt,
-                      (int)c.r.capA, (int)c.r.capB, 0);
+                      (int)c.r.capA, (int)c.r.capB, 0, backward ? 1 : 0);
         return 0;
     };
     if constexpr (XP && G::fuse_first)       // (choose_route asks for `first` on these shapes only)
@@ -3393,7 +3466,7 @@ int launch_wide(const Run &c, bool last)
 
 // the final edge pass: e_out in the plan's segment order
 template <int F, int D, bool XP>
-int launch_edge(const Run &c, float *e_out)
+int launch_edge(const Run &c, float *e_out, bool backward)
 {
     using G = Cfg<F, D>;
     const gnn_plan_t *pl = c.pl;
@@ -3412,7 +3485,7 @@ int launch_edge(const Run &c, float *e_out)
     } else {
         const int nc = (int)pl->n_chunks, cpx = (nc + 7) / 8;
         GNN_LAUNCH_SH("k_edge", (k_edge<F, D, XP>), 8 * cpx, G::NT, (size_t)c.r.ed_lds, c.s, pl->chunks, pl->src, pl->dst,
-                      pl->sd16, w.Pc, w.Qc, w.table, e_out, pl->n_pad, cpx, nc);
+                      pl->sd16, w.Pc, w.Qc, w.table, e_out, pl->n_pad, cpx, nc, backward ? 1 : 0);
     }
     return 0;
 }
@@ -3461,7 +3534,8 @@ int forward_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const Sw
                     rc = launch_iter<F, D, XP, TR>(c, last, tro);
                 } else if constexpr (!TR) {
                     if (c.r.family == GNN_FAMILY_K_ITER2) {
-                        if constexpr (G::iter2) rc = launch_iter2<F, D, XP>(c, t == 0 && c.r.fuse_first, last);
+                        if constexpr (G::iter2)
+                            rc = launch_iter2<F, D, XP>(c, t == 0 && c.r.fuse_first, last, walks_backward(c.r, t));
                     } else if (c.r.rec == GNN_REC_BF16) {
                         if constexpr (D % 32 == 0 && F <= 8) rc = launch_wide<F, D, XP, false>(c, last);
                     } else {
@@ -3474,7 +3548,7 @@ int forward_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const Sw
             }
         }
         if (E > 0 && (!TR || e_out))
-            if (int rc = launch_edge<F, D, XP>(c, e_out)) return rc;
+            if (int rc = launch_edge<F, D, XP>(c, e_out, edge_walks_backward(c.r, n_iters))) return rc;
         if constexpr (TR)
             if (E > 0 && tr.tw_src)      // row T of e_all: the final scores in the backward's own segment order
                 GNN_LAUNCH("k_edge_tw", (k_edge_tw<F, D, XP>), grid_for(E), 256, s, tr.tw_src, tr.tw_dst, w.Pc, w.Qc,
