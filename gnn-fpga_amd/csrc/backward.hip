@@ -35,9 +35,9 @@
 namespace {
 using namespace gnn;
 
-template <int F, int D>
+template <int F_, int D_>
 struct Shape {
-    static constexpr int C = F + D;
+    static constexpr int F = F_, D = D_, C = F + D;
     static constexpr int LDH = (C + 3) & ~3;
 };
 
@@ -1651,6 +1651,10 @@ __global__ __launch_bounds__(kBlock) void k_seg_grad(const int32_t *__restrict__
     }
 }
 
+// floats of one gradient replica, and from one replica to the next (separate 256-byte lines), at a run-time shape
+constexpr int replica_floats(int F, int D) { return D * F + D + D * 2 * (F + D) + D + D + 1 + D * 3 * (F + D) + D + D * D + D; }
+constexpr int replica_stride(int F, int D) { return (replica_floats(F, D) + 63) & ~63; }
+
 // layout of one gradient replica (floats): the ten tensors in state_dict order
 template <int F, int D>
 struct GradLayout {
@@ -1658,7 +1662,8 @@ struct GradLayout {
     static constexpr int oWin = 0, obin = oWin + D * F, oW1 = obin + D, ob1 = oW1 + D * 2 * C,
                          oW2 = ob1 + D, ob2 = oW2 + D, oW3 = ob2 + 1, ob3 = oW3 + D * 3 * C,
                          oW4 = ob3 + D, ob4 = oW4 + D * D, total = ob4 + D;
-    static constexpr int stride = (total + 63) & ~63;      // replicas on separate 256-byte lines
+    static constexpr int stride = replica_stride(F, D);
+    static_assert(total == replica_floats(F, D), "the workspace is sized for this layout");
 };
 
 // rows of the partial table -> the caller's gradient tensors, in a fixed order: thread (element i,
@@ -1730,38 +1735,32 @@ inline int64_t bwd_rows(int64_t N, int64_t E)
 
 struct BwdWs {
     float *PQ, *gu, *gHa, *gHb, *gmio, *rep, *tmp, *A, *B, *G4, *SW;
-    char *rep_end;
     int64_t rows;
-    size_t bytes;
+    size_t rep_bytes, zero_bytes, bytes;      // the replicas; gHa and the replicas; the whole workspace
 };
 
-BwdWs carve_bwd(char *b, int64_t N, int64_t E, int ldh, int C, int D)
+BwdWs carve_bwd(char *b, int64_t N, int64_t E, int F, int D)
 {
+    const size_t ldh = (F + D + 3) & ~3, stride = replica_stride(F, D);
+    Carver c{b};
     BwdWs w;
-    size_t off = 0;
-    auto take = [&](size_t nfloat) {
-        float *p = reinterpret_cast<float *>(b + off);
-        off += align256(nfloat * sizeof(float));
-        return p;
-    };
-    w.PQ = take((size_t)N * 2 * D);
-    w.gu = take((size_t)E);
-    w.gHb = take((size_t)N * ldh);
-    w.gmio = take((size_t)N * 2 * ldh);      // [gmi | gmo], rows padded to LDH
-    // gHa and the gradient replicas (GradLayout<F, D>::stride each; F = C - D) are adjacent: one
-    // memset clears both
-    w.gHa = take((size_t)N * ldh);
-    const int tot = D * (C - D) + D + D * 2 * C + D + D + 1 + D * 3 * C + D + D * D + D;
-    const size_t stride = (size_t)((tot + 63) & ~63);
+    w.PQ = c.take<float>((size_t)N * 2 * D);
+    w.gu = c.take<float>((size_t)E);
+    w.gHb = c.take<float>((size_t)N * ldh);
+    w.gmio = c.take<float>((size_t)N * 2 * ldh);     // [gmi | gmo], rows padded to LDH
+    // gHa and the gradient replicas are adjacent: one memset (zero_bytes from gHa) clears both
+    const size_t at_gHa = c.off;
+    w.gHa = c.take<float>((size_t)N * ldh);
     w.rows = bwd_rows(N, E);
-    w.rep = take((size_t)w.rows * stride);
-    w.rep_end = b + off;
-    w.tmp = take((size_t)fold_chunks(w.rows) * stride);
-    w.A = take((size_t)N * 3 * D);           // [P | R | gp], [Q | S | gp] of the pull-form kernels
-    w.B = take((size_t)N * 3 * D);
-    w.G4 = take((size_t)N * 4 * D);           // [gP gQ Gout Gin] between k_seg_bwd4 and k_seg_fin
-    w.SW = take(D >= 32 ? (size_t)N * (D + 4) : 0);   // wide shapes: a hit's gW2 / gb2 terms (k_seg_bwdW -> k_seg_finW)
-    w.bytes = off;
+    w.rep_bytes = (size_t)w.rows * stride * sizeof(float);
+    w.rep = c.take<float>((size_t)w.rows * stride);
+    w.zero_bytes = c.off - at_gHa;
+    w.tmp = c.take<float>((size_t)fold_chunks(w.rows) * stride);
+    w.A = c.take<float>((size_t)N * 3 * D);          // [P | R | gp], [Q | S | gp] of the pull-form kernels
+    w.B = c.take<float>((size_t)N * 3 * D);
+    w.G4 = c.take<float>((size_t)N * 4 * D);         // [gP gQ Gout Gin] between k_seg_bwd4 and k_seg_fin
+    w.SW = c.take<float>(D >= 32 ? (size_t)N * (D + 4) : 0);   // wide shapes: a hit's gW2 / gb2 terms (k_seg_bwdW -> k_seg_finW)
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -1836,165 +1835,203 @@ __global__ __launch_bounds__(kBlock) void k_head_fold2(const float *__restrict__
     *(i < C ? gWo + i : gbo) += sum;
 }
 
-template <int F, int D>
-int backward_t(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
-               const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
-               char *ws, hipStream_t s, const HeadBwd *head = nullptr)
+// ---- host side.  The environment switches of the backward (A / B runs, tests): this is their one reader, called
+// once per library call and not cached, like the forward's read_switches - tests flip them inside one process.
+struct BwdSwitches { bool wide_per_pass, no_fin_hit; };
+BwdSwitches read_bwd_switches()
 {
-    constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH;
-    const int64_t N = g->n_hits, E = g->n_segments;
-    BwdWs w = carve_bwd(ws, N, E, LDH, C, D);
+    return {getenv("GNN_BWD_WIDE_PER_PASS") != nullptr, getenv("GNN_BWD_NO_FIN_HIT") != nullptr};
+}
+
+// Which kernels a backward takes: fixed by choose_bwd_route before the first launch.
+enum class BwdStart {          // how gH_T starts
+    seeded_head,               // NodeClassifier: k_head_bwd writes it, the head folds add gWo, gbo; it has no edge pass T
+    edge_pass,                 // kb_pq, k_edge_bwd, k_pq_bwd with the loss gradient as ge
+    wide_final_pass,           // the wide triple on a zero gradient row, then k_edge_bwd for the padded segments only
+};
+enum class BwdIter {           // the form of iterations T .. 1 (T = 0: the starting pass is all there is)
+    quad,                      // D <= 16 with the forward's kept hidden layers: four lanes per hit in the walks
+    one_lane,                  // D <= 16 without them: kb_prs, k_hit_bwd, k_seg_bwd
+    wide,                      // D >= 32 with them: 16 lanes per hit
+    per_pass,                  // D >= 32 otherwise: node pass and edge pass in turn
+};
+struct BwdRoute { BwdStart start; BwdIter iter; bool fuse_fin_hit; };     // fuse_fin_hit (quad): k_fin_hit, see BwdRun::quad
+
+template <int F, int D>
+BwdRoute choose_bwd_route(int T, bool have_Q, bool have_head, bool have_grad_out, const BwdSwitches &sw)
+{
+    const BwdIter iter = D <= 16 ? (have_Q ? BwdIter::quad : BwdIter::one_lane)
+                       : D >= 32 && have_Q && !sw.wide_per_pass ? BwdIter::wide : BwdIter::per_pass;
+    const BwdStart start = have_head ? BwdStart::seeded_head
+                         : iter == BwdIter::wide && T > 0 && have_grad_out ? BwdStart::wide_final_pass : BwdStart::edge_pass;
+    return {start, iter, iter == BwdIter::quad && !sw.no_fin_hit};
+}
+
+#define BWD_LISTS g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr
+// One backward in flight: what its launchers share.  A launcher takes what differs between its calls - the H / e / Q
+// rows of the step, gH (the gradient row it reads) and gHprev (the one it writes) - and skips an empty batch.
+template <int F, int D>
+struct BwdRun {
     using GL = GradLayout<F, D>;
-    float *gH = w.gHa, *gHprev = w.gHb;
-    {   // hit gradient of the last iteration and the gradient replicas start at zero
-        hipError_t err = hipMemsetAsync(gH, 0, (size_t)(w.rep_end - reinterpret_cast<char *>(gH)), s);
-        if (err != hipSuccess) return fail(-(int)err, "memset of the gradient workspace failed");
+    static constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH, RS = GL::stride;
+    const gnn_graph_t *g;
+    const gnn_params_t *p;
+    hipStream_t s;
+    int64_t N, E;
+    BwdWs w;
+    float *rp;                 // the gradient replicas
+    BwdRun(const gnn_graph_t *g_, const gnn_params_t *p_, char *ws, hipStream_t s_)
+        : g(g_), p(p_), s(s_), N(g_->n_hits), E(g_->n_segments), w(carve_bwd(ws, N, E, F, D)), rp(w.rep) {}
+    int clear(float *from, size_t bytes) const
+    {
+        const hipError_t err = hipMemsetAsync(from, 0, bytes, s);
+        return err == hipSuccess ? 0 : fail(-(int)err, "memset of the gradient workspace failed");
     }
-    float *const rp = w.rep;
-    constexpr int RS = GL::stride;
-    if (w.rep_end - reinterpret_cast<char *>(rp) < (ptrdiff_t)((size_t)w.rows * RS * sizeof(float)))
-        return fail(GNN_ERR_WORKSPACE, "partial-gradient table does not match GradLayout");
-    if (head && N > 0) {
-        // seeded start (NodeClassifier): the output network's backward writes gH_T and folds gWo, gbo.  Its
-        // partial rows go to G4 and the chunk sums to tmp - both free until the trunk below (and big enough:
-        // grid_for(N) <= N rows of head_stride <= 4 D floats; at most w.rows rows of GradLayout::stride)
-        static_assert(head_stride<F, D>() <= 4 * D && head_stride<F, D>() <= RS, "head rows fit G4 and tmp");
+    // The output network's backward writes gH_T and folds gWo, gbo.  Its partial rows go to G4 and the chunk sums to
+    // tmp - both free until the trunk's kernels (and big enough: grid_for(N) <= N rows of head_stride <= 4 D floats;
+    // at most w.rows rows of GradLayout::stride)
+    int head_bwd(const HeadBwd &h, const float *H, float *gH) const
+    {
+        constexpr int PS = head_stride<F, D>();
+        static_assert(PS <= 4 * D && PS <= RS, "head rows fit G4 and tmp");
+        if (N <= 0) return 0;
         const unsigned hg = grid_for(N);
-        GNN_LAUNCH("k_head_bwd", (k_head_bwd<F, D>), hg, kBlock, s, H_all + (size_t)T * N * LDH, head->y, head->gy,
-                   head->Wo, gH, w.G4, N);
+        GNN_LAUNCH("k_head_bwd", (k_head_bwd<F, D>), hg, kBlock, s, H, h.y, h.gy, h.Wo, gH, w.G4, N);
         const int64_t nc = fold_chunks(hg);
-        GNN_LAUNCH("k_head_fold", k_head_fold1, dim3(1, (unsigned)nc), kBlock, s, w.G4, (int64_t)hg,
-                   head_stride<F, D>(), w.tmp);
-        GNN_LAUNCH("k_head_fold", k_head_fold2, 1, kBlock, s, w.tmp, nc, head_stride<F, D>(), C, head->gWo, head->gbo);
+        GNN_LAUNCH("k_head_fold", k_head_fold1, dim3(1, (unsigned)nc), kBlock, s, w.G4, (int64_t)hg, PS, w.tmp);
+        GNN_LAUNCH("k_head_fold", k_head_fold2, 1, kBlock, s, w.tmp, nc, PS, C, h.gWo, h.gbo);
+        return 0;
     }
-    const float *ge = head ? nullptr : grad_out;
-    for (int t = T; t >= 0; --t) {
-        const float *Ht = H_all + (size_t)t * N * LDH;
-        const float *et = e_all + (size_t)t * E;
-        // edge pass t backward: adds into gH (gradient w.r.t. H_t); a NodeClassifier has no edge pass T - its
-        // backward starts from the seeded gH_T
-        bool edge_done = head && t == T;
-        if constexpr (D >= 32) {
-            // wide shapes, final pass (the only edge pass this loop still runs for them): the pull-form
-            // kernels with the loss gradient as ge - k_hit_bwdW on a zero gradient row builds the records
-            // ([P R 0], [Q S 0]), the walks rebuild gu at both ends, k_seg_finW adds W1^T (gP, gQ); the
-            // padded segments (in no hit's list) keep their own pass
-            if (Q_all && t == T && T > 0 && ge && !getenv("GNN_BWD_WIDE_PER_PASS")) {
-                if (N > 0) {
-                    GNN_LAUNCH("k_hit_bwdW", (k_hit_bwdW<F, D>), grid_for(N), kFinThreads, s, Ht, Ht, Q_all, LDH, p->W1, p->b1,
-                               p->W3, p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
-                    GNN_LAUNCH("k_seg_bwdW", (k_seg_bwdW<F, D>), grid_rows(N), kQuadBlock, s, w.A, w.B, et, g->in_ptr,
-                               g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W2, w.G4, w.SW, N, ge);
-                    GNN_LAUNCH("k_seg_finW", (k_seg_finW<F, D>), grid_for(N), kFinThreads, s, Ht, LDH, w.G4, w.SW, p->W1, p->W3,
-                               gH, rp + GL::oW1, rp + GL::ob1, rp + GL::oW2, rp + GL::ob2, rp + GL::oW3, RS, N);
-                }
-                if (E > 0) {
-                    const unsigned ge_grid = grid_for(E) < (unsigned)kSegGrid ? grid_for(E) : (unsigned)kSegGrid;
-                    GNN_LAUNCH("k_edge_bwd", (k_edge_bwd<F, D>), ge_grid, kBlock, s, g->src, g->dst, w.PQ, p->b1, p->W2, et,
-                               ge, Ht, w.gmio, w.gu, rp + GL::oW2, rp + GL::ob2, rp + GL::ob1, RS, E, 1);
-                }
-                edge_done = true;
-            }
+    // Edge pass backward: adds the gradient w.r.t. H into gH.  ge null: rebuilt from gmio and H (the node pass that
+    // consumed these scores ran just before); padded_segments_only: k_edge_bwd alone (the wide final pass did the rest)
+    int edge_pass(const float *H, const float *e, const float *ge, float *gH, bool padded_segments_only = false) const
+    {
+        const bool hits = N > 0 && !padded_segments_only;
+        if (hits) GNN_LAUNCH("kb_pq", (kb_pq<F, D>), grid_for(N), kBlock, s, H, LDH, p->W1, p->b1, w.PQ, N);
+        if (E > 0) {
+            const unsigned grid = grid_for(E) < (unsigned)kSegGrid ? grid_for(E) : (unsigned)kSegGrid;
+            GNN_LAUNCH("k_edge_bwd", (k_edge_bwd<F, D>), grid, kBlock, s, g->src, g->dst, w.PQ, p->b1, p->W2, e, ge, H,
+                       w.gmio, w.gu, rp + GL::oW2, rp + GL::ob2, rp + GL::ob1, RS, E, padded_segments_only ? 1 : 0);
         }
-        if (!edge_done && N > 0) GNN_LAUNCH("kb_pq", (kb_pq<F, D>), grid_for(N), kBlock, s, Ht, LDH, p->W1, p->b1, w.PQ, N);
-        if (!edge_done && E > 0) {
-            const unsigned ge_grid = grid_for(E) < (unsigned)kSegGrid ? grid_for(E) : (unsigned)kSegGrid;
-            GNN_LAUNCH("k_edge_bwd", (k_edge_bwd<F, D>), ge_grid, kBlock, s, g->src, g->dst, w.PQ,
-                       p->b1, p->W2, et, ge, Ht, w.gmio, w.gu, rp + GL::oW2, rp + GL::ob2, rp + GL::ob1,
-                       RS, E);
-        }
-        if (!edge_done && N > 0)
-            GNN_LAUNCH("k_pq_bwd", (k_pq_bwd<F, D>), grid_for(N), kBlock, s, Ht, LDH, w.PQ, w.gu,
-                       g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W1, p->W2,
+        if (hits)
+            GNN_LAUNCH("k_pq_bwd", (k_pq_bwd<F, D>), grid_for(N), kBlock, s, H, LDH, w.PQ, w.gu, BWD_LISTS, p->W1, p->W2,
                        gH, rp + GL::oW1, rp + GL::ob1, RS, N);
-        if (t == 0) break;
-        if constexpr (D <= 16) {
-            // iterations t-1 .. 0 in pull form: node pass (H_{t-1}, e_{t-1} -> H_t) together with the
-            // edge pass that produced e_{t-1}
-            for (int u = t; u >= 1; --u) {
-                const float *Hu = H_all + (size_t)u * N * LDH;
-                const float *Hp = H_all + (size_t)(u - 1) * N * LDH;
-                const float *ep = e_all + (size_t)(u - 1) * E;
-                if (N > 0) {
-                    if (Q_all) {
-                        // k_hit_bwd4 (u) ran as the tail of the previous iteration's k_fin_hit, except for the first
-                        static const bool unfused = getenv("GNN_BWD_NO_FIN_HIT") != nullptr;      // A / B runs
-                        if (u == t || unfused)
-                            GNN_LAUNCH("k_hit_bwd4", (k_hit_bwd4<F, D>), grid_for(N), kBlock, s, Hp, Hu,
-                                       Q_all + (size_t)(u - 1) * N * D, LDH, p->W1, p->b1, p->W3, p->W4, gH, gHprev, w.A,
-                                       w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
-                        GNN_LAUNCH("k_seg_bwd4", (k_seg_bwd4<F, D>), grid_for(N), kQuadBlock, s, w.A, w.B, ep, g->in_ptr,
-                                   g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W2, w.G4, rp + GL::oW2,
-                                   rp + GL::ob2, RS, N);
-                        if (u > 1 && !unfused) {
-                            // the gradient row of H_{u-1} is finished in registers and feeds iteration u - 1's per-hit
-                            // pass at once: gHprev (its initial row) is read, gH (free by now) takes iteration u - 1's
-                            // initial row - after the swap below the roles are as a separate k_hit_bwd4 leaves them
-                            GNN_LAUNCH("k_fin_hit", (k_fin_hit<F, D>), grid_for(N), kBlock, s, Hp,
-                                       H_all + (size_t)(u - 2) * N * LDH, Q_all + (size_t)(u - 2) * N * D, LDH, w.G4, p->W1,
-                                       p->b1, p->W3, p->W4, gHprev, gH, w.A, w.B, rp + GL::oW1, rp + GL::ob1, rp + GL::oW3,
-                                       rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
-                        } else {
-                            GNN_LAUNCH("k_seg_fin", (k_seg_fin<F, D>), grid_for(N), kBlock, s, Hp, LDH, w.G4, p->W1, p->W3,
-                                       gHprev, rp + GL::oW1, rp + GL::ob1, rp + GL::oW3, RS, N);
-                        }
-                        float *tmp = gH; gH = gHprev; gHprev = tmp;
-                        continue;
-                    }
-                    GNN_LAUNCH("kb_prs", (kb_prs<F, D>), grid_for(N), kBlock, s, Hp, LDH, p->W1, p->b1, p->W3, w.A, w.B, N);
-                    GNN_LAUNCH("k_hit_bwd", (k_hit_bwd<F, D, false>), grid_for(N), kBlock, s, Hp, Hu, nullptr, LDH, ep,
-                               g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W3, p->b3,
-                               p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS,
-                               N);
-                    GNN_LAUNCH("k_seg_bwd", (k_seg_bwd<F, D>), grid_for(N), kBlock, s, Hp, LDH, w.A, w.B, ep, g->in_ptr,
-                               g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W1, p->W2, p->W3, gHprev,
-                               rp + GL::oW1, rp + GL::ob1, rp + GL::oW2, rp + GL::ob2, rp + GL::oW3, RS, N);
-                }
-                float *tmp = gH; gH = gHprev; gHprev = tmp;
-            }
-            break;
-        }
-        if constexpr (D >= 32) {
-            // wide hidden layers with the forward's kept hidden layers: pull form, 16 lanes per hit
-            if (Q_all && !getenv("GNN_BWD_WIDE_PER_PASS")) {
-                for (int u = t; u >= 1; --u) {
-                    const float *Hu = H_all + (size_t)u * N * LDH;
-                    const float *Hp = H_all + (size_t)(u - 1) * N * LDH;
-                    const float *ep = e_all + (size_t)(u - 1) * E;
-                    if (N > 0) {
-                        GNN_LAUNCH("k_hit_bwdW", (k_hit_bwdW<F, D>), grid_for(N), kFinThreads, s, Hp, Hu,
-                                   Q_all + (size_t)(u - 1) * N * D, LDH, p->W1, p->b1, p->W3, p->W4, gH, gHprev, w.A, w.B,
-                                   rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
-                        GNN_LAUNCH("k_seg_bwdW", (k_seg_bwdW<F, D>), grid_rows(N), kQuadBlock, s, w.A, w.B, ep, g->in_ptr,
-                                   g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W2, w.G4, w.SW, N,
-                                   (const float *)nullptr);
-                        GNN_LAUNCH("k_seg_finW", (k_seg_finW<F, D>), grid_for(N), kFinThreads, s, Hp, LDH, w.G4, w.SW, p->W1, p->W3,
-                                   gHprev, rp + GL::oW1, rp + GL::ob1, rp + GL::oW2, rp + GL::ob2, rp + GL::oW3, RS, N);
-                    }
-                    float *tmp = gH; gH = gHprev; gHprev = tmp;
-                }
-                break;
-            }
-        }
-        // (wide hidden layers without Q_all: the per-pass kernels) node pass t-1 backward: H_{t-1}, e_{t-1} -> H_t
-        const float *Hp = H_all + (size_t)(t - 1) * N * LDH;
-        const float *ep = e_all + (size_t)(t - 1) * E;
-        if (N > 0) {
-            GNN_LAUNCH("k_node_bwd", (k_node_bwd<F, D>), grid_for(N), kBlock, s, Hp, Ht, LDH, ep,
-                       g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W3,
-                       p->b3, p->W4, gH, gHprev, w.gmio, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4,
-                       rp + GL::ob4, RS, N);
-            GNN_LAUNCH("k_agg_bwd_n", (k_agg_bwd_n<F, D>), grid_for(N), kBlock, s, ep, w.gmio,
-                       g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, gHprev,
-                       LDH, N);
-        }
-        float *tmp = gH; gH = gHprev; gHprev = tmp;
-        ge = nullptr;      // the next (earlier) edge pass rebuilds its ge from gmio and H_{t-1}
+        return 0;
     }
-    if (N > 0)
-        GNN_LAUNCH("k_input_bwd", (k_input_bwd<F, D>), grid_for(N), kBlock, s, g->X, H_all, LDH, gH,
-                   rp + GL::oWin, rp + GL::obin, RS, N);
-    return grad_fold<F, D>(rp, w.rows, w.tmp, gr, s);
+    // node pass backward (Hp, ep -> Hu): gmi, gmo to gmio, the gradient w.r.t. Hp to gHprev
+    int node_pass(const float *Hp, const float *Hu, const float *ep, const float *gH, float *gHprev) const
+    {
+        if (N <= 0) return 0;
+        GNN_LAUNCH("k_node_bwd", (k_node_bwd<F, D>), grid_for(N), kBlock, s, Hp, Hu, LDH, ep, BWD_LISTS, p->W3, p->b3,
+                   p->W4, gH, gHprev, w.gmio, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
+        GNN_LAUNCH("k_agg_bwd_n", (k_agg_bwd_n<F, D>), grid_for(N), kBlock, s, ep, w.gmio, BWD_LISTS, gHprev, LDH, N);
+        return 0;
+    }
+    // one iteration in pull form on one lane per hit: node pass (Hp, ep -> Hu) together with the edge pass that made ep
+    int one_lane(const float *Hp, const float *Hu, const float *ep, const float *gH, float *gHprev) const
+    {
+        if constexpr (D <= 16) if (N > 0) {
+            GNN_LAUNCH("kb_prs", (kb_prs<F, D>), grid_for(N), kBlock, s, Hp, LDH, p->W1, p->b1, p->W3, w.A, w.B, N);
+            GNN_LAUNCH("k_hit_bwd", (k_hit_bwd<F, D, false>), grid_for(N), kBlock, s, Hp, Hu, nullptr, LDH, ep, BWD_LISTS, p->W3,
+                       p->b3, p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
+            GNN_LAUNCH("k_seg_bwd", (k_seg_bwd<F, D>), grid_for(N), kBlock, s, Hp, LDH, w.A, w.B, ep, BWD_LISTS, p->W1,
+                       p->W2, p->W3, gHprev, rp + GL::oW1, rp + GL::ob1, rp + GL::oW2, rp + GL::ob2, rp + GL::oW3, RS, N);
+        }
+        return 0;
+    }
+    // The same iteration on four lanes per hit (Qp: the kept hidden layer): the per-hit pass (`hit_pass` false: it ran as
+    // the tail of the previous iteration's k_fin_hit), the walk, the dense tail that finishes gHprev.  With Hpp, Qpp (the
+    // next, earlier iteration's rows) the tail and that iteration's per-hit pass are one launch: gHprev (its initial row)
+    // is read, gH (free by now) takes the next initial row - after the caller's swap as a separate k_hit_bwd4 leaves them
+    int quad(bool hit_pass, const float *Hp, const float *Hu, const float *Qp, const float *ep, const float *Hpp,
+             const float *Qpp, float *gH, float *gHprev) const
+    {
+        if constexpr (D <= 16) if (N > 0) {
+            if (hit_pass)
+                GNN_LAUNCH("k_hit_bwd4", (k_hit_bwd4<F, D>), grid_for(N), kBlock, s, Hp, Hu, Qp, LDH, p->W1, p->b1, p->W3,
+                           p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
+            GNN_LAUNCH("k_seg_bwd4", (k_seg_bwd4<F, D>), grid_for(N), kQuadBlock, s, w.A, w.B, ep, BWD_LISTS, p->W2, w.G4,
+                       rp + GL::oW2, rp + GL::ob2, RS, N);
+            if (Hpp)
+                GNN_LAUNCH("k_fin_hit", (k_fin_hit<F, D>), grid_for(N), kBlock, s, Hp, Hpp, Qpp, LDH, w.G4, p->W1, p->b1,
+                           p->W3, p->W4, gHprev, gH, w.A, w.B, rp + GL::oW1, rp + GL::ob1, rp + GL::oW3, rp + GL::ob3,
+                           rp + GL::oW4, rp + GL::ob4, RS, N);
+            else
+                GNN_LAUNCH("k_seg_fin", (k_seg_fin<F, D>), grid_for(N), kBlock, s, Hp, LDH, w.G4, p->W1, p->W3, gHprev,
+                           rp + GL::oW1, rp + GL::ob1, rp + GL::oW3, RS, N);
+        }
+        return 0;
+    }
+    // One iteration in pull form on 16 lanes per hit; k_seg_finW adds into gfin.  As the final edge pass: Hp = Hu =
+    // H_T, gH a zero row (k_hit_bwdW then only builds the records [P R 0], [Q S 0]), the loss gradient as ge - the
+    // walks rebuild gu at both ends - and gfin = gH
+    int wide(const float *Hp, const float *Hu, const float *Qp, const float *ep, const float *ge, const float *gH,
+             float *gHprev, float *gfin) const
+    {
+        if constexpr (D >= 32) if (N > 0) {
+            GNN_LAUNCH("k_hit_bwdW", (k_hit_bwdW<F, D>), grid_for(N), kFinThreads, s, Hp, Hu, Qp, LDH, p->W1, p->b1, p->W3,
+                       p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
+            GNN_LAUNCH("k_seg_bwdW", (k_seg_bwdW<F, D>), grid_rows(N), kQuadBlock, s, w.A, w.B, ep, BWD_LISTS, p->W2, w.G4,
+                       w.SW, N, ge);
+            GNN_LAUNCH("k_seg_finW", (k_seg_finW<F, D>), grid_for(N), kFinThreads, s, Hp, LDH, w.G4, w.SW, p->W1, p->W3,
+                       gfin, rp + GL::oW1, rp + GL::ob1, rp + GL::oW2, rp + GL::ob2, rp + GL::oW3, RS, N);
+        }
+        return 0;
+    }
+};
+
+template <int F, int D>
+int backward_t(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all, const float *H_all,
+               const float *Q_all, const float *grad_out, const gnn_grads_t *gr, char *ws, hipStream_t s,
+               const HeadBwd *head)
+{
+    const BwdRoute route = choose_bwd_route<F, D>(T, Q_all, head, grad_out, read_bwd_switches());
+    const BwdRun<F, D> c(g, p, ws, s);
+    const auto H = [&](int t) { return H_all + (size_t)t * c.N * c.LDH; };
+    const auto e = [&](int t) { return e_all + (size_t)t * c.E; };
+    const auto Q = [&](int t) { return Q_all + (size_t)t * c.N * D; };
+    float *gH = c.w.gHa, *gHprev = c.w.gHb;
+    // the hit gradient of the last iteration and the gradient replicas start at zero
+    int rc = c.clear(gH, c.w.zero_bytes);
+    if (rc) return rc;
+    switch (route.start) {
+    case BwdStart::seeded_head: rc = c.head_bwd(*head, H(T), gH); break;
+    case BwdStart::edge_pass: rc = c.edge_pass(H(T), e(T), grad_out, gH); break;
+    case BwdStart::wide_final_pass:
+        rc = c.wide(H(T), H(T), Q_all, e(T), grad_out, gH, gHprev, gH);
+        if (!rc) rc = c.edge_pass(H(T), e(T), grad_out, gH, true);      // (they are in no hit's list)
+        break;
+    }
+    // iteration u: node pass (H_{u-1}, e_{u-1} -> H_u) and the edge pass that made e_{u-1}; gH is the gradient w.r.t.
+    // H_u on entry and w.r.t. H_{u-1} after the swap
+    switch (route.iter) {
+    case BwdIter::quad:
+        for (int u = T; u >= 1 && !rc; --u, std::swap(gH, gHprev)) {
+            const bool fuse = route.fuse_fin_hit && u > 1;
+            rc = c.quad(u == T || !route.fuse_fin_hit, H(u - 1), H(u), Q(u - 1), e(u - 1), fuse ? H(u - 2) : nullptr,
+                        fuse ? Q(u - 2) : nullptr, gH, gHprev);
+        }
+        break;
+    case BwdIter::one_lane:
+        for (int u = T; u >= 1 && !rc; --u, std::swap(gH, gHprev)) rc = c.one_lane(H(u - 1), H(u), e(u - 1), gH, gHprev);
+        break;
+    case BwdIter::wide:
+        for (int u = T; u >= 1 && !rc; --u, std::swap(gH, gHprev))
+            rc = c.wide(H(u - 1), H(u), Q(u - 1), e(u - 1), nullptr, gH, gHprev, gHprev);
+        break;
+    case BwdIter::per_pass:
+        for (int u = T; u >= 1 && !rc; --u) {
+            rc = c.node_pass(H(u - 1), H(u), e(u - 1), gH, gHprev);
+            std::swap(gH, gHprev);
+            if (!rc) rc = c.edge_pass(H(u - 1), e(u - 1), nullptr, gH);      // ge rebuilt from gmio and H_{u-1}
+        }
+        break;
+    }
+    if (rc) return rc;
+    if (c.N > 0)
+        GNN_LAUNCH("k_input_bwd", (k_input_bwd<F, D>), grid_for(c.N), kBlock, s, g->X, H_all, c.LDH, gH,
+                   c.rp + GradLayout<F, D>::oWin, c.rp + GradLayout<F, D>::obin, c.RS, c.N);
+    return grad_fold<F, D>(c.rp, c.w.rows, c.w.tmp, gr, s);
 }
 
 // ---- per-module backward (the reference's sub-modules are ordinary autograd modules:
@@ -2006,24 +2043,10 @@ template <int F, int D>
 int edge_bwd_t(const float *H, const gnn_graph_t *g, const gnn_params_t *p, const float *e, const float *ge,
                float *gH, const gnn_grads_t *gr, char *ws, hipStream_t s)
 {
-    constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH;
-    const int64_t N = g->n_hits, E = g->n_segments;
-    BwdWs w = carve_bwd(ws, N, E, LDH, C, D);
-    using GL = GradLayout<F, D>;
-    float *const rp = w.rep;
-    constexpr int RS = GL::stride;
-    hipError_t err = hipMemsetAsync(rp, 0, (size_t)w.rows * RS * sizeof(float), s);
-    if (err != hipSuccess) return fail(-(int)err, "memset of the partial-gradient table failed");
-    if (N > 0) GNN_LAUNCH("kb_pq", (kb_pq<F, D>), grid_for(N), kBlock, s, H, LDH, p->W1, p->b1, w.PQ, N);
-    if (E > 0) {
-        const unsigned ge_grid = grid_for(E) < (unsigned)kSegGrid ? grid_for(E) : (unsigned)kSegGrid;
-        GNN_LAUNCH("k_edge_bwd", (k_edge_bwd<F, D>), ge_grid, kBlock, s, g->src, g->dst, w.PQ, p->b1, p->W2, e, ge, H,
-                   w.gmio, w.gu, rp + GL::oW2, rp + GL::ob2, rp + GL::ob1, RS, E);
-    }
-    if (N > 0)
-        GNN_LAUNCH("k_pq_bwd", (k_pq_bwd<F, D>), grid_for(N), kBlock, s, H, LDH, w.PQ, w.gu, g->in_ptr, g->in_eid,
-                   g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W1, p->W2, gH, rp + GL::oW1, rp + GL::ob1, RS, N);
-    return grad_fold<F, D>(rp, w.rows, w.tmp, gr, s);
+    const BwdRun<F, D> c(g, p, ws, s);
+    if (int rc = c.clear(c.rp, c.w.rep_bytes)) return rc;
+    if (int rc = c.edge_pass(H, e, ge, gH)) return rc;
+    return grad_fold<F, D>(c.rp, c.w.rows, c.w.tmp, gr, s);
 }
 
 // NodeNetwork: H' = tanh(W4 tanh(W3 [mi | mo | H] + b3) + b4).  Given gHn = dL/dH' (rows of LDH floats,
@@ -2033,23 +2056,11 @@ template <int F, int D>
 int node_bwd_t(const float *H, const float *e, const float *Hn, const gnn_graph_t *g, const gnn_params_t *p,
                const float *gHn, float *gH, float *ge, const gnn_grads_t *gr, char *ws, hipStream_t s)
 {
-    constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH;
-    const int64_t N = g->n_hits, E = g->n_segments;
-    BwdWs w = carve_bwd(ws, N, E, LDH, C, D);
-    using GL = GradLayout<F, D>;
-    float *const rp = w.rep;
-    constexpr int RS = GL::stride;
-    hipError_t err = hipMemsetAsync(rp, 0, (size_t)w.rows * RS * sizeof(float), s);
-    if (err != hipSuccess) return fail(-(int)err, "memset of the partial-gradient table failed");
-    if (N > 0) {
-        GNN_LAUNCH("k_node_bwd", (k_node_bwd<F, D>), grid_for(N), kBlock, s, H, Hn, LDH, e, g->in_ptr, g->in_eid,
-                   g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, p->W3, p->b3, p->W4, gHn, gH, w.gmio,
-                   rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
-        GNN_LAUNCH("k_agg_bwd_n", (k_agg_bwd_n<F, D>), grid_for(N), kBlock, s, e, w.gmio, g->in_ptr, g->in_eid,
-                   g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, gH, LDH, N);
-    }
-    if (E > 0) GNN_LAUNCH("k_seg_grad", (k_seg_grad<F, D>), grid_for(E), kBlock, s, g->src, g->dst, H, w.gmio, ge, E);
-    return grad_fold<F, D>(rp, w.rows, w.tmp, gr, s);
+    const BwdRun<F, D> c(g, p, ws, s);
+    if (int rc = c.clear(c.rp, c.w.rep_bytes)) return rc;
+    if (int rc = c.node_pass(H, Hn, e, gHn, gH)) return rc;
+    if (c.E > 0) GNN_LAUNCH("k_seg_grad", (k_seg_grad<F, D>), grid_for(c.E), kBlock, s, g->src, g->dst, H, c.w.gmio, ge, c.E);
+    return grad_fold<F, D>(c.rp, c.w.rows, c.w.tmp, gr, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2433,6 +2444,10 @@ int backward_events_t(const gnn_graph_t *g, const gnn_params_t *p, const int32_t
                       const gnn_grads_t *gr, char *ws, hipStream_t s)
 {
     using GL = GradLayout<F, D>;
+    const size_t lds = EvBwd<F, D>::lds_bytes(cap_h, cap_s);
+    if (lds > kEventBwdLdsMax)
+        return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit the one-launch "
+                    "backward at input_dim=%d hidden_dim=%d", cap_h, cap_s, F, D);
     // one row of partial sums per graph (= workgroup), folded in graph order
     const int64_t rows = n_graphs > 0 ? n_graphs : 1;
     float *rp = reinterpret_cast<float *>(ws);
@@ -2444,8 +2459,6 @@ int backward_events_t(const gnn_graph_t *g, const gnn_params_t *p, const int32_t
         if (attr_done.need())
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_event_bwd<F, D>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kEventBwdLdsMax);
-        using B = EvBwd<F, D>;
-        const size_t lds = B::lds_bytes(cap_h, cap_s);
         GNN_LAUNCH_SH("k_event_bwd", (k_event_bwd<F, D>), (unsigned)n_graphs, kBlock, lds, s, *g, *p, hit_ptr,
                       seg_ptr, T, e_all, H_all, grad_out, rp, cap_h, cap_s);
     }
@@ -2502,6 +2515,20 @@ __global__ __launch_bounds__(64) void k_bce_final(const float *__restrict__ part
     X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
     X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
 
+// What the public entry points share: the workspace check, the 256-byte alignment and the shape dispatch -
+// fn(Shape<F, D>, base) for the caller's shape, over the one-launch backward's shapes with EVENTS.
+template <bool EVENTS, typename Fn>
+int with_bwd_shape(const gnn_params_t *p, void *ws, size_t ws_bytes, size_t need, Fn fn)
+{
+    if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
+    char *base = align_ws(ws);
+#define X_(F_, D_) if (p->F == F_ && p->D == D_) return fn(Shape<F_, D_>{}, base);
+    if constexpr (EVENTS) { BWD_EVENT_SHAPES(X_) } else { BWD_FOR_EACH_SHAPE(X_) }
+#undef X_
+    return fail(GNN_ERR_UNSUPPORTED, "no %sbackward kernel for input_dim=%d hidden_dim=%d", EVENTS ? "one-launch " : "",
+                p->F, p->D);
+}
+
 }  // namespace
 
 namespace gnn {
@@ -2526,10 +2553,8 @@ int backward_events_supported(int F, int D, int64_t max_hits, int64_t max_segmen
 
 size_t backward_events_workspace_bytes(int64_t n_graphs, int F, int D)
 {
-    const int C = F + D;
-    const int tot = D * F + D + D * 2 * C + D + D + 1 + D * 3 * C + D + D * D + D;
     const int64_t rows = n_graphs > 0 ? n_graphs : 1;
-    return (size_t)(rows + fold_chunks(rows)) * ((tot + 63) & ~63) * sizeof(float) + 256;
+    return (size_t)(rows + fold_chunks(rows)) * replica_stride(F, D) * sizeof(float) + 256;
 }
 
 int backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
@@ -2537,63 +2562,37 @@ int backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *
                     const float *e_all, const float *H_all, const float *grad_out,
                     const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (ws_bytes < backward_events_workspace_bytes(n_graphs, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "event backward workspace too small: need %zu bytes",
-                    backward_events_workspace_bytes(n_graphs, p->F, p->D));
-    if (!backward_events_supported(p->F, p->D, cap_h, cap_s))
-        return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit the one-launch "
-                    "backward at input_dim=%d hidden_dim=%d", cap_h, cap_s, p->F, p->D);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return backward_events_t<F_, D_>(g, p, hit_ptr, seg_ptr, n_graphs, cap_h, cap_s, T, e_all, H_all, grad_out, gr, base, s);
-    BWD_EVENT_SHAPES(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no one-launch backward for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const size_t need = backward_events_workspace_bytes(n_graphs, p->F, p->D);
+    return with_bwd_shape<true>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
+        return backward_events_t<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, cap_h, cap_s, T, e_all, H_all, grad_out, gr,
+                                             base, s); });
 }
 
-size_t backward_workspace_bytes(int64_t N, int64_t E, int F, int D)
-{
-    const int C = F + D;
-    return carve_bwd(nullptr, N, E, (C + 3) & ~3, C, D).bytes + 256;
-}
+size_t backward_workspace_bytes(int64_t N, int64_t E, int F, int D) { return carve_bwd(nullptr, N, E, F, D).bytes; }
 
 int backward(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
              const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
              void *ws, size_t ws_bytes, hipStream_t s, const HeadBwd *head)
 {
-    if (ws_bytes < backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "backward workspace too small: need %zu bytes",
-                    backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return backward_t<F_, D_>(g, p, T, e_all, H_all, Q_all, grad_out, gr, base, s, head);
-    BWD_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no backward kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const size_t need = backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D);
+    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
+        return backward_t<sh.F, sh.D>(g, p, T, e_all, H_all, Q_all, grad_out, gr, base, s, head); });
 }
 
 int edge_bwd(const float *H, const gnn_graph_t *g, const gnn_params_t *p, const float *e, const float *ge, float *gH,
              const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (ws_bytes < backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "backward workspace too small: need %zu bytes",
-                    backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return edge_bwd_t<F_, D_>(H, g, p, e, ge, gH, gr, base, s);
-    BWD_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no backward kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const size_t need = backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D);
+    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
+        return edge_bwd_t<sh.F, sh.D>(H, g, p, e, ge, gH, gr, base, s); });
 }
 
 int node_bwd(const float *H, const float *e, const float *Hn, const gnn_graph_t *g, const gnn_params_t *p,
              const float *gHn, float *gH, float *ge, const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (ws_bytes < backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "backward workspace too small: need %zu bytes",
-                    backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return node_bwd_t<F_, D_>(H, e, Hn, g, p, gHn, gH, ge, gr, base, s);
-    BWD_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no backward kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const size_t need = backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D);
+    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
+        return node_bwd_t<sh.F, sh.D>(H, e, Hn, g, p, gHn, gH, ge, gr, base, s); });
 }
 
 }  // namespace gnn

@@ -438,3 +438,36 @@ def test_plan_workspace_bytes_are_pinned():
     }
     for (F, D), want in recorded.items():
         assert [_lib.plan_workspace_bytes(n, 0, F, D) for n in (0, 1, 255, 256, 100000)] == want, (F, D)
+
+
+def test_backward_workspace_bytes_are_pinned():
+    """gnn_backward_workspace_bytes per backward shape at (hits, segments) = (0, 0), (1, 0), (909, 6011) and
+    (40000, 300000), and gnn_backward_events_workspace_bytes at 0, 1 and 1024 graphs, as recorded from the build before
+    the gradient replica's size came from one function and the workspace was carved with common.h's Carver."""
+    from gnn_fpga_amd import _lib
+    recorded = {
+        (2, 4): ([7168, 8960, 335360, 14811392], [1792, 1792, 811264]),
+        (2, 8): ([20992, 22784, 606208, 26673408], [4864, 4864, 2433280]),
+        (2, 16): ([67072, 68864, 1199872, 52560128], [15104, 15104, 7840000]),
+        (2, 32): ([242176, 245248, 2747904, 119825664], [54016, 54016, 28385536]),
+        (3, 4): ([7168, 8960, 335360, 14811392], [1792, 1792, 811264]),
+        (3, 8): ([20992, 22784, 606208, 26673408], [4864, 4864, 2433280]),
+        (3, 16): ([69376, 71168, 1206272, 52830464], [15616, 15616, 8110336]),
+        (3, 32): ([249088, 252160, 2767104, 120636672], [55552, 55552, 29196544]),
+        (3, 64): ([940288, 945664, 6664448, 288777472], [209152, 209152, 110297344]),
+        (4, 8): ([23296, 25088, 612608, 26943744], [5376, 5376, 2703616]),
+        (4, 16): ([73984, 75776, 1219072, 53371136], [16640, 16640, 8651008]),
+        (4, 32): ([256000, 259072, 2786304, 121447680], [57088, 57088, 30007552]),
+        (4, 64): ([954112, 959488, 6702848, 290399488], [212224, 212224, 111919360]),
+        (11, 4): ([14080, 15872, 471040, 20742400], [3328, 3328, 1622272]),
+        (11, 8): ([34816, 36608, 761344, 33415424], [7936, 7936, 4055296]),
+        (11, 16): ([97024, 98816, 1399040, 61194496], [21760, 21760, 11354368]),
+    }
+    with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "backward.hip")) as f:
+        listed = re.search(r"#define BWD_FOR_EACH_SHAPE\(X_\)((?:.*\\\n)*.*)\n", f.read()).group(1)
+    assert sorted(recorded) == sorted((int(a), int(b)) for a, b in re.findall(r"X_\((\d+), (\d+)\)", listed))
+    lib = _lib.load()
+    for (F, D), (want, want_events) in recorded.items():
+        got = [lib.gnn_backward_workspace_bytes(n, e, F, D) for n, e in ((0, 0), (1, 0), (909, 6011), (40000, 300000))]
+        assert got == want, (F, D)
+        assert [lib.gnn_backward_events_workspace_bytes(g, F, D) for g in (0, 1, 1024)] == want_events, (F, D)
