@@ -64,6 +64,16 @@ def training_step(X, src, dst, params, n_iters, targets, l1=0.0):
     return float(loss.item()), grads, y.detach().numpy()
 
 
+def upstream_step(X, src, dst, params, n_iters, grad_y, dtype=torch.float64):
+    """{key: gradient} of sum(grad_y * y) over the twelve tensors, as float64 arrays: the backward under an arbitrary
+    upstream gradient of the hit scores.  `dtype`: what the forward and autograd run in (float32: the fp32 oracle)."""
+    w = [torch.tensor(np.asarray(params[k]), dtype=dtype, requires_grad=True) for k in KEYS]
+    y, _ = _forward(torch.tensor(np.asarray(X), dtype=dtype), torch.as_tensor(np.asarray(src, np.int64)),
+                    torch.as_tensor(np.asarray(dst, np.int64)), w, n_iters)
+    (y * torch.tensor(np.asarray(grad_y), dtype=dtype).reshape(-1)).sum().backward()
+    return {k: (p.grad.double().numpy() if p.grad is not None else np.zeros(p.shape)) for k, p in zip(KEYS, w)}
+
+
 def fixture(path):
     """A tests/golden/node_classifier/*.npz as a dict (params / grads as {key: array})."""
     z = np.load(path)

@@ -4,56 +4,12 @@ the names `_lib.profile` reports must equal those recorded in tests/data/backwar
 the commit before the route decision was gathered into choose_bwd_route (csrc/backward.hip) - and must be the
 sequence `_kernels_of` derives from the shape, the iteration count, the kept hidden layers, the head and the switch;
 two runs of a case give the same bits.  The switches are flipped inside this one process: read_bwd_switches reads
-them once per library call."""
-import importlib.util
-import json
-import os
-
+them once per library call.  `_kernels_of` lives in tests/route_cases.py; what the launched kernels compute is checked
+case by case against float64 in tests/test_gpu_route_values.py."""
 import pytest
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_spec = importlib.util.spec_from_file_location("record_backward_routes",
-                                               os.path.join(REPO, "tools", "record_backward_routes.py"))
-recorder = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(recorder)
-
-with open(os.path.join(REPO, "tests", "data", "backward_routes.json")) as _f:
-    RECORDED = json.load(_f)
-
-EDGE_PASS = ["kb_pq", "k_edge_bwd", "k_pq_bwd"]
-WIDE = ["k_hit_bwdW", "k_seg_bwdW", "k_seg_finW"]
-FOLD = ["k_grad_fold", "k_grad_fold"]
-
-
-def _kernels_of(case):
-    """The launches of a case with hits and segments, in order, under the names the profiler gives them."""
-    D, T, q, env, kind = case["D"], case["T"], case["q"] and case["T"] > 0, case["env"], case["kind"]
-    if kind == "edge":
-        return EDGE_PASS + FOLD
-    if kind == "node":
-        return ["k_node_bwd", "k_agg_bwd_n", "k_seg_grad"] + FOLD
-    if kind == "events":
-        return ["k_event_bwd"] + FOLD
-    wide = D >= 32 and q and env != "GNN_BWD_WIDE_PER_PASS"
-    if kind == "nodeclf":
-        names = ["k_head_bwd", "k_head_fold", "k_head_fold"]
-    elif wide:
-        names = WIDE + ["k_edge_bwd"]                # the wide final pass; k_edge_bwd for the padded segments only
-    else:
-        names = list(EDGE_PASS)
-    if D <= 16 and q:
-        fused = env != "GNN_BWD_NO_FIN_HIT"
-        for u in range(T, 0, -1):
-            names += ["k_hit_bwd4"] if u == T or not fused else []
-            names += ["k_seg_bwd4", "k_fin_hit" if u > 1 and fused else "k_seg_fin"]
-    elif D <= 16:
-        names += ["kb_prs", "k_hit_bwd", "k_seg_bwd"] * T
-    elif wide:
-        names += WIDE * T
-    else:
-        names += (["k_node_bwd", "k_agg_bwd_n"] + EDGE_PASS) * T
-    return names + ["k_input_bwd"] + FOLD
+from route_cases import RECORDED_BWD as RECORDED, bwd as recorder, kernels_of as _kernels_of
 
 
 def test_the_cases_are_the_recorded_ones():

@@ -11,7 +11,9 @@ the commit BEFORE a change to the host side of the backward; tests/test_gpu_back
 (`run_case`) on the current build.  A library that reads GNN_BWD_NO_FIN_HIT once per process (every commit before
 read_bwd_switches) cannot have that switch flipped between cases: there, record the whole list first and then the
 GNN_BWD_NO_FIN_HIT case again in a process of its own with `--case`, which sets the variable before the first
-backward.  The hashes are for comparing two builds on one machine and are not kept: kernel work may change them."""
+backward.  The hashes are for comparing two builds on one machine and are not kept: kernel work may change them.
+What the cases compute is checked by tests/test_gpu_route_values.py, which takes a case's inputs from `build_inputs`
+and runs it through `run_inputs` under an upstream gradient of its own, against float64."""
 import argparse
 import contextlib
 import hashlib
@@ -69,8 +71,8 @@ def switch(name):
                 os.environ[k] = v
 
 
-def _batch(case):
-    """The case's batch on the device, every 13th segment padded (src = dst = -1)."""
+def batch_host(case):
+    """The case's batch on the host, every 13th segment padded (src = dst = -1)."""
     from gnn_fpga_amd import HitGraphBatch, synth
     F = case["F"]
     if case["kind"] == "events":
@@ -83,7 +85,76 @@ def _batch(case):
     src, dst = b.src.numpy().copy(), b.dst.numpy().copy()
     src[7::13] = -1
     dst[7::13] = -1
-    return HitGraphBatch(b.X.numpy(), src, dst, hit_ptr=b.hit_ptr, seg_ptr=b.seg_ptr).cuda()
+    return HitGraphBatch(b.X.numpy(), src, dst, hit_ptr=b.hit_ptr, seg_ptr=b.seg_ptr)
+
+
+def host_weights(case):
+    """The case's ten weight tensors on the host, state_dict order: SegmentClassifier's default init from the case's
+    seed (which also seeds the device generator the head and the default upstream gradients are drawn from)."""
+    import torch
+    from gnn_fpga_amd.model import SegmentClassifier
+    torch.manual_seed(5 * case["D"] + case["T"])
+    model = SegmentClassifier(input_dim=case["F"], hidden_dim=case["D"], n_iters=case["T"])
+    return [t.detach().contiguous() for t in model.state_dict().values()]
+
+
+def build_inputs(case, head=None):
+    """The case's inputs on the device, as a namespace: batch `b`, weights `w`, the head (`Wo`, `bo`: nodeclf only;
+    `head` = (Wo, bo) replaces the seeded one), the event layout `lay` (events only), the kept forward tensors
+    `e_all`, `H_all`, `Q_all` (and `y`: nodeclf), and `grad`, the default upstream gradient: randn / count."""
+    import types
+
+    import torch
+    from gnn_fpga_amd import _lib
+    F, D, T, kind = case["F"], case["D"], case["T"], case["kind"]
+    w = [t.cuda() for t in host_weights(case)]
+    b = batch_host(case).cuda()
+    N, E = b.n_hits, b.n_segments
+    inp = types.SimpleNamespace(case=case, b=b, w=w, Wo=None, bo=None, lay=None, y=None, Q_all=None)
+    if kind == "nodeclf":
+        inp.Wo, inp.bo = 0.3 * torch.randn(1, F + D, device="cuda"), torch.randn(1, device="cuda")
+        if head is not None:
+            inp.Wo, inp.bo = (t.to("cuda", torch.float32) for t in head)
+        inp.e_all, inp.H_all, inp.Q_all, inp.y = _lib.nodeclf_forward_train(b, w, inp.Wo, inp.bo, F, D, T, keep_q=case["q"])
+        inp.grad = torch.randn(N, device="cuda") / N
+    elif kind == "events":
+        inp.lay = b.event_layout()
+        assert inp.lay is not None and _lib.events_backward_supported(F, D, inp.lay.max_hits, inp.lay.max_segments)
+        inp.e_all, inp.H_all, _ = _lib.segclf_forward_train(b, w, F, D, T, layout=inp.lay)
+        inp.grad = torch.randn(E, device="cuda") / E
+    else:
+        inp.e_all, inp.H_all, Q_all = _lib.segclf_forward_train(b, w, F, D, T)
+        inp.Q_all = Q_all if case["q"] else None
+        inp.grad = torch.randn(E, device="cuda") / E
+        if kind == "node":
+            inp.grad = torch.randn_like(inp.H_all[1]) / N
+    return inp
+
+
+def run_inputs(inp, grad=None, into=None):
+    """One backward of the case on `inp` (build_inputs), with the environment as the caller left it.  `grad`: the
+    upstream gradient instead of the default one - of e_T [E] (segclf, big, events), of e [E] (edge), of H' (node:
+    rows of H_all's stride, the first D columns used), of y [N] (nodeclf).  `into` (segclf, big, events): ten
+    tensors the gradients are added into.  Returns the gradient tensors: the ten weights' (segclf, big, events; and
+    gWo, gbo after them: nodeclf), gH and gW1, gb1, gW2, gb2 (edge), gH, ge and gW3, gb3, gW4, gb4 (node)."""
+    from gnn_fpga_amd import _lib
+    case, b, w = inp.case, inp.b, inp.w
+    F, D, T, kind = case["F"], case["D"], case["T"], case["kind"]
+    go = inp.grad if grad is None else grad
+    e_all, H_all = inp.e_all, inp.H_all
+    assert into is None or kind in ("segclf", "big", "events")
+    if kind == "nodeclf":
+        grads, gWo, gbo = _lib.nodeclf_backward(b, w, inp.Wo, inp.bo, F, D, T, e_all, H_all, inp.y, go, Q_all=inp.Q_all)
+        return list(grads) + [gWo, gbo]
+    if kind == "events":
+        return list(_lib.segclf_backward_events(b, inp.lay, w, F, D, T, e_all, H_all, go, into=into))
+    if kind == "edge":
+        gH, grads = _lib.edge_bwd(H_all[0], b, w, F, D, e_all[0], go)
+        return [gH] + list(grads)
+    if kind == "node":
+        gH, ge, grads = _lib.node_bwd(H_all[0], e_all[0], H_all[1], b, w, F, D, go)
+        return [gH, ge] + list(grads)
+    return list(_lib.segclf_backward(b, w, F, D, T, e_all, H_all, go, into=into, Q_all=inp.Q_all))
 
 
 def run_case(case):
@@ -91,45 +162,10 @@ def run_case(case):
     (kernel names of the first run, gradient tensors of the first run, of the second)."""
     import torch
     from gnn_fpga_amd import _lib
-    from gnn_fpga_amd.model import SegmentClassifier
-    F, D, T, kind = case["F"], case["D"], case["T"], case["kind"]
-    torch.manual_seed(5 * D + T)
-    b = _batch(case)
-    model = SegmentClassifier(input_dim=F, hidden_dim=D, n_iters=T).cuda()
-    w = [t.detach().contiguous() for t in model.state_dict().values()]
-    N, E = b.n_hits, b.n_segments
-    if kind == "nodeclf":
-        Wo, bo = 0.3 * torch.randn(1, F + D, device="cuda"), torch.randn(1, device="cuda")
-        e_all, H_all, Q_all, y = _lib.nodeclf_forward_train(b, w, Wo, bo, F, D, T, keep_q=case["q"])
-        gy = torch.randn(N, device="cuda") / N
-
-        def run():
-            grads, gWo, gbo = _lib.nodeclf_backward(b, w, Wo, bo, F, D, T, e_all, H_all, y, gy, Q_all=Q_all)
-            return list(grads) + [gWo, gbo]
-    elif kind == "events":
-        lay = b.event_layout()
-        assert lay is not None and _lib.events_backward_supported(F, D, lay.max_hits, lay.max_segments)
-        e_all, H_all, _ = _lib.segclf_forward_train(b, w, F, D, T, layout=lay)
-        go = torch.randn(E, device="cuda") / E
-        run = lambda: list(_lib.segclf_backward_events(b, lay, w, F, D, T, e_all, H_all, go))
-    else:
-        e_all, H_all, Q_all = _lib.segclf_forward_train(b, w, F, D, T)
-        go = torch.randn(E, device="cuda") / E
-        if kind == "edge":
-            def run():
-                gH, grads = _lib.edge_bwd(H_all[0], b, w, F, D, e_all[0], go)
-                return [gH] + list(grads)
-        elif kind == "node":
-            gHn = torch.randn_like(H_all[1]) / N
-
-            def run():
-                gH, ge, grads = _lib.node_bwd(H_all[0], e_all[0], H_all[1], b, w, F, D, gHn)
-                return [gH, ge] + list(grads)
-        else:
-            run = lambda: list(_lib.segclf_backward(b, w, F, D, T, e_all, H_all, go, Q_all=Q_all if case["q"] else None))
+    inp = build_inputs(case)
     with _lib.profile(64) as prof:
-        first = [t.clone() for t in run()]
-    second = [t.clone() for t in run()]
+        first = [t.clone() for t in run_inputs(inp)]
+    second = [t.clone() for t in run_inputs(inp)]
     torch.cuda.synchronize()
     return [k for k, _ in prof.records], first, second
 

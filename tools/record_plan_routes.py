@@ -6,7 +6,9 @@ branch of the route decision (choose_route in csrc/sell_pipeline.hip).
 
 The JSON holds, per case, the ordered kernel names `_lib.profile` reports.  It is recorded at the commit BEFORE a
 change to the host side of the pipeline; tests/test_gpu_plan_route.py replays the cases (`run_case`) on the current
-build.  The hashes are for comparing two builds on one machine and are not kept: kernel work may change them."""
+build.  The hashes are for comparing two builds on one machine and are not kept: kernel work may change them.
+What the cases compute is checked by tests/test_gpu_route_values.py, which takes a case's inputs from `build_inputs`,
+runs it through `run_inputs` and compares the scores with float64."""
 import argparse
 import contextlib
 import hashlib
@@ -63,9 +65,11 @@ def _switch(name):
                 os.environ[k] = v
 
 
-def run_case(case):
-    """Runs the case's forward twice.  Returns (kernel names of the first run, scores of the first run, scores of
-    the second, plan, flags)."""
+def build_inputs(case):
+    """The case's inputs on the device, as a namespace: the `graphs` it is made of (host), `batch`, `weights` (the
+    model's ten effective tensors), `plan`, `flags`, and `twin` (the level-ordered batch: the training case only)."""
+    import types
+
     import torch
     from gnn_fpga_amd import HitGraphBatch, _lib, synth
     from gnn_fpga_amd.model import SegmentClassifier
@@ -80,25 +84,45 @@ def run_case(case):
     weights = [t.detach().contiguous() for t in model.effective_weights()]
     batch = HitGraphBatch.from_graphs(graphs).cuda()
     plan = batch.build_plan(D, case["limits"])
-    flags = 0
+    flags, twin = 0, None
     if case["train"]:
         twin = batch.level_ordered(D)
         assert twin._fused is plan
-        run = lambda: _lib.segclf_forward_train_fused(twin, weights, F, D, T)[3]
     else:
         if case["xp"]:
             assert _lib.exp_product_bound(weights, F, D, plan.x_absmax) <= 60.0
             flags |= _lib.GNN_FLAG_EXP_PRODUCT
         if case["bf16"]:
             flags |= _lib.GNN_FLAG_BF16_MLP
-        run = lambda: _lib.segclf_forward_plan(plan, weights, F, D, T, flags=flags)
+    return types.SimpleNamespace(case=case, graphs=graphs, batch=batch, weights=weights, plan=plan, flags=flags, twin=twin)
+
+
+def run_inputs(inp):
+    """The case's forward twice on `inp` (build_inputs), under the case's switch.  Returns (kernel names of the first
+    run, scores of the first run, scores of the second), the scores in the caller's segment order."""
+    import torch
+    from gnn_fpga_amd import _lib
+    case = inp.case
+    F, D, T = case["F"], case["D"], case["T"]
+    if case["train"]:
+        run = lambda: _lib.segclf_forward_train_fused(inp.twin, inp.weights, F, D, T)[3]
+    else:
+        run = lambda: _lib.segclf_forward_plan(inp.plan, inp.weights, F, D, T, flags=inp.flags)
     with _switch(case["env"]):
         run()                                   # (a batch's one-time work - plan struct, counts - is not a launch)
         with _lib.profile(64) as prof:
             first = run().clone()
         second = run().clone()
     torch.cuda.synchronize()
-    return [k for k, _ in prof.records], first, second, plan, flags
+    return [k for k, _ in prof.records], first, second
+
+
+def run_case(case):
+    """Runs the case's forward twice.  Returns (kernel names of the first run, scores of the first run, scores of
+    the second, plan, flags)."""
+    inp = build_inputs(case)
+    names, first, second = run_inputs(inp)
+    return names, first, second, inp.plan, inp.flags
 
 
 def main():
