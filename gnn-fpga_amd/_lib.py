@@ -457,7 +457,8 @@ def edge_fwd(H, src, dst, W1, b1, W2, b2, F, D):
 def node_fwd(H, e, batch, W3, b3, W4, b4, F, D):
     """H [n_hits, ldh], e [n_segments] -> Hnext [n_hits, ldh] = [H' | X | 0]."""
     n, ldh = H.shape
-    Hn = torch.zeros_like(H)
+    # (the kernel writes the h_stride(F, D) floats of every row, 0-pad included; a wider row's tail is the caller's)
+    Hn = torch.empty_like(H) if ldh == h_stride(F, D) else torch.zeros_like(H)
     g = graph_struct(batch)
     with _on(H, g) as st:
         _check(load().gnn_node_fwd(_dev(H, torch.float32, "H"), ldh, _dev(e, torch.float32, "e"),

@@ -8,6 +8,17 @@
  * Conventions
  *   - every pointer is a DEVICE pointer into caller-owned memory (e.g. tensor.data_ptr());
  *     the library never allocates, frees or retains caller buffers;
+ *   - workspaces and output buffers need NOT be initialised by the caller: a call clears what it
+ *     counts in or adds up, and writes EVERY element of every output it documents - padded
+ *     segments' scores, rows of empty graphs or events, list tails and the 0-pad of a hit-feature
+ *     row included - unless an exception is listed at the entry point (there is one: the columns
+ *     of gnn_gcn_forward's H_all past a layer's own width are unspecified);
+ *   - a call writes nothing outside the workspace bytes its *_workspace_bytes function asked for
+ *     and the documented extent of its outputs;
+ *   - buffers documented as "ADDED into", "ORed into" or "zero them first" (gnn_grads_t, grad_H of
+ *     gnn_edge_bwd, the counters of gnn_segment_metrics_update, the lists of
+ *     gnn_gcn_compress_fill) are inputs as well: the caller initialises those;
+ *     (tests/test_gpu_uninitialised.py runs every entry point on poisoned, guarded buffers)
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream);
  *     all work is asynchronous on it, no implicit synchronisation;
  *   - return value 0 = success; negative = -(hipError_t) or one of GNN_ERR_*;
@@ -139,7 +150,8 @@ int gnn_edge_fwd(const float *H, int32_t ldh, const int32_t *src, const int32_t 
  *   Hnext[n] = [tanh(W4 tanh(W3 [mi|mo|H[n]] + b3) + b4) | X[n]]   (X[n] = H[n][D:D+F]).
  * Replaces gnn/model.py:113-125 (four bmm, two broadcast multiplies, cat, 2x MaskedLinear+Tanh)
  * and :154.  Sums run in ascending segment id (fixed order: bit-reproducible).
- * Only X, in_*, out_* and n_hits of `g` are read.  Hnext must not alias H. */
+ * Only X, in_*, out_* and n_hits of `g` are read.  Hnext must not alias H.  Of every row of Hnext the first
+ * gnn_h_stride(F, D) floats are written (the 0-pad is H's); floats past them, where ldh is larger, are not touched. */
 int gnn_node_fwd(const float *H, int32_t ldh, const float *e, const gnn_graph_t *g,
                  const float *W3, const float *b3, const float *W4, const float *b4,
                  float *Hnext, int32_t F, int32_t D, void *stream);
@@ -745,7 +757,9 @@ int gnn_track_match(const int32_t *track_of_hit, const int64_t *particle_id, int
  *     non-finite entry) from the dense fp32 a [B][N][N]; every entry with a != 0 counts.  The caller reads info back
  *     (the ONE read-back of a compression), sizes the lists (zero-filled) and calls gnn_gcn_compress_fill.
  *   gnn_gcn_forward: ONE launch, one workgroup per graph: out [B][N] logits from x [B][N][F].  H_all (NULL for
- *     inference) [B][n_dims][N][max_width] receives the post-ReLU h of every layer, which the backward reads.
+ *     inference) [B][n_dims][N][max_width] receives the post-ReLU h of every layer, which the backward reads:
+ *     columns [0, dims[l]) of layer l are written, the columns past a layer's own width are UNSPECIFIED (never
+ *     written, never read by gnn_gcn_backward).
  *   gnn_gcn_backward: ONE launch, one workgroup per graph (per-graph partial sums into the workspace, A^T gz pulled
  *     over the column lists, no float atomics) and ONE fixed-order reduction launch: grads [n_params] is WRITTEN, the
  *     same bits in every run.  grad_out [B][N] is the gradient of the logits.  No gradient for x or a.

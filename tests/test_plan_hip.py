@@ -25,10 +25,8 @@ CASES = ["layered", "ragged", "padded", "global", "wide", "one_graph_big_levels"
          "shuffled", "big_shuffled", "c3", "many_c3", "leading_pads", "tiny_tiles", "many_muon", "mu200_size"]
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_hip_builder_builds_the_same_plan(hip, case, monkeypatch):
-    from gnn_fpga_amd.plan import SellPlan
-    from gnn_fpga_amd.plan_hip import HipSellPlan
+def case_batch(case):
+    """(the case's batch on the host, F, D, what it overrides of plan_limits); shared with test_gpu_uninitialised.py."""
     F, D, lim_over = 3, 8, {}
     pads = None
     if case == "layered":
@@ -85,6 +83,14 @@ def test_hip_builder_builds_the_same_plan(hip, case, monkeypatch):
         src[pads] = -1
         dst[pads] = -1
         b = HitGraphBatch(b.X.numpy(), src, dst, hit_ptr=b.hit_ptr, seg_ptr=b.seg_ptr)
+    return b, F, D, lim_over
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_hip_builder_builds_the_same_plan(hip, case, monkeypatch):
+    from gnn_fpga_amd.plan import SellPlan
+    from gnn_fpga_amd.plan_hip import HipSellPlan
+    b, F, D, lim_over = case_batch(case)
     lim = hip.plan_limits(F, D)
     lim.update(lim_over)
     host = SellPlan(b, lim)
