@@ -35,12 +35,6 @@
 namespace {
 using namespace gnn;
 
-template <int F_, int D_>
-struct Shape {
-    static constexpr int F = F_, D = D_, C = F + D;
-    static constexpr int LDH = (C + 3) & ~3;
-};
-
 // row of LDH floats (16-byte aligned: LDH % 4 == 0) as float4 loads
 template <int N4>
 __device__ __forceinline__ void load_row4(const float *__restrict__ row, float *v)
@@ -2511,19 +2505,15 @@ __global__ __launch_bounds__(64) void k_bce_final(const float *__restrict__ part
     if (threadIdx.x == 0) loss[0] = s * scale;
 }
 
-#define BWD_FOR_EACH_SHAPE(X_) \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
-    X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
-
 // What the public entry points share: the workspace check, the 256-byte alignment and the shape dispatch -
-// fn(Shape<F, D>, base) for the caller's shape, over the one-launch backward's shapes with EVENTS.
+// fn(Shape<F, D>, base) for the caller's shape (GNN_FOR_EACH_SHAPE, common.h), over the one-launch backward's shapes with EVENTS.
 template <bool EVENTS, typename Fn>
 int with_bwd_shape(const gnn_params_t *p, void *ws, size_t ws_bytes, size_t need, Fn fn)
 {
     if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
     char *base = align_ws(ws);
 #define X_(F_, D_) if (p->F == F_ && p->D == D_) return fn(Shape<F_, D_>{}, base);
-    if constexpr (EVENTS) { BWD_EVENT_SHAPES(X_) } else { BWD_FOR_EACH_SHAPE(X_) }
+    if constexpr (EVENTS) { BWD_EVENT_SHAPES(X_) } else { GNN_FOR_EACH_SHAPE(X_) }
 #undef X_
     return fail(GNN_ERR_UNSUPPORTED, "no %sbackward kernel for input_dim=%d hidden_dim=%d", EVENTS ? "one-launch " : "",
                 p->F, p->D);

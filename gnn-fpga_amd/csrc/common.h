@@ -47,6 +47,21 @@ struct ProfChain {
 
 constexpr int kBlock = 256;   // 4 waves of 64
 
+// The (input_dim, hidden_dim) pairs the per-pass forward (gnn_kernels.hip) and the backward (backward.hip) have kernels
+// for: one list, so that a shape cannot be trained without a forward or the other way round.
+// (input_dim 4: the hit classifier of gnn/MPNN_HitClassifier.ipynb - r, phi, z and the seed label - and the first
+// shapes whose hit rows [H' | X] have no zero pad column, C == LDH)
+#define GNN_FOR_EACH_SHAPE(X_) \
+    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
+    X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
+
+// a shape as a type: hit rows [H'(D) | X(F) | 0-pad] of C floats, stored LDH = gnn_h_stride(F, D) apart
+template <int F_, int D_>
+struct Shape {
+    static constexpr int F = F_, D = D_, C = F + D;
+    static constexpr int LDH = (C + 3) & ~3;
+};
+
 // csr_build.hip's device-wide scan, shared: exclusive scans of n_arrays (1 or 2) int32 count arrays stored `stride`
 // apart into ptr_a / ptr_b [n + 1] (entry n = the total); `sums` = scan_sums_words(n) int32 of scratch
 int64_t scan_sums_words(int64_t n);

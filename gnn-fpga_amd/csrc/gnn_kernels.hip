@@ -18,6 +18,14 @@
 // Weights are tiny (569 floats at F=3, D=8): every weight address is wave-uniform, so the
 // compiler keeps them on the scalar path (s_load / SGPR operands) - no LDS, no VGPR copies.
 // No MFMA here by design: at D <= 16 the work is HBM/gather-bound integer-indexed traffic.
+//
+// Host side (below the kernels): choose_fwd_route fixes the route of a call before its first launch, FwdRun has the
+// one launch site of every kernel, forward_impl is the loop over it.  The route, with `wide` open to D >= 32 while
+// GNN_NODE_ONE_LANE is unset (read_fwd_switches, once per call):
+//   input pass  k_input (H0 and P | Q);  wide at >= 2048 hits when P | Q is wanted: k_input (H0), k_pq_mlpW (P | Q)
+//   edge pass   k_edge
+//   node pass   k_node;  wide at >= 2048 hits, and with a NodeClassifier's head at every size: k_node_walkW, k_node_mlpW
+//   gnn_input_fwd / gnn_edge_fwd (k_pq, k_edge) / gnn_node_fwd: one lane per item at every size
 #include "common.h"
 
 #include <type_traits>
@@ -100,12 +108,6 @@ ProfChain::~ProfChain()
 
 namespace {
 using namespace gnn;
-
-template <int F, int D>
-struct Shape {
-    static constexpr int C = F + D;
-    static constexpr int LDH = (C + 3) & ~3;
-};
 
 // P = W1[:, :C] h + b1, Q = W1[:, C:] h  -> PQ row [P(D) | Q(D)], stored as float4s.
 template <int F, int D>
@@ -1011,95 +1013,69 @@ __global__ __launch_bounds__(kBlock) void k_unpad(const float *__restrict__ H, i
 }
 
 // ---------------------------------------------------------------------------------------------
-// shape dispatch
+// host side of the per-pass forward
 // ---------------------------------------------------------------------------------------------
-// (input_dim 4: the hit classifier of gnn/MPNN_HitClassifier.ipynb - r, phi, z and the seed label - and the first
-// shapes whose hit rows [H' | X] have no zero pad column, C == LDH)
-#define GNN_FOR_EACH_SHAPE(X_) \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
-    X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
-
-// (Wo / bo / y: a NodeClassifier without message passing scores its hits from H0 here)
-template <int F, int D>
-int run_input(const float *X, const float *Win, const float *bin, const float *W1,
-              const float *b1, float *H, int ldh, float *PQ, int64_t n, hipStream_t s,
-              const float *Wo = nullptr, const float *bo = nullptr, float *y = nullptr)
+// fn(Shape<F, D>) for the caller's shape (GNN_FOR_EACH_SHAPE, common.h)
+template <typename Fn>
+int with_fwd_shape(int F, int D, Fn fn)
 {
-    if (n <= 0) return 0;
-    if constexpr (D >= 32) {
-        // wide hidden layers at detector size: the P / Q products on the matrix cores
-        if (PQ && n >= kNodeWideMinHits && ldh == Shape<F, D>::LDH && !getenv("GNN_NODE_ONE_LANE")) {
-            GNN_LAUNCH("k_input", (k_input<F, D>), grid_for(n), kBlock, s, X, Win, bin, W1, b1, H, ldh,
-                       (float *)nullptr, n, Wo, bo, y);
-            GNN_LAUNCH("k_pq_mlpW", (k_pq_mlpW<F, D>), grid_for(n), kBlock, s, H, ldh, W1, b1, PQ, n);
-            return 0;
-        }
-    }
-    GNN_LAUNCH("k_input", (k_input<F, D>), grid_for(n), kBlock, s, X, Win, bin, W1, b1, H, ldh,
-               PQ, n, Wo, bo, y);
-    return 0;
+#define X_(F_, D_) if (F == F_ && D == D_) return fn(Shape<F_, D_>{});
+    GNN_FOR_EACH_SHAPE(X_)
+#undef X_
+    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", F, D);
 }
 
-template <int F, int D>
-int run_pq(const float *H, int ldh, const float *W1, const float *b1, float *PQ, int64_t n,
-           hipStream_t s)
+bool params_complete(const gnn_params_t *p)
 {
-    if (n > 0) GNN_LAUNCH("k_pq", (k_pq<F, D>), grid_for(n), kBlock, s, H, ldh, W1, b1, PQ, n);
-    return 0;
+    return p && p->Win && p->bin && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3 && p->W4 && p->b4;
+}
+bool grads_complete(const gnn_grads_t *gr)
+{
+    return gr && gr->Win && gr->bin && gr->W1 && gr->b1 && gr->W2 && gr->b2 && gr->W3 && gr->b3 && gr->W4 && gr->b4;
 }
 
-template <int D>
-int run_edge(const int32_t *src, const int32_t *dst, const float *PQ, const float *b1,
-             const float *W2, const float *b2, float *e, int64_t n_seg, hipStream_t s)
-{
-    if (n_seg > 0)
-        GNN_LAUNCH("k_edge", (k_edge<D>), grid_for(n_seg), kBlock, s, src, dst, PQ, b1, W2, b2, e,
-                   n_seg);
-    return 0;
-}
+// The environment switch of the per-pass forward (A / B runs, tests): this is its one reader, called once per library
+// call and not cached, like read_bwd_switches - tests flip it inside one process.
+struct FwdSwitches { bool node_one_lane; };
+FwdSwitches read_fwd_switches() { return {getenv("GNN_NODE_ONE_LANE") != nullptr}; }
+
+// Which kernels a forward takes: fixed by choose_fwd_route before the first launch.  One lane per hit (k_input with
+// P / Q, k_node), or wide: the P / Q products on the matrix cores (k_input, k_pq_mlpW) and the 16-lane list walk with
+// the matrix-core MLP (k_node_walkW, k_node_mlpW).  The edge pass has one kernel.
+struct FwdRoute { bool wide_input, wide_node; };
+constexpr FwdRoute kOneLane = {false, false};       // the module entry points: one lane per item at every size
 
 template <int F, int D>
-int run_node(const float *H, int ldh, const float *e, const gnn_graph_t *g, const float *W3,
-             const float *b3, const float *W4, const float *b4, const float *W1, const float *b1,
-             float *Hn, int ldhn, float *PQ, hipStream_t s, float *Qkeep = nullptr, float *Mbuf = nullptr,
-             const float *Wo = nullptr, const float *bo = nullptr, float *y = nullptr,
-             int64_t wide_min_hits = kNodeWideMinHits)
+FwdRoute choose_fwd_route(int64_t n_hits, bool have_head, int n_iters, const FwdSwitches &sw)
 {
-    if (g->n_hits <= 0) return 0;
-    if constexpr (D >= 32) {
-        // wide hidden layers at detector size: 16-lane list walk + matrix-core MLP (Mbuf: [n_hits, 2 ldh] scratch)
-        if (Mbuf && g->n_hits >= wide_min_hits && ldh == Shape<F, D>::LDH && !getenv("GNN_NODE_ONE_LANE")) {
-            GNN_LAUNCH("k_node_walkW", (k_node_walkW<F, D>), grid_walk(g->n_hits), kWalkBlock, s, H, ldh, e, g->in_ptr,
-                       g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, Mbuf, g->n_hits);
-            GNN_LAUNCH("k_node_mlpW", (k_node_mlpW<F, D>), grid_for(g->n_hits), kBlock, s, H, ldh, Mbuf, W3, b3, W4, b4,
-                       W1, b1, Hn, ldhn, PQ, Qkeep, g->n_hits, Wo, bo, y);
-            return 0;
-        }
-    }
-    GNN_LAUNCH("k_node", (k_node<F, D>), grid_for(g->n_hits), kBlock, s, H, ldh, e, g->in_ptr,
-               g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr, W3, b3, W4, b4, W1, b1,
-               Hn, ldhn, PQ, Qkeep, g->n_hits, Wo, bo, y);
-    return 0;
+    // wide needs hidden layers of 32 or 64 units, and the switch off
+    const bool can_wide = D >= 32 && !sw.node_one_lane;
+    const bool detector_size = n_hits >= kNodeWideMinHits;
+    // the node pass is wide at detector size; a NodeClassifier's at every size: at the notebook's 32 x 50 hits the one-lane
+    // k_node<4, 64> spills (0.21 ms a pass against 0.075 ms for k_node_walkW + k_node_mlpW, profiles/nodeclf_kernel_trace.txt)
+    const bool wide_node = can_wide && (detector_size || have_head);
+    // the input pass is wide at detector size (a NodeClassifier's too: it keeps the threshold) when P / Q is wanted at
+    // all - a head without message passing scores the hits from H0 and has no edge pass
+    const bool wide_input = can_wide && detector_size && !(have_head && n_iters == 0);
+    return {wide_input, wide_node};
 }
 
-struct Workspace {
+struct FwdWs {
     float *Ha, *Hb, *PQ, *e, *M;
     size_t bytes;
 };
 
-Workspace carve(void *base, int64_t n_hits, int64_t n_seg, int ldh, int D)
+FwdWs carve_fwd(char *b, int64_t N, int64_t E, int F, int D)
 {
-    Workspace w;
-    size_t off = 0;
-    char *b = static_cast<char *>(base);
-    const size_t hbytes = align256((size_t)n_hits * ldh * sizeof(float));
-    w.Ha = reinterpret_cast<float *>(b + off); off += hbytes;
-    w.Hb = reinterpret_cast<float *>(b + off); off += hbytes;
-    w.PQ = reinterpret_cast<float *>(b + off); off += align256((size_t)n_hits * 2 * D * sizeof(float));
-    w.e = reinterpret_cast<float *>(b + off);  off += align256((size_t)n_seg * sizeof(float));
-    w.M = reinterpret_cast<float *>(b + off);             // wide shapes: [mi | mo] between k_node_walkW and k_node_mlpW
-    off += align256(D >= 32 ? (size_t)n_hits * 2 * ldh * sizeof(float) : 0);
-    w.bytes = off;
+    const size_t ldh = (F + D + 3) & ~3;
+    Carver c{b};
+    FwdWs w;
+    w.Ha = c.take<float>((size_t)N * ldh);
+    w.Hb = c.take<float>((size_t)N * ldh);
+    w.PQ = c.take<float>((size_t)N * 2 * D);
+    w.e = c.take<float>((size_t)E);
+    w.M = c.take<float>(D >= 32 ? (size_t)N * 2 * ldh : 0);      // wide shapes: [mi | mo] between k_node_walkW and k_node_mlpW
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -1109,58 +1085,127 @@ struct Head {
     float *y;
 };
 
-// head == NULL: SegmentClassifier (n_iters x (edge pass, node pass), final edge pass -> e_out).  head != NULL:
+#define FWD_LISTS g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr
+// One forward in flight: what its launchers share.  A launcher takes what differs between its calls - the H / e / P|Q /
+// Q rows of the pass and the head, if this pass scores the hits - and skips an empty batch.  `ws` null (the module
+// entry points, on the one-lane route): nothing is carved, every row is the caller's.
+template <int F, int D>
+struct FwdRun {
+    static constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH;
+    const gnn_graph_t *g;
+    const gnn_params_t *p;
+    hipStream_t s;
+    int64_t N, E;
+    FwdWs w;
+    FwdRoute route;
+    FwdRun(const gnn_graph_t *g_, const gnn_params_t *p_, char *ws, hipStream_t s_, FwdRoute route_)
+        : g(g_), p(p_), s(s_), N(g_->n_hits), E(g_->n_segments), w(carve_fwd(ws, N, E, F, D)), route(route_) {}
+    // input network: H = [tanh(Win X + bin) | X | 0], P | Q of it into PQ (null: none), the head's scores from H0
+    int input(float *H, int ldh, float *PQ, const Head *head) const
+    {
+        if (N <= 0) return 0;
+        GNN_LAUNCH("k_input", (k_input<F, D>), grid_for(N), kBlock, s, g->X, p->Win, p->bin, p->W1, p->b1, H, ldh,
+                   route.wide_input ? nullptr : PQ, N, head ? head->Wo : nullptr, head ? head->bo : nullptr,
+                   head ? head->y : nullptr);
+        if constexpr (D >= 32)
+            if (route.wide_input) GNN_LAUNCH("k_pq_mlpW", (k_pq_mlpW<F, D>), grid_for(N), kBlock, s, H, ldh, p->W1, p->b1, PQ, N);
+        return 0;
+    }
+    // P | Q of an H somebody else made (the EdgeNetwork entry point)
+    int pq(const float *H, int ldh, float *PQ) const
+    {
+        if (N > 0) GNN_LAUNCH("k_pq", (k_pq<F, D>), grid_for(N), kBlock, s, H, ldh, p->W1, p->b1, PQ, N);
+        return 0;
+    }
+    int edge(const float *PQ, float *e) const
+    {
+        if (E > 0) GNN_LAUNCH("k_edge", (k_edge<D>), grid_for(E), kBlock, s, g->src, g->dst, PQ, p->b1, p->W2, p->b2, e, E);
+        return 0;
+    }
+    // node pass (H, e -> Hn), P | Q of Hn into PQ and its hidden layer into Qkeep (null: none), the head's scores from Hn
+    int node(const float *H, int ldh, const float *e, float *Hn, float *PQ, float *Qkeep, const Head *head) const
+    {
+        if (N <= 0) return 0;
+        const float *Wo = head ? head->Wo : nullptr, *bo = head ? head->bo : nullptr;
+        float *y = head ? head->y : nullptr;
+        if constexpr (D >= 32)
+            if (route.wide_node) {
+                GNN_LAUNCH("k_node_walkW", (k_node_walkW<F, D>), grid_walk(N), kWalkBlock, s, H, ldh, e, FWD_LISTS, w.M, N);
+                GNN_LAUNCH("k_node_mlpW", (k_node_mlpW<F, D>), grid_for(N), kBlock, s, H, ldh, w.M, p->W3, p->b3, p->W4,
+                           p->b4, p->W1, p->b1, Hn, ldh, PQ, Qkeep, N, Wo, bo, y);
+                return 0;
+            }
+        GNN_LAUNCH("k_node", (k_node<F, D>), grid_for(N), kBlock, s, H, ldh, e, FWD_LISTS, p->W3, p->b3, p->W4, p->b4,
+                   p->W1, p->b1, Hn, ldh, PQ, Qkeep, N, Wo, bo, y);
+        return 0;
+    }
+    // H (padded rows) -> one unpadded trace row [N, C]
+    int unpad(const float *H, float *out) const
+    {
+        if (N > 0) GNN_LAUNCH("k_unpad", k_unpad, grid_for(N * C), kBlock, s, H, LDH, C, out, N * C);
+        return 0;
+    }
+};
+
+// where a forward's results go; null: not wanted
+struct FwdOut {
+    float *e_out;           // the final edge pass [E]
+    float *e_trace;         // every edge pass, row t of E floats (row n_iters = e_out's values)
+    float *H_trace;         // every H unpadded, row t of [N, C]
+    float *H_all;           // training forward: every iteration's H is kept here, no ping-pong
+    float *Q_all;           // training forward: the node passes' hidden layers, row t of [N, D]
+    const Head *head;       // NodeClassifier
+};
+
+// head null: SegmentClassifier (n_iters x (edge pass, node pass), final edge pass -> e_out).  With a head:
 // NodeClassifier - the loop ends after the last node pass, whose kernel scores the hits (k_input's for
 // n_iters = 0): no final edge pass and no P / Q for it; e_trace then has n_iters rows.
 template <int F, int D>
-int forward_impl(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, float *e_out,
-                 float *e_trace, float *H_trace, void *ws, hipStream_t s, float *H_all = nullptr,
-                 float *Q_all = nullptr, const Head *head = nullptr)
+int forward_impl(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, const FwdOut &o, char *ws, hipStream_t s)
 {
-    constexpr int C = Shape<F, D>::C;
-    constexpr int LDH = Shape<F, D>::LDH;
-    const int64_t N = g->n_hits, E = g->n_segments;
-    Workspace w = carve(ws, N, E, LDH, D);
-    // training forward: every iteration's H is kept (H_all), no ping-pong
-    float *H = H_all ? H_all : w.Ha, *Hn = H_all ? H_all + (size_t)N * LDH : w.Hb;
-    const bool head0 = head && n_iters == 0;
-    int rc = run_input<F, D>(g->X, p->Win, p->bin, p->W1, p->b1, H, LDH, head0 ? nullptr : w.PQ, N, s,
-                             head0 ? head->Wo : nullptr, head0 ? head->bo : nullptr, head0 ? head->y : nullptr);
-    if (rc) return rc;
-    for (int t = 0; t <= n_iters; ++t) {
-        if (H_trace && N > 0)
-            GNN_LAUNCH("k_unpad", k_unpad, grid_for(N * C), kBlock, s, H, LDH, C,
-                       H_trace + (size_t)t * N * C, N * C);
-        const bool last = (t == n_iters);
-        if (last && head) break;
-        const Head *tail = (head && t == n_iters - 1) ? head : nullptr;      // the node pass that feeds the head
-        float *e_t = e_trace ? e_trace + (size_t)t * E : (last ? e_out : w.e);
-        rc = run_edge<D>(g->src, g->dst, w.PQ, p->b1, p->W2, p->b2, e_t, E, s);
-        if (rc) return rc;
+    const FwdRoute route = choose_fwd_route<F, D>(g->n_hits, o.head, n_iters, read_fwd_switches());
+    const FwdRun<F, D> c(g, p, ws, s, route);
+    const size_t row = (size_t)c.N * c.LDH;
+    float *H = o.H_all ? o.H_all : c.w.Ha, *Hn = o.H_all ? o.H_all + row : c.w.Hb;
+    const bool head0 = o.head && n_iters == 0;
+    int rc = c.input(H, c.LDH, head0 ? nullptr : c.w.PQ, head0 ? o.head : nullptr);
+    for (int t = 0; !rc; ++t) {
+        if (o.H_trace && (rc = c.unpad(H, o.H_trace + (size_t)t * c.N * c.C))) break;
+        const bool last = t == n_iters;
+        if (last && o.head) break;
+        float *e_t = o.e_trace ? o.e_trace + (size_t)t * c.E : (last ? o.e_out : c.w.e);
+        if ((rc = c.edge(c.w.PQ, e_t))) break;
         if (last) {
-            if (e_trace && E > 0 && e_out != e_t) {
-                hipError_t err = hipMemcpyAsync(e_out, e_t, (size_t)E * sizeof(float),
-                                                hipMemcpyDeviceToDevice, s);
+            if (o.e_trace && c.E > 0 && o.e_out != e_t) {
+                hipError_t err = hipMemcpyAsync(o.e_out, e_t, (size_t)c.E * sizeof(float), hipMemcpyDeviceToDevice, s);
                 if (err != hipSuccess) return fail(-(int)err, "copy of final scores failed");
             }
             break;
         }
-        rc = run_node<F, D>(H, LDH, e_t, g, p->W3, p->b3, p->W4, p->b4, p->W1, p->b1, Hn, LDH,
-                            tail ? nullptr : w.PQ, s, Q_all ? Q_all + (size_t)t * N * D : nullptr, w.M,
-                            tail ? tail->Wo : nullptr, tail ? tail->bo : nullptr, tail ? tail->y : nullptr,
-                            // a NodeClassifier takes the wide kernels at every size: at the notebook's 32 x 50 hits
-                            // the one-lane k_node<4, 64> spills (0.21 ms a pass against 0.075 ms for k_node_walkW +
-                            // k_node_mlpW, profiles/nodeclf_kernel_trace.txt); SegmentClassifier keeps its routes
-                            head ? 0 : kNodeWideMinHits);
-        if (rc) return rc;
-        if (H_all) {
+        const Head *tail = t == n_iters - 1 ? o.head : nullptr;          // the node pass that feeds the head
+        rc = c.node(H, c.LDH, e_t, Hn, tail ? nullptr : c.w.PQ, o.Q_all ? o.Q_all + (size_t)t * c.N * D : nullptr, tail);
+        if (o.H_all) {
             H = Hn;
-            Hn = H + (size_t)N * LDH;
+            Hn = H + row;
         } else {
-            float *tmp = H; H = Hn; Hn = tmp;
+            std::swap(H, Hn);
         }
     }
-    return 0;
+    return rc;
+}
+
+// What the whole-model entry points share.  The last of their argument checks: the shape has kernels and the workspace
+// holds gnn_forward_workspace_bytes; then the 256-byte alignment and the shape dispatch.
+int check_forward(const gnn_graph_t *g, const gnn_params_t *p, const void *ws, size_t ws_bytes)
+{
+    if (!gnn_shape_supported(p->F, p->D))
+        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    return check_workspace(ws, ws_bytes, carve_fwd(nullptr, g->n_hits, g->n_segments, p->F, p->D).bytes);
+}
+int forward(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, const FwdOut &o, void *ws, void *stream)
+{
+    return with_fwd_shape(p->F, p->D, [&](auto sh) {
+        return forward_impl<sh.F, sh.D>(g, p, n_iters, o, align_ws(ws), static_cast<hipStream_t>(stream)); });
 }
 
 }  // namespace
@@ -1212,11 +1257,9 @@ int gnn_segclf_forward_events(const gnn_graph_t *g, const gnn_params_t *p, const
     if (!gnn_events_supported(p->F, p->D, max_hits, max_segments))
         return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit one workgroup's LDS at input_dim=%d hidden_dim=%d",
                     max_hits, max_segments, p->F, p->D);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return run_events<F_, D_>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_out, s);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    return with_fwd_shape(p->F, p->D, [&](auto sh) {
+        return run_events<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_out,
+                                      static_cast<hipStream_t>(stream)); });
 }
 
 int gnn_input_fwd(const float *X, const float *Win, const float *bin, float *H, int64_t n_hits,
@@ -1224,11 +1267,12 @@ int gnn_input_fwd(const float *X, const float *Win, const float *bin, float *H, 
 {
     if (!X || !Win || !bin || !H || n_hits < 0) return fail(GNN_ERR_BADARG, "gnn_input_fwd: bad argument");
     if (ldh < ((F + D + 3) & ~3) || (ldh & 3)) return fail(GNN_ERR_BADARG, "gnn_input_fwd: ldh must be a multiple of 4 >= C");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define X_(F_, D_) if (F == F_ && D == D_) return run_input<F_, D_>(X, Win, bin, nullptr, nullptr, H, ldh, nullptr, n_hits, s);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", F, D);
+    gnn_graph_t g = {};
+    gnn_params_t p = {};
+    g.X = X, g.n_hits = n_hits;
+    p.Win = Win, p.bin = bin;
+    return with_fwd_shape(F, D, [&](auto sh) {
+        return FwdRun<sh.F, sh.D>(&g, &p, nullptr, static_cast<hipStream_t>(stream), kOneLane).input(H, ldh, nullptr, nullptr); });
 }
 
 int gnn_edge_fwd(const float *H, int32_t ldh, const int32_t *src, const int32_t *dst,
@@ -1239,16 +1283,14 @@ int gnn_edge_fwd(const float *H, int32_t ldh, const int32_t *src, const int32_t 
     if (!H || !src || !dst || !W1 || !b1 || !W2 || !b2 || !e || !pq_ws || n_hits < 0 || n_segments < 0)
         return fail(GNN_ERR_BADARG, "gnn_edge_fwd: bad argument");
     if (ldh < F + D) return fail(GNN_ERR_BADARG, "gnn_edge_fwd: ldh < C");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define X_(F_, D_)                                                              \
-    if (F == F_ && D == D_) {                                                   \
-        int rc = run_pq<F_, D_>(H, ldh, W1, b1, pq_ws, n_hits, s);              \
-        if (rc) return rc;                                                      \
-        return run_edge<D_>(src, dst, pq_ws, b1, W2, b2, e, n_segments, s);     \
-    }
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", F, D);
+    gnn_graph_t g = {};
+    gnn_params_t p = {};
+    g.src = src, g.dst = dst, g.n_hits = n_hits, g.n_segments = n_segments;
+    p.W1 = W1, p.b1 = b1, p.W2 = W2, p.b2 = b2;
+    return with_fwd_shape(F, D, [&](auto sh) {
+        const FwdRun<sh.F, sh.D> c(&g, &p, nullptr, static_cast<hipStream_t>(stream), kOneLane);
+        if (int rc = c.pq(H, ldh, pq_ws)) return rc;
+        return c.edge(pq_ws, e); });
 }
 
 int gnn_node_fwd(const float *H, int32_t ldh, const float *e, const gnn_graph_t *g,
@@ -1260,17 +1302,17 @@ int gnn_node_fwd(const float *H, int32_t ldh, const float *e, const gnn_graph_t 
     if (g->n_hits > 0 && (!g->in_ptr || !g->out_ptr)) return fail(GNN_ERR_BADARG, "gnn_node_fwd: CSR missing");
     if (ldh < ((F + D + 3) & ~3) || (ldh & 3)) return fail(GNN_ERR_BADARG, "gnn_node_fwd: ldh must be a multiple of 4 >= C");
     if (Hnext == H) return fail(GNN_ERR_BADARG, "gnn_node_fwd: Hnext must not alias H");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define X_(F_, D_) if (F == F_ && D == D_) return run_node<F_, D_>(H, ldh, e, g, W3, b3, W4, b4, nullptr, nullptr, Hnext, ldh, nullptr, s);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", F, D);
+    gnn_params_t p = {};
+    p.W3 = W3, p.b3 = b3, p.W4 = W4, p.b4 = b4;
+    return with_fwd_shape(F, D, [&](auto sh) {
+        return FwdRun<sh.F, sh.D>(g, &p, nullptr, static_cast<hipStream_t>(stream), kOneLane)
+            .node(H, ldh, e, Hnext, nullptr, nullptr, nullptr); });
 }
 
 size_t gnn_forward_workspace_bytes(int64_t n_hits, int64_t n_segments, int32_t F, int32_t D)
 {
     if (n_hits < 0 || n_segments < 0 || F <= 0 || D <= 0) return 0;
-    return carve(nullptr, n_hits, n_segments, (F + D + 3) & ~3, D).bytes + 256;
+    return carve_fwd(nullptr, n_hits, n_segments, F, D).bytes;
 }
 
 int gnn_segclf_forward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_iters, float *e_out,
@@ -1284,20 +1326,9 @@ int gnn_segclf_forward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_it
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward: segment arrays missing");
     if (g->n_hits > 0 && (!g->X || !g->in_ptr || !g->out_ptr))
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward: hit arrays missing");
-    if (!p->Win || !p->bin || !p->W1 || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward: weight pointer missing");
-    if (!gnn_shape_supported(p->F, p->D))
-        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    if (!workspace || workspace_bytes < gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes",
-                    gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
-    // 256-byte align the carve base
-    void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return forward_impl<F_, D_>(g, p, n_iters, e_out, e_trace, H_trace, ws, s);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward: weight pointer missing");
+    if (int rc = check_forward(g, p, workspace, workspace_bytes)) return rc;
+    return forward(g, p, n_iters, {e_out, e_trace, H_trace, nullptr, nullptr, nullptr}, workspace, stream);
 }
 
 int gnn_segclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_iters,
@@ -1309,19 +1340,11 @@ int gnn_segclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, int32_
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train: bad argument");
     if ((g->n_segments > 0 && (!e_all || !g->src || !g->dst)) || (g->n_hits > 0 && (!H_all || !g->X || !g->in_ptr || !g->out_ptr)))
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train: array missing");
-    if (!gnn_shape_supported(p->F, p->D))
-        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    if (!workspace || workspace_bytes < gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "workspace too small");
-    void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = check_forward(g, p, workspace, workspace_bytes)) return rc;
     // e_trace = e_all makes every edge pass land in its row; the "final scores" copy goes to the
     // last row itself (no-op copy avoided by passing that row as e_out)
     float *last = e_all ? e_all + (size_t)n_iters * g->n_segments : nullptr;
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return forward_impl<F_, D_>(g, p, n_iters, last, e_all, nullptr, ws, s, H_all, Q_all);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    return forward(g, p, n_iters, {last, e_all, nullptr, H_all, Q_all, nullptr}, workspace, stream);
 }
 
 size_t gnn_backward_workspace_bytes(int64_t n_hits, int64_t n_segments, int32_t F, int32_t D)
@@ -1340,8 +1363,7 @@ int gnn_segclf_backward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_i
         return fail(GNN_ERR_BADARG, "gnn_segclf_backward: bad argument");
     if ((g->n_segments > 0 && (!e_all || !grad_out)) || (g->n_hits > 0 && !H_all))
         return fail(GNN_ERR_BADARG, "gnn_segclf_backward: saved tensors missing");
-    if (!gr->Win || !gr->bin || !gr->W1 || !gr->b1 || !gr->W2 || !gr->b2 || !gr->W3 || !gr->b3 || !gr->W4 || !gr->b4)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_backward: gradient pointer missing");
+    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward: gradient pointer missing");
     return backward(g, p, n_iters, e_all, H_all, Q_all, grad_out, gr, workspace, workspace_bytes,
                     static_cast<hipStream_t>(stream));
 }
@@ -1349,7 +1371,7 @@ int gnn_segclf_backward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_i
 // ---- NodeClassifier (gnn/MPNN_HitClassifier.ipynb cells 20-21): the trunk above, the output network in place
 // of the final edge pass ------------------------------------------------------------------------------------
 static int nodeclf_check(const char *who, const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
-                         int32_t n_iters, const float *y, void *workspace, size_t workspace_bytes)
+                         int32_t n_iters, const float *y, const void *workspace, size_t workspace_bytes)
 {
     if (!g || !p || !Wo || !bo || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0)
         return fail(GNN_ERR_BADARG, "%s: bad argument", who);
@@ -1357,29 +1379,17 @@ static int nodeclf_check(const char *who, const gnn_graph_t *g, const gnn_params
         return fail(GNN_ERR_BADARG, "%s: hit arrays missing", who);
     if (n_iters > 0 && g->n_segments > 0 && (!g->src || !g->dst))
         return fail(GNN_ERR_BADARG, "%s: segment arrays missing", who);
-    if (!p->Win || !p->bin || !p->W1 || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4)
-        return fail(GNN_ERR_BADARG, "%s: weight pointer missing", who);
-    if (!gnn_shape_supported(p->F, p->D))
-        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    if (!workspace || workspace_bytes < gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D))
-        return fail(GNN_ERR_WORKSPACE, "%s: workspace too small: need %zu bytes", who,
-                    gnn_forward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D));
-    return 0;
+    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "%s: weight pointer missing", who);
+    return check_forward(g, p, workspace, workspace_bytes);
 }
 
 int gnn_nodeclf_forward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo, int32_t n_iters,
                         float *y_out, float *H_trace, void *workspace, size_t workspace_bytes, void *stream)
 {
     gnn::ProfChain chain_;
-    int rc = nodeclf_check("gnn_nodeclf_forward", g, p, Wo, bo, n_iters, y_out, workspace, workspace_bytes);
-    if (rc) return rc;
-    void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = nodeclf_check("gnn_nodeclf_forward", g, p, Wo, bo, n_iters, y_out, workspace, workspace_bytes)) return rc;
     const Head head = {Wo, bo, y_out};
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return forward_impl<F_, D_>(g, p, n_iters, nullptr, nullptr, H_trace, ws, s, nullptr, nullptr, &head);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    return forward(g, p, n_iters, {nullptr, nullptr, H_trace, nullptr, nullptr, &head}, workspace, stream);
 }
 
 int gnn_nodeclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
@@ -1387,17 +1397,11 @@ int gnn_nodeclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, const
                               size_t workspace_bytes, void *stream)
 {
     gnn::ProfChain chain_;
-    int rc = nodeclf_check("gnn_nodeclf_forward_train", g, p, Wo, bo, n_iters, y_out, workspace, workspace_bytes);
-    if (rc) return rc;
+    if (int rc = nodeclf_check("gnn_nodeclf_forward_train", g, p, Wo, bo, n_iters, y_out, workspace, workspace_bytes)) return rc;
     if ((n_iters > 0 && g->n_segments > 0 && !e_all) || (g->n_hits > 0 && !H_all))
         return fail(GNN_ERR_BADARG, "gnn_nodeclf_forward_train: array missing");
-    void *ws = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const Head head = {Wo, bo, y_out};
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return forward_impl<F_, D_>(g, p, n_iters, nullptr, e_all, nullptr, ws, s, H_all, Q_all, &head);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    return forward(g, p, n_iters, {nullptr, e_all, nullptr, H_all, Q_all, &head}, workspace, stream);
 }
 
 int gnn_nodeclf_backward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo, int32_t n_iters,
@@ -1410,8 +1414,7 @@ int gnn_nodeclf_backward(const gnn_graph_t *g, const gnn_params_t *p, const floa
         return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: bad argument");
     if ((n_iters > 0 && g->n_segments > 0 && !e_all) || (g->n_hits > 0 && (!H_all || !y || !grad_y)))
         return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: saved tensors missing");
-    if (!gr->Win || !gr->bin || !gr->W1 || !gr->b1 || !gr->W2 || !gr->b2 || !gr->W3 || !gr->b3 || !gr->W4 || !gr->b4)
-        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: gradient pointer missing");
+    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: gradient pointer missing");
     if (!gnn_shape_supported(p->F, p->D))
         return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
     const HeadBwd head = {Wo, y, grad_y, gWo, gbo};
@@ -1467,11 +1470,6 @@ int gnn_dense_to_index(const float *Ri, const float *Ro, int64_t B, int64_t N, i
     return 0;
 }
 
-static bool grads_complete(const gnn_grads_t *gr)
-{
-    return gr && gr->Win && gr->bin && gr->W1 && gr->b1 && gr->W2 && gr->b2 && gr->W3 && gr->b3 && gr->W4 && gr->b4;
-}
-
 int gnn_edge_bwd(const float *H, int32_t ldh, const gnn_graph_t *g, const gnn_params_t *p, const float *e,
                  const float *grad_e, float *grad_H, const gnn_grads_t *gr, void *workspace,
                  size_t workspace_bytes, void *stream)
@@ -1510,11 +1508,9 @@ int gnn_segclf_forward_train_events(const gnn_graph_t *g, const gnn_params_t *p,
     if (!gnn_events_supported(p->F, p->D, max_hits, max_segments))
         return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit one workgroup's LDS at input_dim=%d hidden_dim=%d",
                     max_hits, max_segments, p->F, p->D);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return run_events<F_, D_>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, nullptr, s, e_all, H_all);
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    return with_fwd_shape(p->F, p->D, [&](auto sh) {
+        return run_events<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, nullptr,
+                                      static_cast<hipStream_t>(stream), e_all, H_all); });
 }
 
 int gnn_events_backward_supported(int32_t F, int32_t D, int64_t max_hits, int64_t max_segments)
@@ -1539,8 +1535,7 @@ int gnn_segclf_backward_events(const gnn_graph_t *g, const gnn_params_t *p, cons
     if (n_graphs > 0 && (!hit_ptr || !seg_ptr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: graph offsets missing");
     if ((g->n_segments > 0 && (!e_all || !grad_out || !g->src || !g->dst)) || (g->n_hits > 0 && (!H_all || !g->in_ptr || !g->out_ptr)))
         return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: saved tensors or graph arrays missing");
-    if (!gr->Win || !gr->bin || !gr->W1 || !gr->b1 || !gr->W2 || !gr->b2 || !gr->W3 || !gr->b3 || !gr->W4 || !gr->b4)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: gradient pointer missing");
+    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: gradient pointer missing");
     return backward_events(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_all, H_all,
                            grad_out, gr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
@@ -1587,8 +1582,7 @@ int gnn_segclf_forward_plan(const gnn_plan_t *pl, const gnn_params_t *p, int32_t
     if (!pl->X || !pl->in_off || !pl->out_off || (pl->n_tiles > 0 && !pl->tiles) ||
         (pl->n_segments > 0 && (!pl->src || !pl->dst || !pl->sd16 || !pl->chunks || !e_out)))
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: plan array missing");
-    if (!p->Win || !p->bin || !p->W1 || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: weight pointer missing");
+    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: weight pointer missing");
     return sell_forward(pl, p, n_iters, e_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
@@ -1607,8 +1601,7 @@ int gnn_segclf_forward_train_plan(const gnn_plan_t *pl, const gnn_params_t *p, i
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: e_out or the (tw_src, tw_dst) pair is needed");
     if (pl->n_pad > 0 && (!seg_ptr || !H_all || (n_iters > 0 && !Q_all)))
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: output array missing");
-    if (!p->Win || !p->bin || !p->W1 || !p->b1 || !p->W2 || !p->b2 || !p->W3 || !p->b3 || !p->W4 || !p->b4)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: weight pointer missing");
+    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: weight pointer missing");
     const int ldh = gnn_h_stride(p->F, p->D);
     if (ldh <= 0) return fail(GNN_ERR_UNSUPPORTED, "no HIP kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
     return sell_forward_train(pl, p, n_iters, seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh, e_out, workspace,

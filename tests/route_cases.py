@@ -1,10 +1,10 @@
-"""The route cases of tools/record_backward_routes.py and tools/record_plan_routes.py with what a value check needs
-(test infrastructure, not product; shared by test_gpu_backward_route.py, test_gpu_plan_route.py,
-test_gpu_route_values.py and test_route_values_host.py):
+"""The route cases of tools/record_backward_routes.py, tools/record_plan_routes.py and tools/record_forward_routes.py with
+what a value check needs (test infrastructure, not product; shared by test_gpu_backward_route.py, test_gpu_plan_route.py,
+test_gpu_forward_route.py, test_gpu_route_values.py and test_route_values_host.py):
 
-  the kernels    `kernels_of` / `plan_kernels_of`: the launches of a case, derived from its shape, iteration count,
-                 kept hidden layers, head and switch; `route_of`: what choose_bwd_route (csrc/backward.hip) returns
-                 for it, restated
+  the kernels    `kernels_of` / `plan_kernels_of` / `pass_kernels_of`: the launches of a case, derived from its shape,
+                 iteration count, kept hidden layers, head and switch; `route_of`: what choose_bwd_route
+                 (csrc/backward.hip) returns for it, restated
   the matrix     `matrix_cases()`: beyond the 19 recorded backward cases, every shape the library supports at T = 2
                  with the kept hidden layers, T = 2 without them and T = 0 on the per-pass entry point, every shape
                  the one-launch backward accepts at T = 2, and the seeded head without k_fin_hit - on the recorder's
@@ -48,8 +48,10 @@ def _json(name):
 
 bwd = _tool("record_backward_routes")
 fwd = _tool("record_plan_routes")
+fwd_pass = _tool("record_forward_routes")
 RECORDED_BWD = _json("backward_routes.json")
 RECORDED_FWD = _json("plan_routes.json")
+RECORDED_PASS = _json("forward_routes.json")
 
 MIN_SCALE = 0.05        # every gradient tensor's max|fp64 reference| under `upstream`, unless it is identically zero
 # The events batch has 450 segments against the others' 6011: a thirteenth of the terms in every sum.  Unscaled, the
@@ -129,6 +131,34 @@ def plan_kernels_of(route, n_iters, n_pad, n_segments, training):
         names += [route["family"]] * n_iters
     names += ["k_edge"] if n_segments > 0 else []                    # (k_edge_w: profiled as k_edge)
     names += ["k_edge_tw"] if training and n_segments > 0 else []
+    return names
+
+
+NODE_WIDE_MIN_HITS = 2048     # kNodeWideMinHits (csrc/gnn_kernels.hip)
+
+
+def pass_kernels_of(case):
+    """The launches of a per-pass forward case with hits and segments, in order, under the names the profiler gives
+    them: choose_fwd_route (csrc/gnn_kernels.hip) restated from the entry point, hidden_dim, iteration count, total
+    hits, head, trace rows and switch."""
+    kind, D, T = case["kind"], case["D"], case["T"]
+    if kind in ("events", "events_train"):
+        return ["k_event"]
+    if kind in ("input", "edge", "node"):             # the module entry points: one lane per item at every size
+        return {"input": ["k_input"], "edge": ["k_pq", "k_edge"], "node": ["k_node"]}[kind]
+    n_hits = fwd_pass.SIZES[case["size"]][0] + 9
+    head = kind in ("nodeclf", "nodeclf_train")
+    wide = D >= 32 and case["env"] != "GNN_NODE_ONE_LANE"
+    wide_node = wide and (head or n_hits >= NODE_WIDE_MIN_HITS)
+    wide_input = wide and n_hits >= NODE_WIDE_MIN_HITS and not (head and T == 0)
+    names = ["k_input"] + (["k_pq_mlpW"] if wide_input else [])
+    for t in range(T + 1):
+        names += ["k_unpad"] if case["trace"] else []
+        if t == T and head:                           # the last node pass scored the hits: no final edge pass
+            break
+        names += ["k_edge"]
+        if t < T:
+            names += ["k_node_walkW", "k_node_mlpW"] if wide_node else ["k_node"]
     return names
 
 

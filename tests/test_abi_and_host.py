@@ -463,8 +463,8 @@ def test_backward_workspace_bytes_are_pinned():
         (11, 8): ([34816, 36608, 761344, 33415424], [7936, 7936, 4055296]),
         (11, 16): ([97024, 98816, 1399040, 61194496], [21760, 21760, 11354368]),
     }
-    with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "backward.hip")) as f:
-        listed = re.search(r"#define BWD_FOR_EACH_SHAPE\(X_\)((?:.*\\\n)*.*)\n", f.read()).group(1)
+    with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "common.h")) as f:         # the list the backward dispatches over
+        listed = re.search(r"#define GNN_FOR_EACH_SHAPE\(X_\)((?:.*\\\n)*.*)\n", f.read()).group(1)
     assert sorted(recorded) == sorted((int(a), int(b)) for a, b in re.findall(r"X_\((\d+), (\d+)\)", listed))
     lib = _lib.load()
     for (F, D), (want, want_events) in recorded.items():
