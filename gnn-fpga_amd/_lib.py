@@ -338,6 +338,7 @@ class _on:
         return self.ctx.__exit__(*exc)
 
 
+@functools.lru_cache(maxsize=None)
 def shape_supported(F, D):
     return bool(load().gnn_shape_supported(F, D))
 
@@ -581,17 +582,18 @@ def segclf_forward_train_fused(batch, weights, F, D, n_iters, want_out=True):
     plan it was made from.  Returns (e_all, H_all, Q_all, e_out) - the first three as segclf_forward_train gives
     them for this batch (row T of e_all by k_edge_tw, in this batch's segment order), e_out the final scores in the
     CALLER's segment order (None with want_out=False: a loss taken in this batch's order needs no second copy) - or
-    None when this batch or shape has no fused training forward (GNN_NO_FUSED_TRAIN=1 also says no: A / B runs)."""
-    plan = getattr(batch, "_fused", None)
-    if plan is None or getattr(batch, "_fused_dim", None) != D or os.environ.get("GNN_NO_FUSED_TRAIN"):
-        return None
-    if plan.n_pad != batch.n_hits or plan.n_segments != batch.n_segments or not plan_shape_supported(F, D):
-        return None
-    n_valid = getattr(batch, "_n_valid", None)
+    None when this batch or shape has no fused training forward (call_route.fused_train_available)."""
+    from .call_route import fused_train_available
+    return segclf_forward_train_twin(batch, weights, F, D, n_iters, want_out) if fused_train_available(batch, F, D) else None
+
+
+def segclf_forward_train_twin(twin, weights, F, D, n_iters, want_out=True):
+    """segclf_forward_train_fused for a twin that is known to have the fused training forward."""
+    n_valid = getattr(twin, "_n_valid", None)
     if n_valid is None:
-        n_valid = batch._n_valid = int((batch.src >= 0).sum().item())          # once per batch
-    return segclf_forward_train_plan(plan, batch.in_ptr, n_valid, weights, F, D, n_iters, tw_src=batch.src,
-                                     tw_dst=batch.dst, want_out=want_out)
+        n_valid = twin._n_valid = int((twin.src >= 0).sum().item())            # once per batch
+    return segclf_forward_train_plan(twin._fused, twin.in_ptr, n_valid, weights, F, D, n_iters, tw_src=twin.src,
+                                     tw_dst=twin.dst, want_out=want_out)
 
 
 def segclf_backward(batch, weights, F, D, n_iters, e_all, H_all, grad_out, into=None, Q_all=None):
@@ -820,6 +822,7 @@ def bce_loss(e, y, scale, want_grad=True):
     return loss, grad
 
 
+@functools.lru_cache(maxsize=None)
 def plan_shape_supported(F, D):
     return bool(load().gnn_plan_shape_supported(F, D))
 
@@ -917,7 +920,8 @@ def segclf_forward_train_plan(plan, seg_ptr, n_segments_valid, weights, F, D, n_
     `tw_src` / `tw_dst` int32 [E]: that batch's segment endpoints (plan hit ids, -1 = padded).
     Returns (e_all [(T + 1), E] in that batch's segment order - row T filled when tw_src / tw_dst are given, else
     the caller's to fill from e_out -, H_all [(T + 1), n_pad, ldh], Q_all [T, n_pad, D], e_out [E] in the plan's
-    segment order or None with want_out=False) or None when the shape has no fused training forward."""
+    segment order or None with want_out=False).  A shape without a fused training forward is an error like any other:
+    whether there is one is decided before the call (call_route.fused_train_available)."""
     dev = plan.X.device
     E, Np = plan.n_segments, plan.n_pad
     ldh = h_stride(F, D)
@@ -938,16 +942,13 @@ def segclf_forward_train_plan(plan, seg_ptr, n_segments_valid, weights, F, D, n_
         plan._struct_dev = dev
     p = params_struct(weights, F, D, flags)
     with _on(plan.X, g, p) as st:
-        rc = load().gnn_segclf_forward_train_plan(ctypes.byref(g), ctypes.byref(p), n_iters,
-                                                  _dev(seg_ptr, torch.int32, "seg_ptr"),
-                                                  None if tw_src is None else _dev(tw_src, torch.int32, "tw_src"),
-                                                  None if tw_dst is None else _dev(tw_dst, torch.int32, "tw_dst"),
-                                                  e_all.data_ptr(), H_all.data_ptr(),
-                                                  Q_all.data_ptr(), None if e_out is None else e_out.data_ptr(),
-                                                  workspace.data_ptr(), workspace.numel(), st)
-    if rc == GNN_ERR_UNSUPPORTED:
-        return None
-    _check(rc)
+        _check(load().gnn_segclf_forward_train_plan(ctypes.byref(g), ctypes.byref(p), n_iters,
+                                                    _dev(seg_ptr, torch.int32, "seg_ptr"),
+                                                    None if tw_src is None else _dev(tw_src, torch.int32, "tw_src"),
+                                                    None if tw_dst is None else _dev(tw_dst, torch.int32, "tw_dst"),
+                                                    e_all.data_ptr(), H_all.data_ptr(),
+                                                    Q_all.data_ptr(), None if e_out is None else e_out.data_ptr(),
+                                                    workspace.data_ptr(), workspace.numel(), st))
     return e_all, H_all, Q_all, e_out
 
 

@@ -9,86 +9,63 @@ gnn/model.py:30 does.  X gets no gradient (the reference never asks for one).
 import torch
 
 from . import _lib
+from .call_route import refuse_unsupported, training_route
+
+
+def _trunk_weights(model):
+    """The ten tensors of the trunk in state_dict order, masks applied WITH torch ops (see above)."""
+    lin = model.input_network[0]
+    en, nn_ = model.edge_network.network, model.node_network.network
+    return [lin.weight, lin.bias,
+            en[0].effective_weight(), en[0].bias, en[2].effective_weight(), en[2].bias,
+            nn_[0].effective_weight(), nn_[0].bias, nn_[2].effective_weight(), nn_[2].bias]
+
+
+# ---- one training forward / backward pair on a call_route.Route: what _SegClf and GradBucket.step both run ------------
+def train_forward(route, w, F, D, n_iters, want_out=True):
+    """(e_all, H_all, Q_all, e_out) on route.batch: e_out - the final scores in the CALLER's segment order - only from
+    the twin's fused forward, and only when wanted (a loss taken in the twin's order needs no second copy)."""
+    if route.kind == "twin":                # the fused tile kernels of the plan the twin was made from
+        return _lib.segclf_forward_train_twin(route.batch, w, F, D, n_iters, want_out=want_out)
+    # small graphs (the reference's muon events, route.layout): the whole forward in one launch; else per module
+    return _lib.segclf_forward_train(route.batch, w, F, D, n_iters, layout=route.layout) + (None,)
+
+
+def train_backward(route, w, F, D, n_iters, e_all, H_all, Q_all, grad_e, into=None):
+    """The ten gradients (`into`: added into these ten tensors); grad_e in route.batch's segment order."""
+    if route.kind == "events":              # the whole backward in one launch
+        return _lib.segclf_backward_events(route.batch, route.layout, w, F, D, n_iters, e_all, H_all, grad_e, into=into)
+    return _lib.segclf_backward(route.batch, w, F, D, n_iters, e_all, H_all, grad_e, into=into, Q_all=Q_all)
 
 
 class _SegClf(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, batch, F, D, n_iters, use_events, *weights):
+    def forward(ctx, route, F, D, n_iters, *weights):
         w = [t.detach().to(torch.float32).contiguous() for t in weights]
-        # small graphs (the reference's muon events): the whole forward in one launch
-        lay = batch.event_layout() if (use_events and batch.n_graphs > 0) else None
-        # (only when the backward has its one-launch form too: the per-pass backward wants Q_all)
-        if not _lib.events_preferred(F, D, lay, backward=True):
-            lay = None
-        # plan-space twin of a detector-size batch: the fused tile kernels of the batch's own plan
-        fused = _lib.segclf_forward_train_fused(batch, w, F, D, n_iters) if lay is None else None
-        if fused is not None:
-            e_all, H_all, Q_all, e_out = fused
-        else:
-            e_all, H_all, Q_all = _lib.segclf_forward_train(batch, w, F, D, n_iters, layout=lay)
-        ctx.batch, ctx.F, ctx.D, ctx.n_iters, ctx.use_events = batch, F, D, n_iters, lay is not None
+        e_all, H_all, Q_all, e_out = train_forward(route, w, F, D, n_iters)
+        ctx.route, ctx.F, ctx.D, ctx.n_iters = route, F, D, n_iters
         ctx.save_for_backward(e_all, H_all, Q_all, *w)
-        if fused is not None:
+        if e_out is not None:
             return e_out                                 # already in the caller's segment order
-        rank = getattr(batch, "seg_rank", None)          # level-ordered twin: back to the caller's segment order
+        rank = getattr(route.batch, "seg_rank", None)    # level-ordered twin: back to the caller's segment order
         return e_all[n_iters].clone() if rank is None else e_all[n_iters].index_select(0, rank)
 
     @staticmethod
     def backward(ctx, grad_out):
         e_all, H_all, Q_all, *w = ctx.saved_tensors
         go = grad_out.to(torch.float32).contiguous()
-        b = ctx.batch
-        order = getattr(b, "seg_order", None)
+        order = getattr(ctx.route.batch, "seg_order", None)
         if order is not None:
             go = go.index_select(0, order)
-        # small graphs (the reference's muon events): the whole backward in one launch
-        lay = b.event_layout() if ctx.use_events else None          # (the forward's decision)
-        if lay is not None:
-            grads = _lib.segclf_backward_events(b, lay, list(w), ctx.F, ctx.D, ctx.n_iters, e_all, H_all, go)
-        else:
-            grads = _lib.segclf_backward(b, list(w), ctx.F, ctx.D, ctx.n_iters, e_all, H_all, go, Q_all=Q_all)
-        return (None, None, None, None, None) + tuple(grads)
-
-
-def training_batch(model, batch, use_events):
-    """The batch the training kernels run on: detector-size batches are renumbered in plan order once
-    (HitGraphBatch.level_ordered) so that the kernels' record gathers stay L2-local.
-    model.level_order_training: "auto" (default: from the second time the same batch object is trained
-    on), True (always), False (never)."""
-    policy = getattr(model, "level_order_training", "auto")
-    if not policy or batch.n_hits < 20000:
-        return batch
-    if policy == "auto" and getattr(batch, "_twin", None) is None:
-        # the twin costs a plan build and two sorts (10 ms at 3.2 M segments, ten steps' worth): it is
-        # built when a batch object comes back (epochs over cached batches, batch_generator), not for a
-        # batch that is seen once
-        batch._train_uses = getattr(batch, "_train_uses", 0) + 1
-        if batch._train_uses < 2:
-            return batch
-    if use_events:
-        lay = batch.event_layout()
-        if _lib.events_preferred(model.input_dim, model.hidden_dim, lay, backward=True):
-            return batch                       # small graphs: the one-launch kernels
-    return batch.level_ordered(model.hidden_dim)
+        grads = train_backward(ctx.route, list(w), ctx.F, ctx.D, ctx.n_iters, e_all, H_all, Q_all, go)
+        return (None, None, None, None) + tuple(grads)
 
 
 def segclf_apply(model, batch):
     """Differentiable forward of `model` (a gnn_fpga_amd SegmentClassifier) on `batch`."""
     F, D = model.input_dim, model.hidden_dim
-    if not batch.X.is_cuda:
-        raise _lib.GnnHipError("SegmentClassifier.forward needs tensors on a ROCm device; "
-                               "there is no CPU path")
-    if not _lib.shape_supported(F, D):
-        raise _lib.GnnHipError("no HIP training kernels for input_dim=%d hidden_dim=%d" % (F, D))
-    lin = model.input_network[0]
-    en, nn_ = model.edge_network.network, model.node_network.network
-    weights = [lin.weight, lin.bias,
-               en[0].effective_weight(), en[0].bias, en[2].effective_weight(), en[2].bias,
-               nn_[0].effective_weight(), nn_[0].bias, nn_[2].effective_weight(), nn_[2].bias]
-    # (the 1024-graph bound of the one-launch kernels: beyond it the per-pass kernels fill the chip)
-    use_events = bool(getattr(model, "use_events", True)) and batch.n_graphs <= 1024
-    batch = training_batch(model, batch, use_events)
-    e = _SegClf.apply(batch, F, D, model.n_iters, use_events, *weights)
+    refuse_unsupported("SegmentClassifier.forward", batch.X, F, D, training=True)
+    e = _SegClf.apply(training_route(model, batch), F, D, model.n_iters, *_trunk_weights(model))
     if batch.dense_shape:
         e = e.view(batch.dense_shape[0], batch.dense_shape[2])
     return e
@@ -173,16 +150,9 @@ class _NodeClf(torch.autograd.Function):
 def nodeclf_apply(model, batch):
     """Differentiable forward of `model` (a gnn_fpga_amd NodeClassifier) on `batch`: hit scores [n_hits]."""
     F, D = model.input_dim, model.hidden_dim
-    if not batch.X.is_cuda:
-        raise _lib.GnnHipError("NodeClassifier.forward needs tensors on a ROCm device; there is no CPU path")
-    if not _lib.shape_supported(F, D):
-        raise _lib.GnnHipError("no HIP training kernels for input_dim=%d hidden_dim=%d" % (F, D))
-    lin, out = model.input_network[0], model.output_network[0]
-    en, nn_ = model.edge_network.network, model.node_network.network
-    weights = [lin.weight, lin.bias,
-               en[0].effective_weight(), en[0].bias, en[2].effective_weight(), en[2].bias,
-               nn_[0].effective_weight(), nn_[0].bias, nn_[2].effective_weight(), nn_[2].bias,
-               out.weight, out.bias]
+    refuse_unsupported("NodeClassifier.forward", batch.X, F, D, training=True)
+    out = model.output_network[0]
+    weights = _trunk_weights(model) + [out.weight, out.bias]
     return _NodeClf.apply(batch, F, D, model.n_iters, *weights)
 
 

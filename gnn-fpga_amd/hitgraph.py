@@ -194,8 +194,7 @@ class HitGraphBatch:
         b.__dict__.update(self.__dict__)
         b.X = X
         b._gstruct = b._gstruct_raw = None       # cached C structs hold the old X pointer
-        b._twin = None
-        b._forwards = getattr(self, "_forwards", 0)
+        b._twin = None                           # (`_forwards`, call_route's counter, is carried over with the rest)
         if self.plan is not None:
             b.plan = self.plan.with_features(X)
             b.plan.hidden_dim = self.plan.hidden_dim

@@ -24,6 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F_
 
 from . import _lib
+from .call_route import inference_route, refuse_unsupported
 from .hitgraph import HitGraphBatch
 
 
@@ -66,6 +67,25 @@ def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def _net_weights(n):
+    """The four tensors of an edge / node network the kernels consume, masks applied."""
+    return [_f32c(n[0].effective_weight()), _f32c(n[0].bias), _f32c(n[2].effective_weight()), _f32c(n[2].bias)]
+
+
+def _effective_weights(model):
+    """The trunk's ten tensors the kernels consume, in state_dict order, masks applied."""
+    lin = model.input_network[0]
+    return [_f32c(lin.weight), _f32c(lin.bias)] + model.edge_network.weights() + model.node_network.weights()
+
+
+def _grown_workspace(module, need, device):
+    """module._workspace, replaced by a larger one (or one on `device`) when it does not do."""
+    ws = module._workspace
+    if ws is None or ws.numel() < need or ws.device != device:
+        ws = module._workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
+
+
 class EdgeNetwork(nn.Module):
     """Scores every segment from the features of its two hits (reference gnn/model.py:36-81)."""
 
@@ -84,9 +104,7 @@ class EdgeNetwork(nn.Module):
         self._C, self._D = input_dim, hidden_dim
 
     def weights(self):
-        n = self.network
-        return [_f32c(n[0].effective_weight()), _f32c(n[0].bias),
-                _f32c(n[2].effective_weight()), _f32c(n[2].bias)]
+        return _net_weights(self.network)
 
     def forward(self, X, Ri, Ro=None):
         """X = hit features H [B,N,C]; (Ri, Ro) dense, or Ri a HitGraphBatch.  -> e [B,E].
@@ -123,9 +141,7 @@ class NodeNetwork(nn.Module):
         self._C, self._D = input_dim, output_dim
 
     def weights(self):
-        n = self.network
-        return [_f32c(n[0].effective_weight()), _f32c(n[0].bias),
-                _f32c(n[2].effective_weight()), _f32c(n[2].bias)]
+        return _net_weights(self.network)
 
     def forward(self, X, e, Ri, Ro=None):
         """X = H [B,N,C], e [B,E] -> H' [B,N,D] (without the skip concat, like the reference).
@@ -233,7 +249,7 @@ class SegmentClassifier(nn.Module):
     # cell 3) never pays a plan.  The two routes sum in different orders (scores differ by ~1e-7).
     use_plan = "auto"
     first_forward_max_segments = 4_000_000      # "auto": larger never-seen batches build their plan at once (hidden_dim
-                                                # <= 16; half of it at hidden_dim 32, 0.6 M at 64: tools/fresh_probe.py)
+                                                # <= 16; scaled for wider ones by call_route.first_forward_limit)
 
     def __init__(self, input_dim=2, hidden_dim=8, n_iters=3, hidden_activation=nn.Tanh,
                  masks_e=None, masks_n=None):
@@ -250,7 +266,7 @@ class SegmentClassifier(nn.Module):
                                         hidden_activation, masks_n)
         self._workspace = None
         self.use_events = True    # batches of small graphs: whole forward in one launch
-        # training on a batch's level-ordered twin (autograd.training_batch): "auto" (default) = from the
+        # training on a batch's level-ordered twin (call_route.choose_training): "auto" (default) = from the
         # second time the same batch object is trained on - a stream of never-repeated batches (the
         # unchanged estimator.py loop hands over fresh dense matrices every step) never pays the twin's
         # plan build and two sorts, ten steps' worth; the first and the later steps on a batch sum in
@@ -263,6 +279,7 @@ class SegmentClassifier(nn.Module):
                                        # whole units (compact_dead_units; inference paths only)
         self._xp_cache = None     # (key, flag): the last exp-product decision (kept on the plan)
         self._w_cache = None      # (key, weights, GnnParams, D_run, info): rebuilt when a parameter changes
+        self._route = None        # the kind of the last call's call_route.Route (tests / diagnostics)
 
     def __getstate__(self):
         """copy.deepcopy(model) (gnn/estimator_maskedlinear.py:83, `load_weights`) and torch.save(model) go through
@@ -270,15 +287,11 @@ class SegmentClassifier(nn.Module):
         neither pickled nor shared with a copy whose tensors live elsewhere), route decisions - stay behind and are
         rebuilt by the copy's first forward."""
         st = self.__dict__.copy()
-        st["_workspace"] = st["_xp_cache"] = st["_w_cache"] = None
+        st["_workspace"] = st["_xp_cache"] = st["_w_cache"] = st["_route"] = None
         st.pop("_layers5", None)
         return st
 
-    def effective_weights(self):
-        """The ten tensors the kernels consume, in state_dict order, masks applied."""
-        lin = self.input_network[0]
-        return ([_f32c(lin.weight), _f32c(lin.bias)] + self.edge_network.weights() +
-                self.node_network.weights())
+    effective_weights = _effective_weights
 
     def _param_key(self):
         """Changes whenever a parameter is replaced, updated in place, moved, or (un)masked."""
@@ -345,68 +358,39 @@ class SegmentClassifier(nn.Module):
 
     def forward(self, inputs, trace=False):
         """Apply forward pass of the model: inputs = [X, Ri, Ro] or a HitGraphBatch."""
-        if isinstance(inputs, HitGraphBatch):
-            batch = inputs
-        else:
-            X, Ri, Ro = inputs
-            batch = _as_batch(X, Ri, Ro)
+        batch = inputs if isinstance(inputs, HitGraphBatch) else _as_batch(*inputs)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from .autograd import segclf_apply   # backward kernels live there
             return segclf_apply(self, batch)
-        F, D = self.input_dim, self.hidden_dim
-        if not batch.X.is_cuda:
-            raise _lib.GnnHipError("SegmentClassifier.forward needs tensors on a ROCm device; "
-                                   "there is no CPU path")
-        if not _lib.shape_supported(F, D):
-            raise _lib.GnnHipError("no HIP kernel for input_dim=%d hidden_dim=%d" % (F, D))
-        if not trace:
-            # inference: cached effective weights; D = the hidden_dim the kernels run at (narrower
-            # than the module's when masks have killed whole units)
-            weights, pstruct, D = self._cached_weights()
-        # small events (muon graphs): one launch, one workgroup per graph, everything in LDS
-        # (up to ~1k graphs: beyond that the tiled pipeline's throughput wins, tools/latency_probe.py)
-        lay = batch.event_layout() if (self.use_events and not trace and batch.n_graphs <= 1024 and
-                                       _lib.shape_supported(F, D)) else None
-        if _lib.events_preferred(F, D, lay):
-            e = _lib.segclf_forward_events(batch, lay, weights, F, D, self.n_iters, params=pstruct)
-            if batch.dense_shape:
-                e = e.view(batch.dense_shape[0], batch.dense_shape[2])
-            return e
-        fused = not trace and self.use_plan and _lib.plan_shape_supported(F, D)
-        if fused and self.use_plan == "auto" and (batch.plan is None or batch.plan.hidden_dim != D):
-            seen = getattr(batch, "_forwards", 0)
-            batch._forwards = seen + 1
-            # first forward of a never-seen batch: no plan yet - up to the size where the plan pays for itself
-            # at once (tools/fresh_probe.py: 32 c3 graphs 1.22 ms against 1.72 with the plan, 256 graphs 9.5
-            # against 6.7: the crossover is near 6.5 M segments)
-            # (the wide shapes' per-module kernels are slower against their fused ones: hidden_dim 32 crosses near
-            # 3 M segments, hidden_dim 64 - T = 6 - near 0.7 M)
-            limit = self.first_forward_max_segments
-            limit = limit if D <= 16 else limit // 2 if D <= 32 else limit * 3 // 20
-            fused = seen > 0 or batch.n_segments > limit
-        if fused:
-            plan = batch.build_plan(D)
-            need = _lib.plan_workspace_bytes(plan.n_pad, plan.n_segments, F, D)
-        else:
-            need = _lib.workspace_bytes(batch.n_hits, batch.n_segments, F, D)
-        if (self._workspace is None or self._workspace.numel() < need or
-                self._workspace.device != batch.X.device):
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=batch.X.device)
-        if fused:     # relabel + SELL-16 plan, fused iteration kernels (csrc/sell_pipeline.hip)
-            res = _lib.segclf_forward_plan(plan, weights, F, D, self.n_iters,
-                                           workspace=self._workspace,
-                                           flags=(self._exp_product_flag(plan, weights) |
-                                                  (_lib.GNN_FLAG_BF16_MLP if self.mlp_bf16 else 0)),
-                                           params=pstruct)
-        else:         # CSR kernels, one per reference module (csrc/gnn_kernels.hip); traces
-            # (inference: the cached - possibly compacted - weights at the width they run at; traces: full width)
-            res = _lib.segclf_forward(batch, self.effective_weights() if trace else weights, F,
-                                      self.hidden_dim if trace else D, self.n_iters,
-                                      workspace=self._workspace, trace=trace)
-        e = res[0] if trace else res
+        refuse_unsupported("SegmentClassifier.forward", batch.X, self.input_dim, self.hidden_dim)
+        if trace:       # every module's output at full width
+            weights, pstruct, D = self.effective_weights(), None, self.hidden_dim
+        else:           # cached effective weights; D = the hidden_dim the kernels run at (narrower than the module's
+            weights, pstruct, D = self._cached_weights()        # when masks have killed whole units)
+        route = inference_route(self, batch, D, trace)          # which kernels, and why: call_route.py
+        out = getattr(self, "_run_" + route.kind)(route, weights, pstruct, D, trace)
+        e = out[0] if trace else out
         if batch.dense_shape:
             e = e.view(batch.dense_shape[0], batch.dense_shape[2])
-        return (e, res[1], res[2]) if trace else e
+        return (e, out[1], out[2]) if trace else e
+
+    def _run_events(self, route, weights, pstruct, D, trace):
+        """Small events (muon graphs): one launch, one workgroup per graph, everything in LDS."""
+        return _lib.segclf_forward_events(route.batch, route.layout, weights, self.input_dim, D, self.n_iters,
+                                          params=pstruct)
+
+    def _run_plan(self, route, weights, pstruct, D, trace):
+        """Relabel + SELL-16 plan, fused iteration kernels (csrc/sell_pipeline.hip)."""
+        plan, F = route.plan, self.input_dim
+        ws = _grown_workspace(self, _lib.plan_workspace_bytes(plan.n_pad, plan.n_segments, F, D), route.batch.X.device)
+        flags = self._exp_product_flag(plan, weights) | (_lib.GNN_FLAG_BF16_MLP if self.mlp_bf16 else 0)
+        return _lib.segclf_forward_plan(plan, weights, F, D, self.n_iters, workspace=ws, flags=flags, params=pstruct)
+
+    def _run_per_module(self, route, weights, pstruct, D, trace):
+        """CSR kernels, one per reference module (csrc/gnn_kernels.hip); trace=True: also e_t and H_t of every pass."""
+        b, F = route.batch, self.input_dim
+        ws = _grown_workspace(self, _lib.workspace_bytes(b.n_hits, b.n_segments, F, D), b.X.device)
+        return _lib.segclf_forward(b, weights, F, D, self.n_iters, workspace=ws, trace=trace)
 
 
 class NodeClassifier(nn.Module):
@@ -441,37 +425,22 @@ class NodeClassifier(nn.Module):
         st["_workspace"] = None
         return st
 
-    def effective_weights(self):
-        """The trunk's ten tensors the kernels consume, in state_dict order, masks applied."""
-        lin = self.input_network[0]
-        return ([_f32c(lin.weight), _f32c(lin.bias)] + self.edge_network.weights() +
-                self.node_network.weights())
+    effective_weights = _effective_weights
 
     def forward(self, inputs, trace=False):
         """inputs = [X, Ri, Ro] or a HitGraphBatch -> hit scores ([B, N] or [n_hits]); trace=True also
         returns the hit features of every iteration [(T+1), n_hits, C]."""
-        if isinstance(inputs, HitGraphBatch):
-            batch = inputs
-        else:
-            X, Ri, Ro = inputs
-            batch = _as_batch(X, Ri, Ro)
+        batch = inputs if isinstance(inputs, HitGraphBatch) else _as_batch(*inputs)
         F, D = self.input_dim, self.hidden_dim
-        if not batch.X.is_cuda:
-            raise _lib.GnnHipError("NodeClassifier.forward needs tensors on a ROCm device; "
-                                   "there is no CPU path")
-        if not _lib.shape_supported(F, D):
-            raise _lib.GnnHipError("no HIP kernel for input_dim=%d hidden_dim=%d" % (F, D))
+        refuse_unsupported("NodeClassifier.forward", batch.X, F, D)
         if not trace and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             from .autograd import nodeclf_apply   # backward kernels live there
             y = nodeclf_apply(self, batch)
         else:
             out = self.output_network[0]
-            need = _lib.workspace_bytes(batch.n_hits, batch.n_segments, F, D)
-            if (self._workspace is None or self._workspace.numel() < need or
-                    self._workspace.device != batch.X.device):
-                self._workspace = torch.empty(need, dtype=torch.uint8, device=batch.X.device)
+            ws = _grown_workspace(self, _lib.workspace_bytes(batch.n_hits, batch.n_segments, F, D), batch.X.device)
             res = _lib.nodeclf_forward(batch, self.effective_weights(), _f32c(out.weight), _f32c(out.bias), F, D,
-                                       self.n_iters, workspace=self._workspace, trace=trace)
+                                       self.n_iters, workspace=ws, trace=trace)
             y = res[0] if trace else res
         if batch.dense_shape:
             y = y.view(batch.dense_shape[0], batch.dense_shape[1])

@@ -109,27 +109,18 @@ class GradBucket:
         bit); about a third of its host time.  Returns the global mean loss (0-d tensor); call
         `optimizer.step()` afterwards.  Reference: gnn/estimator.py:49-60."""
         from . import _lib
+        from .autograd import refuse_unsupported, train_backward, train_forward, training_route
         F, D, T = model.input_dim, model.hidden_dim, model.n_iters
-        if not batch.X.is_cuda:
-            raise _lib.GnnHipError("GradBucket.step needs tensors on a ROCm device; there is no CPU path")
+        refuse_unsupported("GradBucket.step", batch.X, F, D, training=True)
         layers = [model.edge_network.network[0], model.edge_network.network[2],
                   model.node_network.network[0], model.node_network.network[2]]
         with torch.no_grad():
             w = model.effective_weights()               # masks applied (W * mask), detached, contiguous
             self.flat.zero_()
-            use_events = bool(getattr(model, "use_events", True)) and 0 < batch.n_graphs <= 1024
-            lay = batch.event_layout() if use_events else None
-            if not _lib.events_preferred(F, D, lay, backward=True):
-                lay = None
-            if lay is None:
-                from .autograd import training_batch
-                batch = training_batch(model, batch, False)      # level-ordered twin: L2-local gathers
+            route = training_route(model, batch)
+            batch = route.batch                         # detector-size batches: the level-ordered twin
             # (the loss below is taken in the twin's segment order: no copy of the scores in the caller's order)
-            fused = _lib.segclf_forward_train_fused(batch, w, F, D, T, want_out=False) if lay is None else None
-            if fused is not None:
-                e_all, H_all, Q_all, _ = fused
-            else:
-                e_all, H_all, Q_all = _lib.segclf_forward_train(batch, w, F, D, T, layout=lay)
+            e_all, H_all, Q_all, _ = train_forward(route, w, F, D, T, want_out=False)
             yv = y.detach().to(torch.float32).contiguous().reshape(-1)
             order = getattr(batch, "seg_order", None)      # level-ordered twin: its segments are sorted
             if order is not None:
@@ -143,10 +134,7 @@ class GradBucket:
                 yv = kept[2]
             loss_sum, ge = _lib.bce_loss(e_all[T], yv, 1.0)
             into = [p.grad for p in self.params]
-            if lay is not None:
-                _lib.segclf_backward_events(batch, lay, w, F, D, T, e_all, H_all, ge, into=into)
-            else:
-                _lib.segclf_backward(batch, w, F, D, T, e_all, H_all, ge, into=into, Q_all=Q_all)
+            train_backward(route, w, F, D, T, e_all, H_all, Q_all, ge, into=into)
             for layer in layers:                        # d/dW of W * mask (gnn/model.py:30)
                 if layer.mask_flag:
                     layer.weight.grad.mul_(layer.mask.to(layer.weight.device))

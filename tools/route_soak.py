@@ -5,7 +5,7 @@ import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
-from gnn_fpga_amd import HitGraphBatch, synth, _lib
+from gnn_fpga_amd import HitGraphBatch, synth
 from gnn_fpga_amd.model import SegmentClassifier
 from oracle import index_c
 
@@ -72,11 +72,9 @@ for t in range(trials):
             continue
         worst["first_vs_fused"] = max(worst["first_vs_fused"], d)
         m.use_events = True
-        bb = fresh()
-        lay = bb.event_layout() if bb.n_graphs <= 1024 else None
-        if _lib.events_preferred(F, D, lay):
+        e_ev = m(fresh()).reshape(-1)
+        if m._route.kind == "events":        # (call_route.choose_inference's answer for this batch)
             n_events += 1
-            e_ev = m(bb).reshape(-1)
             d = (e_ev - e_fused).abs().max().item() if e_ev.numel() else 0.0
             worst["events_vs_fused"] = max(worst["events_vs_fused"], d)
             assert d < TOL, ("events vs fused", t, F, D, T, kind, d)
