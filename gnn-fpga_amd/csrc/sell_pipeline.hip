@@ -304,6 +304,16 @@ struct Cfg {
     static constexpr bool pipelined = (D <= 8 && F <= 3) || (D == 4);
     // shapes whose persistent phase-split kernel (k_iter2) builds with zero scratch / AGPRs
     static constexpr bool iter2 = (D <= 8);
+    // k_iter2's sweeps that score one list step per lane (sweep16_lane) instead of one per quad (sweep16), by launch
+    // variant (FIRST or later) and phase (A = in-sweeps, B = out-sweeps).  D = 8, both phases of the later launches:
+    // what profiles/lane_sweep_ab.txt measured faster.  The fused first launch has no registers for the rotated
+    // form (its own-hit network lives beside the sweep) and is slower with the unrotated one; D = 4 has no measured
+    // workload and keeps sweep16.  -DGNN_QUAD_SWEEP builds sweep16 everywhere (A / B runs).
+#ifdef GNN_QUAD_SWEEP
+    template <bool FIRST, bool PHASE_B> static constexpr bool lane_sweep = false;
+#else
+    template <bool FIRST, bool PHASE_B> static constexpr bool lane_sweep = iter2 && D == 8 && !FIRST;
+#endif
     // big weight tables are packed once by k_pack and copied, not rebuilt per workgroup
     static constexpr bool pack_first = (TL<F, D>::total > 4096);
     // ... and whose first-iteration variant (input network fused in, FIRST) does as well
@@ -1430,6 +1440,26 @@ __device__ __forceinline__ void sweep(const int *pre, const int32_t *__restrict_
     }
 }
 
+// k_iter2's packed lists: the next 8 list steps of a quad, one word per lane (lane q: steps 2q, 2q + 1 of the 8 as
+// 16-bit window indices); `c` holds the NC prefetched words of this lane, `taken` counts the words handed out
+template <int NC>
+__device__ __forceinline__ int take_word16(int (&c)[NC], int &taken, const int32_t *__restrict__ nbr16,
+                                           const int32_t *__restrict__ off16, int slice, int i16, int q)
+{
+    int w = c[0];
+    if (taken >= NC) {              // list longer than the prefetched words (rare): fetch and
+                                    // wait here, through asm: no tracked pending load on `w`
+        a_load_i32_s<0>(w, nbr16 + __builtin_amdgcn_readfirstlane(off16[slice]) + taken * 4 * SLICE,
+                        (unsigned)(q * SLICE + i16) * 4u);
+        a_wait_all();
+        asm volatile("" : "+v"(w));
+    }
+#pragma unroll
+    for (int i = 0; i + 1 < NC; ++i) c[i] = c[i + 1];
+    ++taken;
+    return w;
+}
+
 template <int D, int NC, bool XP, bool PIPE>
 __device__ __forceinline__ void sweep16(int (&c)[NC], const int32_t *__restrict__ nbr16,
                                         const int32_t *__restrict__ off16, int slice, int i16,
@@ -1439,20 +1469,7 @@ __device__ __forceinline__ void sweep16(int (&c)[NC], const int32_t *__restrict_
     constexpr int d4 = D / 4;
     if (len <= 0) return;
     int taken = 0;
-    auto take_word = [&]() {            // next 8 list steps of the quad
-        int w = c[0];
-        if (taken >= NC) {              // list longer than the prefetched words (rare): fetch and
-                                        // wait here, through asm: no tracked pending load on `w`
-            a_load_i32_s<0>(w, nbr16 + __builtin_amdgcn_readfirstlane(off16[slice]) + taken * 4 * SLICE,
-                            (unsigned)(q * SLICE + i16) * 4u);
-            a_wait_all();
-            asm volatile("" : "+v"(w));
-        }
-#pragma unroll
-        for (int i = 0; i + 1 < NC; ++i) c[i] = c[i + 1];
-        ++taken;
-        return w;
-    };
+    auto take_word = [&]() { return take_word16<NC>(c, taken, nbr16, off16, slice, i16, q); };
     // the 4 records of one step group; HI = 0: steps held by lanes 0,1 of the quad, 1: lanes 2,3
     // LDS byte address of this lane's piece of record 0; v_mad_u32_u16 then turns a 16-bit window
     // index (either half of a packed word, op_sel) into the piece's address in ONE instruction
@@ -1510,6 +1527,96 @@ __device__ __forceinline__ void sweep16(int (&c)[NC], const int32_t *__restrict_
             score4<d4, XP>(rb, own, w2, b2, q, acc);
         }
     }
+}
+
+// The same walk with one list step per LANE (D = 8): in a step group lane q of a quad scores step 4g + q alone -
+// the whole record, all 8 hidden units, the W2 product with b2 seeded into it, one sigmoid - and adds e R into a
+// lane-private 8-wide sum.  The four sums of a quad are folded into `acc` (this lane's 2 dimensions, where sweep16
+// leaves them) once per list: no transposes and no broadcasts per group.  Lists, group order and step order are
+// sweep16's; steps past a list's end read the NULL record as there.
+// Slot s of lane q holds chunk (s + q) & 3 of a record (a chunk = 16 bytes, [P | R] of 2 hidden units), so the lanes
+// of a quad read four different chunks with every instruction.  With all lanes on chunk s the 16 lanes of a
+// ds_read_b128 group share 4 of the bank row's 16 columns: measured, that form is slower than sweep16
+// (profiles/lane_sweep_ab.txt).  Own values and W2 are rotated to match - W2 is per lane then, 8 registers - which
+// makes the all-gather and the reduce-scatter plain rotations inside the quad.
+// One record group in registers (read, then score): a second one in flight, as sweep16's pipelined form has, does
+// not fit beside the rotated values.
+// `wtab`: W2 in the LDS weight table (chunk j at wtab + j * wst).
+template <int NC, bool XP>
+__device__ __forceinline__ void sweep16_lane(int (&c)[NC], const int32_t *__restrict__ nbr16,
+                                             const int32_t *__restrict__ off16, int slice, int i16,
+                                             int len, const float *REC, int q, const float *own,
+                                             const float *wtab, int wst, float b2, float *acc)
+{
+    constexpr int D = 8, CH = 4;        // floats of a record's chunk
+    if (len <= 0) return;
+    int taken = 0;
+    auto take_word = [&]() { return take_word16<NC>(c, taken, nbr16, off16, slice, i16, q); };
+    typedef __attribute__((address_space(3))) const float lds_cf;
+    f2_t ownr[4], w2r[4], sum[4];
+    unsigned base[4];                   // LDS byte address of slot s's chunk of record 0
+    // all-gather: slot s = the own values of lane (q + s) & 3
+    ownr[0] = f2_t{own[0], own[1]};
+    ownr[1] = f2_t{dpp<0x39>(own[0]), dpp<0x39>(own[1])};      // quad_perm [1,2,3,0]
+    ownr[2] = f2_t{dpp<0x4E>(own[0]), dpp<0x4E>(own[1])};      // quad_perm [2,3,0,1]
+    ownr[3] = f2_t{dpp<0x93>(own[0]), dpp<0x93>(own[1])};      // quad_perm [3,0,1,2]
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int ch = (s + q) & 3;
+        base[s] = (unsigned)(uintptr_t)(lds_cf *)(REC + ch * CH);
+        w2r[s] = f2_t{wtab[ch * wst], wtab[ch * wst + 1]};
+        sum[s] = f2_t{0.0f, 0.0f};
+    }
+    const unsigned sh = (q & 1) << 4;   // this lane's half of a list word
+    // the record of this lane's step of one group; hi = 0: the steps in the words of lanes 0,1 of the quad, 1: lanes 2,3.
+    // v_mad_u32_u16 turns the 16-bit window index into a chunk's address in one instruction (as sweep16)
+    auto issue = [&](f4_t *r, int w, bool hi) {
+        const int wq = hi ? __builtin_amdgcn_mov_dpp(w, 0xFA, 0xF, 0xF, true)     // quad_perm [2,2,3,3]
+                          : __builtin_amdgcn_mov_dpp(w, 0x50, 0xF, 0xF, true);    // quad_perm [0,0,1,1]
+        const unsigned idx = (unsigned)wq >> sh;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            unsigned ad;
+            asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(ad) : "v"(idx), "n"(8 * D), "v"(base[s]));
+            r[s] = *(const __attribute__((address_space(3))) f4_t *)(uintptr_t)ad;
+        }
+    };
+    // packed fp32 as score4: the two hidden units of a chunk are a register pair
+    auto score = [&](const f4_t *r) {
+        const f2_t one2 = {1.0f, 1.0f};
+        f2_t z2 = {b2, 0.0f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const f2_t ps = {r[s].x, r[s].y};
+            f2_t a;
+            if constexpr (XP) {
+                a = ps * ownr[s] + one2;
+            } else {
+                const f2_t z = ps + ownr[s];
+                const f2_t ex = {__builtin_amdgcn_exp2f(z.x), __builtin_amdgcn_exp2f(z.y)};
+                a = ex + one2;
+            }
+            const f2_t rr = {__builtin_amdgcn_rcpf(a.x), __builtin_amdgcn_rcpf(a.y)};
+            z2 = w2r[s] * rr + z2;
+        }
+        const float e = r_f(z2.x + z2.y);
+        const f2_t e2 = {e, e};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) sum[s] = f2_t{r[s].z, r[s].w} * e2 + sum[s];
+    };
+    for (int k = 0; k < len; k += 8) {
+        const int w = take_word();
+        f4_t r[4];
+        issue(r, w, false);
+        score(r);
+        if (k + 4 < len) {
+            issue(r, w, true);
+            score(r);
+        }
+    }
+    // reduce-scatter: lane q's chunk sits in slot s of lane (q - s) & 3
+    acc[0] += (sum[0].x + dpp<0x93>(sum[1].x)) + (dpp<0x4E>(sum[2].x) + dpp<0x39>(sum[3].x));
+    acc[1] += (sum[0].y + dpp<0x93>(sum[1].y)) + (dpp<0x4E>(sum[2].y) + dpp<0x39>(sum[3].y));
 }
 
 // What the TRAINING forward keeps of an iteration besides the next records (gnn_segclf_forward_train_plan; the
@@ -2810,7 +2917,11 @@ __global__ __launch_bounds__(1024) void k_iter2(
                     a_cur.Q.get(Qn);
                 }
                 const int len = __builtin_amdgcn_readfirstlane(a_cur.len);
-                sweep16<D, NC, XP, !FIRST>(a_cur.c, in_nbr16, in_off16, slice, i16, len, bufA, q, Qn, w2, b2, acc);
+                if constexpr (Cfg<F, D>::template lane_sweep<FIRST, false>)
+                    sweep16_lane<NC, XP>(a_cur.c, in_nbr16, in_off16, slice, i16, len, bufA, q, Qn,
+                                                    lds + L::o_w2, L::stride, b2, acc);
+                else
+                    sweep16<D, NC, XP, !FIRST>(a_cur.c, in_nbr16, in_off16, slice, i16, len, bufA, q, Qn, w2, b2, acc);
             }
             if constexpr (!LR) {
                 if (next >= 0) {
@@ -2872,7 +2983,11 @@ __global__ __launch_bounds__(1024) void k_iter2(
                     b_cur.P.get(Pn);
                 }
                 const int len = __builtin_amdgcn_readfirstlane(b_cur.len);
-                sweep16<D, NC, XP, false>(b_cur.c, out_nbr16, out_off16, slice, i16, len, bufB, q, Pn, w2, b2, acc);
+                if constexpr (Cfg<F, D>::template lane_sweep<FIRST, true>)
+                    sweep16_lane<NC, XP>(b_cur.c, out_nbr16, out_off16, slice, i16, len, bufB, q, Pn,
+                                                   lds + L::o_w2, L::stride, b2, acc);
+                else
+                    sweep16<D, NC, XP, false>(b_cur.c, out_nbr16, out_off16, slice, i16, len, bufB, q, Pn, w2, b2, acc);
             }
             // the next slice's registers arrive here (in flight during the sweep); doing it before
             // the hit update keeps the two register sets from overlapping with the MLP's

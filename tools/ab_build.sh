@@ -5,6 +5,7 @@
 # list of units); AB_VARIANT_LIB=<library> takes one that target built earlier instead of building now.
 # usage: bash tools/ab_build.sh -DGNN_NO_PIPE_B [bench args]
 #        bash tools/ab_build.sh -DGNN_NO_TRIM / -DGNN_FORWARD_WALK    (profiles/trim_walk_ab.txt: same scores, other work)
+#        bash tools/ab_build.sh -DGNN_QUAD_SWEEP                      (profiles/lane_sweep_ab.txt: sweep16 everywhere)
 set -eo pipefail
 FLAG=${1:?switch}; shift || true
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
