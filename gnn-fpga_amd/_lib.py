@@ -367,30 +367,21 @@ def graph_struct(batch):
 
 def raw_graph_struct(batch):
     """gnn_graph_t of a batch WITHOUT its segment lists (all six pointers NULL): what gnn_segclf_forward_events takes
-    for a never-seen batch - it builds the lists in LDS.  Cached on the batch like cached_graph_struct."""
+    for a never-seen batch - it builds the lists in LDS."""
     dev = batch.X.device
-    g = getattr(batch, "_gstruct_raw", None)
-    if g is None or g._device != dev:
-        g = GnnGraph()
-        g.X = _dev(batch.X, torch.float32, "X")
-        g.src, g.dst = _dev(batch.src, torch.int32, "src"), _dev(batch.dst, torch.int32, "dst")
-        if batch.src.device != dev or batch.dst.device != dev:
-            raise GnnHipError("the arrays of a batch must live on one device")
-        g.n_hits, g.n_segments = batch.n_hits, batch.n_segments
-        g._device = dev
-        batch._gstruct_raw = g
+    g = GnnGraph()
+    g.X = _dev(batch.X, torch.float32, "X")
+    g.src, g.dst = _dev(batch.src, torch.int32, "src"), _dev(batch.dst, torch.int32, "dst")
+    if batch.src.device != dev or batch.dst.device != dev:
+        raise GnnHipError("the arrays of a batch must live on one device")
+    g.n_hits, g.n_segments = batch.n_hits, batch.n_segments
+    g._device = dev
     return g
 
 
 def cached_graph_struct(batch):
-    """graph_struct(batch), built once per (batch, device): the tensors of a batch are never
-    replaced in place, so their device pointers are stable while the batch lives."""
-    dev = batch.X.device
-    g = getattr(batch, "_gstruct", None)
-    if g is None or batch._gstruct_dev != dev:
-        g = batch._gstruct = graph_struct(batch)
-        batch._gstruct_dev = dev
-    return g
+    """graph_struct(batch), built once per batch, device and X: device pointers are stable while the batch lives."""
+    return batch.derived("features", "gstruct", graph_struct)
 
 
 def params_struct(weights, F, D, flags=0):
@@ -532,7 +523,8 @@ def segclf_forward_events(batch, layout, weights, F, D, n_iters, out=None, param
         out = torch.empty(batch.n_segments, dtype=torch.float32, device=dev)
     # a batch nobody has asked the segment lists of (a never-seen event): the kernel builds them in LDS itself;
     # one graph: no offset arrays either - nothing is prepared or uploaded for a single fresh event
-    g = cached_graph_struct(batch) if getattr(batch, "_csr", None) is not None else raw_graph_struct(batch)
+    g = (cached_graph_struct(batch) if batch.derived("device", "csr") is not None else
+         batch.derived("features", "gstruct_raw", raw_graph_struct))
     p = params if params is not None else params_struct(weights, F, D)
     with _on(batch.X, g, p) as st:
         if batch.n_graphs == 1:
@@ -589,9 +581,7 @@ def segclf_forward_train_fused(batch, weights, F, D, n_iters, want_out=True):
 
 def segclf_forward_train_twin(twin, weights, F, D, n_iters, want_out=True):
     """segclf_forward_train_fused for a twin that is known to have the fused training forward."""
-    n_valid = getattr(twin, "_n_valid", None)
-    if n_valid is None:
-        n_valid = twin._n_valid = int((twin.src >= 0).sum().item())            # once per batch
+    n_valid = twin.derived("device", "n_valid", lambda t: int((t.src >= 0).sum().item()))      # once per batch
     return segclf_forward_train_plan(twin._fused, twin.in_ptr, n_valid, weights, F, D, n_iters, tw_src=twin.src,
                                      tw_dst=twin.dst, want_out=want_out)
 
@@ -885,25 +875,26 @@ def plan_workspace_bytes(n_hits, n_segments, F, D):
     return int(load().gnn_plan_workspace_bytes(n_hits, n_segments, F, D))
 
 
+def cached_plan_struct(plan):
+    return plan.derived("features", "struct", plan_struct)
+
+
 def segclf_forward_plan(plan, weights, F, D, n_iters, out=None, workspace=None, flags=0,
                         params=None):
     """Whole SegmentClassifier forward on a planned batch (fused pipeline) -> scores [E].
     `params`: a GnnParams built earlier from the same `weights` (skips re-validation)."""
     dev = plan.X.device
-    need = getattr(plan, "_ws_need", None)
-    if need is None or plan._ws_need_shape != (F, D):
+    need = plan.derived("structure", ("ws_need", F, D))
+    if need is None:
         if not plan_shape_supported(F, D):
             raise GnnHipError("no fused HIP kernel for input_dim=%d hidden_dim=%d" % (F, D))
-        need = plan._ws_need = plan_workspace_bytes(plan.n_pad, plan.n_segments, F, D)
-        plan._ws_need_shape = (F, D)
+        need = plan_workspace_bytes(plan.n_pad, plan.n_segments, F, D)
+        plan.remember("structure", ("ws_need", F, D), need)
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     if out is None:
         out = torch.empty(plan.n_segments, dtype=torch.float32, device=dev)
-    g = getattr(plan, "_struct", None)
-    if g is None or plan._struct_dev != dev:       # device pointers are stable while the plan lives
-        g = plan._struct = plan_struct(plan)
-        plan._struct_dev = dev
+    g = cached_plan_struct(plan)
     p = params if params is not None else params_struct(weights, F, D, flags)
     p.flags = flags
     with _on(plan.X, g, p) as st:
@@ -936,10 +927,7 @@ def segclf_forward_train_plan(plan, seg_ptr, n_segments_valid, weights, F, D, n_
     H_all = torch.empty((n_iters + 1, Np, ldh), dtype=torch.float32, device=dev)
     Q_all = torch.empty((n_iters, Np, D), dtype=torch.float32, device=dev)
     e_out = torch.empty(E, dtype=torch.float32, device=dev) if want_out else None
-    g = getattr(plan, "_struct", None)
-    if g is None or plan._struct_dev != dev:
-        g = plan._struct = plan_struct(plan)
-        plan._struct_dev = dev
+    g = cached_plan_struct(plan)
     p = params_struct(weights, F, D, flags)
     with _on(plan.X, g, p) as st:
         _check(load().gnn_segclf_forward_train_plan(ctypes.byref(g), ctypes.byref(p), n_iters,
@@ -1175,9 +1163,7 @@ def _muon_graph_out(dev, n_hits, n_segments, n_graphs):
 def _muon_graphs(t, hit_ptr, seg_ptr, layout, entry_start, status=None, layout_ptrs=None):
     from .hitgraph import HitGraphBatch
     from .muon_graph import MG_GRAPH_PRESENT, MG_GRAPH_VP_MISSING, MG_GRAPH_WRITTEN, MuonGraphs
-    batch = HitGraphBatch._from_device_arrays(t["X"], t["src"], t["dst"], t["y"], hit_ptr, seg_ptr)
-    if layout_ptrs is not None:                  # the padded offsets, made on the device: nothing to upload later
-        batch._event[0]._both = layout_ptrs
+    batch = HitGraphBatch._from_device_arrays(t["X"], t["src"], t["dst"], t["y"], hit_ptr, seg_ptr, layout_ptrs=layout_ptrs)
     f = t["flags"]
     return MuonGraphs(batch, t["entry"], t["pt"], t["eta"], (f & MG_GRAPH_WRITTEN) != 0,
                       (f & MG_GRAPH_VP_MISSING) != 0, t["hit_source"], t["hit_row"], layout=layout,

@@ -47,14 +47,14 @@ class _SegClf(torch.autograd.Function):
         ctx.save_for_backward(e_all, H_all, Q_all, *w)
         if e_out is not None:
             return e_out                                 # already in the caller's segment order
-        rank = getattr(route.batch, "seg_rank", None)    # level-ordered twin: back to the caller's segment order
+        rank = route.batch.seg_rank                      # level-ordered twin: back to the caller's segment order
         return e_all[n_iters].clone() if rank is None else e_all[n_iters].index_select(0, rank)
 
     @staticmethod
     def backward(ctx, grad_out):
         e_all, H_all, Q_all, *w = ctx.saved_tensors
         go = grad_out.to(torch.float32).contiguous()
-        order = getattr(ctx.route.batch, "seg_order", None)
+        order = ctx.route.batch.seg_order
         if order is not None:
             go = go.index_select(0, order)
         grads = train_backward(ctx.route, list(w), ctx.F, ctx.D, ctx.n_iters, e_all, H_all, Q_all, go)

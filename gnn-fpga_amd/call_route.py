@@ -1,7 +1,7 @@
 """Which kernels a SegmentClassifier call runs: decided once per call, here, before the first launch (the rules as two
 tables: DESIGN.md section 4, "Which route a model call takes").  `choose_inference` / `choose_training` are pure functions
 of plain values; `inference_route` / `training_route` read the knobs off the model, read and bump the per-batch counters
-`_forwards` / `_train_uses` (nobody else does), ask the batch for its event layout, plan and twin at most once and return
+"forwards" / "train_uses" (host entries of `batch.derived`; nobody else does), ask the batch for its event layout, plan and twin at most once and return
 a `Route`; its kind stays on the model as `_route.kind` (tests, diagnostics).
 
   inference  "events"      the whole forward in one launch, one workgroup per graph (k_event)
@@ -20,7 +20,7 @@ from . import _lib
 
 EVENTS_MAX_GRAPHS = 1024    # one-launch kernels: beyond it the tiled / per-pass kernels fill the chip (tools/latency_probe.py)
 TWIN_MIN_HITS = 20000       # smaller batches gain nothing from the level-ordered twin
-Choice = collections.namedtuple("Choice", "kind bump")     # bump: the batch's counter (_forwards / _train_uses) goes up
+Choice = collections.namedtuple("Choice", "kind bump")     # bump: the batch's counter (forwards / train_uses) goes up
 _EVENTS, _PER_MODULE, _PLAN, _PASS = (Choice(k, False) for k in ("events", "per_module", "plan", "pass"))
 # layout: the event layout ("events" only); plan: the execution plan ("plan" only); batch: what the kernels run on
 Route = collections.namedtuple("Route", "kind layout plan batch")
@@ -46,7 +46,7 @@ def first_forward_limit(max_segments, D):
 
 def choose_inference(F, D, trace, use_events, use_plan, max_segments, n_graphs, n_segments, layout, plan_dim, seen):
     """D: the width the kernels run at; layout: batch.event_layout(); plan_dim: hidden_dim of the plan the batch
-    carries (None: no plan); seen: how often the "auto" policy has met this batch (_forwards)."""
+    carries (None: no plan); seen: how often the "auto" policy has met this batch ("forwards")."""
     if trace:                                           # every module's output is wanted: full width, no plan
         return _PER_MODULE
     if (use_events and n_graphs <= EVENTS_MAX_GRAPHS and _lib.shape_supported(F, D) and
@@ -62,7 +62,7 @@ def choose_inference(F, D, trace, use_events, use_plan, max_segments, n_graphs, 
 
 
 def choose_training(F, D, use_events, policy, n_graphs, n_hits, layout, has_twin, uses, twin_differs=True, fused=True):
-    """policy: model.level_order_training; has_twin: the batch has its twin already; uses: its _train_uses;
+    """policy: model.level_order_training; has_twin: the batch has its twin already; uses: its "train_uses";
     twin_differs: batch.level_ordered() is another batch (it returns the batch itself when there is nothing to gain);
     fused: `fused_train_available` of that twin.  The last two are known only once the twin is built: with the
     defaults the answer "twin" means that it is wanted."""
@@ -87,8 +87,8 @@ def _fused_train_shape(F, D):
 def fused_train_available(twin, F, D):
     """Can the training forward of this plan-space batch (HitGraphBatch.level_ordered) run the fused tile kernels of
     the plan it was made from?  (GNN_NO_FUSED_TRAIN=1 says no: A / B runs.)"""
-    plan = getattr(twin, "_fused", None)
-    return (plan is not None and getattr(twin, "_fused_dim", None) == D and not os.environ.get("GNN_NO_FUSED_TRAIN") and
+    plan = twin._fused
+    return (plan is not None and twin._fused_dim == D and not os.environ.get("GNN_NO_FUSED_TRAIN") and
             plan.n_pad == twin.n_hits and plan.n_segments == twin.n_segments and _fused_train_shape(F, D))
 
 
@@ -97,12 +97,12 @@ def inference_route(model, batch, D_run, trace=False):
     use_events, n_graphs, plan = model.use_events, batch.n_graphs, batch.plan
     # (the layout is asked for only where it can matter: a batch's first answer costs a pass over its endpoints)
     lay = batch.event_layout() if use_events and not trace and n_graphs <= EVENTS_MAX_GRAPHS else None
-    seen = getattr(batch, "_forwards", 0)
+    seen = batch.derived("host", "forwards") or 0
     kind, bump = choose_inference(model.input_dim, D_run, trace, use_events, model.use_plan,
                                   model.first_forward_max_segments, n_graphs, batch.n_segments, lay,
                                   None if plan is None else plan.hidden_dim, seen)
     if bump:
-        batch._forwards = seen + 1
+        batch.remember("host", "forwards", seen + 1)
     model.__dict__["_route"] = _KEPT[kind]      # (the dict directly: nn.Module.__setattr__ costs more than the decision)
     return Route(kind, lay if kind == "events" else None, batch.build_plan(D_run) if kind == "plan" else None, batch)
 
@@ -112,15 +112,15 @@ def training_route(model, batch):
     F, D = model.input_dim, model.hidden_dim
     use_events = getattr(model, "use_events", True)
     lay = batch.event_layout() if use_events and 0 < batch.n_graphs <= EVENTS_MAX_GRAPHS else None
-    uses = getattr(batch, "_train_uses", 0)
+    uses = batch.derived("host", "train_uses") or 0
     facts = (F, D, use_events, getattr(model, "level_order_training", "auto"), batch.n_graphs, batch.n_hits, lay,
-             getattr(batch, "_twin", None) is not None, uses)
+             batch.derived("features", "twin") is not None, uses)
     c, run = choose_training(*facts), batch
     if c.kind == "twin":                        # wanted: build it (once per batch) and ask again with what came out
         twin = batch.level_ordered(D)
         c = choose_training(*facts, twin_differs=twin is not batch, fused=fused_train_available(twin, F, D))
         run = batch if c.kind == "pass" else twin
     if c.bump:
-        batch._train_uses = uses + 1
+        batch.remember("host", "train_uses", uses + 1)
     model.__dict__["_route"] = _KEPT[c.kind]
     return Route(c.kind, lay if c.kind == "events" else None, None, run)

@@ -61,12 +61,12 @@ class _EventLayout:
     device tensors, uploaded at first use (one copy for both; a single-graph forward never needs them) -
     hit_ptr / seg_ptr [G+1] int32."""
 
-    def __init__(self, hp, sp, device=None, sizes=None):
+    def __init__(self, hp, sp, device=None, sizes=None, both=None):
         self._hp, self._sp = hp, sp
         if sizes is None:
             sizes = (int(np.diff(np.asarray(hp)).max(initial=0)), int(np.diff(np.asarray(sp)).max(initial=0)))
         self.max_hits, self.max_segments = sizes
-        self._device, self._both = device, None
+        self._device, self._both = device, both      # both: [2, G+1] int32 made on the device (nothing to upload)
 
     def ptrs(self, device=None):
         device = self._device if device is None else device
@@ -78,13 +78,78 @@ class _EventLayout:
     seg_ptr = property(lambda self: self.ptrs()[1])
 
 
-class HitGraphBatch:
-    """A block-diagonal batch of hit graphs in index form (see module docstring)."""
+class DerivedStores:
+    """What batches and plans share: `_derived`, one dict ("store") of derived values per kind of dependency."""
+    __slots__ = ()
 
+    def derived(self, kind, name, make=None):
+        """Entry `name` of the store `kind`; if absent: made by `make(self)` and kept, or None without `make`."""
+        store = self._derived[kind]
+        v = store.get(name)
+        if v is None and make is not None:
+            v = store[name] = make(self)
+        return v
+
+    def remember(self, kind, name, value):
+        self._derived[kind][name] = value
+
+
+class HitGraphBatch(DerivedStores):
+    """A block-diagonal batch of hit graphs in index form (see module docstring).
+
+    Every field an instance can have is named in `__slots__` and set in `_set`, which every constructor goes through.
+    What is DERIVED from the arrays - by this module or another - lives in three stores (`derived` / `remember`):
+
+      "host"      from segments and offsets: "event" ((max_hits, max_segments) of the event layout, () = never the
+                  one-launch kernels), "ends" (host copies of src / dst), call_route's counters
+      "device"    also from the device: "csr", "csr_status", "layout" (the event layout with its device pointers),
+                  uploaded seg_ptr / hit_ptr; on a twin the valid-segment count and the sorted targets
+      "features"  also from X: both GnnGraph structs (they hold X's address) and the level-ordered twin
+
+                         host                device                                   features
+      to(device)         kept                the segment lists moved, the rest dropped dropped
+      with_features(X)   copied by value     shared                                   empty
+      level_ordered()    "event": () only    empty                                    empty (the twin is its own twin)
+      forget()           dropped             dropped                                  dropped (and the plan)
+    """
+
+    __slots__ = ("X", "src", "dst", "y", "n_hits", "n_features", "n_segments", "n_graphs", "hit_ptr", "seg_ptr",
+                 "dense_shape", "plan", "validate_csr",
+                 "hit_index", "pt", "eta",                              # set by the graph builders / from_npz
+                 "seg_order", "seg_rank", "_fused", "_fused_dim",       # a level-ordered twin's; None on any other batch
+                 "_derived", "__weakref__")
     _TENSORS = ("X", "src", "dst", "y")        # (+ the six CSR arrays once they exist)
 
-    def __init__(self, X, src, dst, y=None, hit_ptr=None, seg_ptr=None,
-                 dense_shape=None, csr=None, _checked=False):
+    def _set(self, X, src, dst, y, hit_ptr, seg_ptr, dense_shape=None, *, host=None, device=None, plan=None,
+             hit_index=None, pt=None, eta=None, validate_csr=False, seg_order=None, seg_rank=None, fused=None,
+             fused_dim=None):
+        """THE place where a batch's fields come into being (tensors, host int64 offsets; host / device: stores)."""
+        self.X, self.src, self.dst, self.y = X, src, dst, y
+        self.n_hits, self.n_features, self.n_segments = int(X.shape[0]), int(X.shape[1]), int(src.shape[0])
+        self.hit_ptr, self.seg_ptr, self.n_graphs = hit_ptr, seg_ptr, len(hit_ptr) - 1
+        self.dense_shape, self.plan = dense_shape, plan     # dense_shape: (B, N_max, E_max) when built from a padded batch
+        # Device-built lists: False = trust the endpoints (checked where the batch was made; the builder skips malformed
+        # segments either way), True = read the builder's status word back - 4 bytes and one synchronisation per batch.
+        self.validate_csr = validate_csr
+        self.hit_index, self.pt, self.eta = hit_index, pt, eta
+        self.seg_order, self.seg_rank, self._fused, self._fused_dim = seg_order, seg_rank, fused, fused_dim
+        self._derived = {"host": {} if host is None else host, "device": {} if device is None else device,
+                         "features": {}}
+        return self
+
+    # read-only views of four entries under the names they had as attributes (tests and diagnostics read them)
+    _twin = property(lambda self: self.derived("features", "twin"))
+    _csr = property(lambda self: self.derived("device", "csr"))
+    _forwards = property(lambda self: self.derived("host", "forwards") or 0)
+    _src_host = property(lambda self: (self.derived("host", "ends") or (None,))[0])
+
+    def forget(self):
+        """A batch nobody has seen: no derived entry (counters, and lists the caller brought, included), no plan."""
+        self._derived = {"host": {}, "device": {}, "features": {}}
+        self.plan = None
+        return self
+
+    def __init__(self, X, src, dst, y=None, hit_ptr=None, seg_ptr=None, dense_shape=None, csr=None, _checked=False):
         X = np.ascontiguousarray(X, dtype=np.float32)
         src = np.ascontiguousarray(src, dtype=_I32)
         dst = np.ascontiguousarray(dst, dtype=_I32)
@@ -96,60 +161,37 @@ class HitGraphBatch:
                 raise ValueError("a padded segment must have src = dst = -1")
             if src.size and (src.max(initial=-1) >= n or dst.max(initial=-1) >= n):
                 raise ValueError("segment endpoint out of range")
-        self.n_hits, self.n_features = n, X.shape[1]
-        self.n_segments = src.shape[0]
-        self.hit_ptr = np.asarray([0, n] if hit_ptr is None else hit_ptr, dtype=np.int64)
-        self.seg_ptr = np.asarray([0, self.n_segments] if seg_ptr is None else seg_ptr,
-                                  dtype=np.int64)
-        self.n_graphs = len(self.hit_ptr) - 1
-        self.dense_shape = dense_shape  # (B, N_max, E_max) when built from a padded batch
         t = torch.from_numpy
-        self.X, self.src, self.dst = t(X), t(src), t(dst)
         # The two CSRs serve the per-module kernels, the small-event kernel and the backward; the
         # tiled pipeline works from its own plan.  They are therefore built on first use (two
         # stable sorts of E keys: 15 s for 25.6 M segments) unless the caller brought them.
-        self._csr = None if csr is None else tuple(t(np.ascontiguousarray(a, dtype=_I32)) for a in csr)
-        self._src_host = src if csr is None else None
-        self._dst_host = dst if csr is None else None
-        self.y = None if y is None else t(np.ascontiguousarray(y, dtype=np.float32))
-        self.plan = None
+        self._set(t(X), t(src), t(dst), None if y is None else t(np.ascontiguousarray(y, dtype=np.float32)),
+                  np.asarray([0, n] if hit_ptr is None else hit_ptr, dtype=np.int64),
+                  np.asarray([0, src.shape[0]] if seg_ptr is None else seg_ptr, dtype=np.int64), dense_shape,
+                  device=None if csr is None else {"csr": tuple(t(np.ascontiguousarray(a, dtype=_I32)) for a in csr)})
 
     _CSR_NAMES = ("in_ptr", "in_eid", "in_nbr", "out_ptr", "out_eid", "out_nbr")
 
-    # Device-built lists: False = trust the endpoints (they were checked where the batch was made: on the host in
-    # the constructor, by gnn_dense_to_index's flags for dense input; the builder skips malformed segments either
-    # way), True = read the builder's status word back - 4 bytes and one synchronisation per batch.
-    validate_csr = False
+    def _build_csr(self):
+        n = self.n_hits
+        if self.X.is_cuda and os.environ.get("GNN_CSR_BUILDER", "hip") == "hip":
+            # gnn_csr_build (csrc/csr_build.hip): counting sort + rank, a handful of launches, no read-back;
+            # eid / nbr arrays keep all n_segments entries (the lists, then -1)
+            from . import _lib
+            parts = _lib.csr_build(self.src, self.dst, n)
+            if self.validate_csr and int(parts[6].item()) & 1:
+                raise ValueError("segment endpoint out of range, or a segment with exactly one negative end")
+            self.remember("device", "csr_status", parts[6])
+            return parts[:6]
+        if self.X.is_cuda:           # torch ops (stable sorts on the GPU; GNN_CSR_BUILDER=torch): A / B runs
+            return _csr_by_device(self.dst, self.src, n) + _csr_by_device(self.src, self.dst, n)
+        src, dst = self.src.numpy(), self.dst.numpy()
+        return tuple(torch.from_numpy(a) for a in _csr_by(dst, src, n) + _csr_by(src, dst, n))
 
     def _ensure_csr(self):
-        if self._csr is None:
-            n = self.n_hits
-            if self.X.is_cuda and os.environ.get("GNN_CSR_BUILDER", "hip") == "hip":
-                # gnn_csr_build (csrc/csr_build.hip): counting sort + rank, a handful of launches, no read-back;
-                # eid / nbr arrays keep all n_segments entries (the lists, then -1)
-                from . import _lib
-                parts = _lib.csr_build(self.src, self.dst, n)
-                if self.validate_csr and int(parts[6].item()) & 1:
-                    raise ValueError("segment endpoint out of range, or a segment with exactly one negative end")
-                self._csr, self._csr_status = parts[:6], parts[6]
-            elif self.X.is_cuda:     # torch ops (stable sorts on the GPU; GNN_CSR_BUILDER=torch): A / B runs
-                self._csr = _csr_by_device(self.dst, self.src, n) + _csr_by_device(self.src, self.dst, n)
-            else:
-                src, dst = self._src_host, self._dst_host
-                parts = _csr_by(dst, src, n) + _csr_by(src, dst, n)
-                self._csr = tuple(torch.from_numpy(a) for a in parts)
-                self._src_host = self._dst_host = None
-            # (device-built lists: the host copies of the endpoints are NOT dropped here - handing 2 x 12.8 MB back to
-            # the OS took 5 ms of the first forward / training step of a 3.2 M-segment batch born on the host, ten
-            # times the list build itself; `to(device)` lets go of large ones where the upload is paid anyway)
-        return self._csr
+        return self.derived("device", "csr", HitGraphBatch._build_csr)
 
-    in_ptr = property(lambda self: self._ensure_csr()[0])
-    in_eid = property(lambda self: self._ensure_csr()[1])
-    in_nbr = property(lambda self: self._ensure_csr()[2])
-    out_ptr = property(lambda self: self._ensure_csr()[3])
-    out_eid = property(lambda self: self._ensure_csr()[4])
-    out_nbr = property(lambda self: self._ensure_csr()[5])
+    in_ptr, in_eid, in_nbr, out_ptr, out_eid, out_nbr = (property(lambda self, i=i: self._ensure_csr()[i]) for i in range(6))
 
     def build_plan(self, hidden_dim, limits=None):
         """Tiles + windows + SELL-16 execution plan of the fused kernels, built once for the
@@ -190,15 +232,11 @@ class HitGraphBatch:
         if tuple(X.shape) != tuple(self.X.shape):
             raise ValueError("expected X of shape %s" % (tuple(self.X.shape),))
         X = X.to(self.X.device).contiguous()
-        b = HitGraphBatch.__new__(HitGraphBatch)
-        b.__dict__.update(self.__dict__)
-        b.X = X
-        b._gstruct = b._gstruct_raw = None       # cached C structs hold the old X pointer
-        b._twin = None                           # (`_forwards`, call_route's counter, is carried over with the rest)
-        if self.plan is not None:
-            b.plan = self.plan.with_features(X)
-            b.plan.hidden_dim = self.plan.hidden_dim
-        return b
+        d = self._derived        # (the C structs hold the old X pointer, the twin the old rows: "features" starts empty)
+        return HitGraphBatch.__new__(HitGraphBatch)._set(
+            X, self.src, self.dst, self.y, self.hit_ptr, self.seg_ptr, self.dense_shape, host=dict(d["host"]),
+            device=d["device"], plan=None if self.plan is None else self.plan.with_features(X),
+            hit_index=self.hit_index, pt=self.pt, eta=self.eta, validate_csr=self.validate_csr)
 
     def level_ordered(self, hidden_dim=8):
         """The same batch in PLAN SPACE: hits numbered by the execution plan's padded ids - (graph, detector
@@ -212,10 +250,10 @@ class HitGraphBatch:
         (`seg_order` / `seg_rank`) and weight gradients do not depend on numbering, so the twin is a drop-in for the
         training forward / backward.  Built once per batch (one plan + GPU sorts for its CSRs) and cached; returns
         self when there is nothing to gain (CPU batch, no segments, no plan for this shape)."""
-        twin = getattr(self, "_twin", None)
+        twin = self.derived("features", "twin")
         if twin is not None:
             return twin
-        self._twin = self
+        self.remember("features", "twin", self)
         if not self.X.is_cuda or self.n_hits == 0 or self.n_segments == 0:
             return self
         try:
@@ -229,10 +267,6 @@ class HitGraphBatch:
         rank = torch.empty(self.n_hits, dtype=torch.int64, device=dev)
         rank[perm[new_ids]] = new_ids                             # caller's hit id -> padded id
         src, dst = self.src.to(torch.int64), self.dst.to(torch.int64)
-        t = HitGraphBatch.__new__(HitGraphBatch)
-        t.__dict__.update({k: v for k, v in self.__dict__.items() if not k.startswith("_")})
-        t.n_hits = n_pad
-        t.X = plan.X[:n_pad].contiguous()                         # the plan's renumbered rows (dummies: zeros)
         ts = torch.where(src >= 0, rank[src.clamp_min(0)], src)
         td = torch.where(dst >= 0, rank[dst.clamp_min(0)], dst)
         # segments sorted by end hit, padded ones last, ties in the caller's order: seg_order[k] = caller's index
@@ -240,63 +274,63 @@ class HitGraphBatch:
         # caller's order
         key = torch.where(ts >= 0, td, torch.full_like(td, 2 ** 62))
         seg_order = torch.argsort(key, stable=True)
-        t.src = ts[seg_order].to(torch.int32).contiguous()
-        t.dst = td[seg_order].to(torch.int32).contiguous()
-        t.seg_order = seg_order
-        t.seg_rank = torch.empty_like(seg_order)
-        t.seg_rank[seg_order] = torch.arange(self.n_segments, dtype=torch.int64, device=dev)
-        if getattr(self, "y", None) is not None and torch.is_tensor(self.y) and self.y.numel() == self.n_segments:
-            t.y = self.y.to(dev)[seg_order]
-        t._csr = None
-        t._src_host = t._dst_host = None
-        t._gstruct = None
-        t._event = (None,)                     # detector-size graphs: never the one-launch kernels
-        t.plan = None
-        t._fused = plan                        # the plan whose padded ids ARE this batch's hit ids
-        t._fused_dim = hidden_dim
-        t._twin = t
-        self._twin = t
+        seg_rank = torch.empty_like(seg_order)
+        seg_rank[seg_order] = torch.arange(self.n_segments, dtype=torch.int64, device=dev)
+        y = self.y
+        if y is not None and y.numel() == self.n_segments:
+            y = y.to(dev)[seg_order]
+        # taken over: offsets and dense shape, not `hit_index` (the caller's numbering).  X: the plan's renumbered rows
+        # (dummies: zeros); "event": () - never the one-launch kernels; fused: the plan whose padded ids ARE its hit ids
+        t = HitGraphBatch.__new__(HitGraphBatch)._set(
+            plan.X[:n_pad].contiguous(), ts[seg_order].to(torch.int32).contiguous(),
+            td[seg_order].to(torch.int32).contiguous(), y, self.hit_ptr, self.seg_ptr, self.dense_shape,
+            host={"event": ()}, validate_csr=self.validate_csr, seg_order=seg_order, seg_rank=seg_rank, fused=plan,
+            fused_dim=hidden_dim)
+        t.remember("features", "twin", t)
+        self.remember("features", "twin", t)
         return t
+
+    def _event_sizes(self):
+        """The event layout's host part: (max_hits, max_segments) if block-diagonal as `event_layout` says, else ()."""
+        hp, sp = self.hit_ptr, self.seg_ptr
+        from . import _lib
+        if self.n_graphs == 1:
+            # one graph (a single event through the model): nothing to check beyond what the constructor checked,
+            # and no numpy passes on the way to the first launch
+            ok = (hp[0] == 0 and sp[0] == 0 and hp[1] == self.n_hits and sp[1] == self.n_segments and
+                  self.n_hits < 2 ** 31 and self.n_segments <= _lib.EVENTS_MAX_SEGMENTS)     # (larger: never a layout)
+            return (self.n_hits, self.n_segments) if ok else ()
+        ok = (hp[0] == 0 and sp[0] == 0 and hp[-1] == self.n_hits and
+              sp[-1] == self.n_segments and np.all(np.diff(hp) >= 0) and np.all(np.diff(sp) >= 0)
+              and self.n_hits < 2 ** 31 and self.n_segments < 2 ** 31)
+        # graphs too large for the one-workgroup-per-graph kernels never take them: skip the
+        # endpoint check, which copies src / dst to the host (50 us and a synchronisation on the
+        # first forward of every detector-size batch)
+        if not ok or int(np.diff(sp).max(initial=0)) > _lib.EVENTS_MAX_SEGMENTS:
+            return ()
+        if self.n_segments and self.n_graphs > 1:
+            # (the host copies `to` kept of a batch made on the host, else one copy back from the device)
+            src, dst = self.derived("host", "ends") or (self.src.cpu().numpy(), self.dst.cpu().numpy())
+            gseg = np.repeat(np.arange(self.n_graphs), np.diff(sp))
+            lo, hi = hp[:-1][gseg], hp[1:][gseg]
+            pad = src < 0
+            if not np.all(pad | ((src >= lo) & (src < hi) & (dst >= lo) & (dst < hi))):
+                return ()
+        return (int(np.diff(hp).max(initial=0)), int(np.diff(sp).max(initial=0)))
 
     def event_layout(self):
         """Per-graph layout for the one-workgroup-per-graph kernel (`_lib.segclf_forward_events`):
         device copies of hit_ptr / seg_ptr and the largest graph's size, or None when the batch is
         not block-diagonal in the sense that kernel needs (every segment of graph i inside
         [seg_ptr[i], seg_ptr[i+1]) joins two hits of graph i; padded segments are fine).
-        Checked once, on the host."""
-        if getattr(self, "_event", None) is None and self.n_graphs == 1:
-            # one graph (a single event through the model): nothing to check beyond what the constructor checked,
-            # and no numpy passes on the way to the first launch
-            hp, sp = self.hit_ptr, self.seg_ptr
-            from . import _lib
-            ok = (hp[0] == 0 and sp[0] == 0 and hp[1] == self.n_hits and sp[1] == self.n_segments and
-                  self.n_hits < 2 ** 31 and self.n_segments <= _lib.EVENTS_MAX_SEGMENTS)     # (larger: never a layout)
-            self._event = (_EventLayout(hp, sp, sizes=(self.n_hits, self.n_segments)) if ok else None,)
-        if getattr(self, "_event", None) is None:
-            hp, sp = self.hit_ptr, self.seg_ptr
-            ok = (hp[0] == 0 and sp[0] == 0 and hp[-1] == self.n_hits and
-                  sp[-1] == self.n_segments and np.all(np.diff(hp) >= 0) and np.all(np.diff(sp) >= 0)
-                  and self.n_hits < 2 ** 31 and self.n_segments < 2 ** 31)
-            if ok:
-                # graphs too large for the one-workgroup-per-graph kernels never take them: skip the
-                # endpoint check, which copies src / dst to the host (50 us and a synchronisation on the
-                # first forward of every detector-size batch)
-                from . import _lib
-                if int(np.diff(sp).max(initial=0)) > _lib.EVENTS_MAX_SEGMENTS:
-                    ok = False
-            if ok and self.n_segments and self.n_graphs > 1:
-                # (one graph: its endpoints were range-checked where the batch was made - nothing left to check;
-                # several: the host copies the constructor kept, else one copy back from the device)
-                src = self._src_host if self._src_host is not None else self.src.cpu().numpy()
-                dst = self._dst_host if self._dst_host is not None else self.dst.cpu().numpy()
-                gseg = np.repeat(np.arange(self.n_graphs), np.diff(sp))
-                lo, hi = hp[:-1][gseg], hp[1:][gseg]
-                pad = src < 0
-                ok = bool(np.all(pad | ((src >= lo) & (src < hi) & (dst >= lo) & (dst < hi))))
-            self._event = (_EventLayout(hp, sp) if ok else None,)
-        lay = self._event[0]
-        if lay is not None:
-            lay._device = self.X.device          # where hit_ptr / seg_ptr are uploaded when somebody asks for them
+        Checked once, on the host; the layout object itself (it uploads hit_ptr / seg_ptr when somebody asks for
+        them) is the device's."""
+        lay = self._derived["device"].get("layout")
+        if lay is None:
+            sizes = self.derived("host", "event", HitGraphBatch._event_sizes)
+            if sizes:
+                lay = _EventLayout(self.hit_ptr, self.seg_ptr, self.X.device, sizes)
+                self.remember("device", "layout", lay)
         return lay
 
     # -- constructors ------------------------------------------------------------------
@@ -507,68 +541,49 @@ class HitGraphBatch:
                 raise ValueError("incidence matrix column with more than one hit")
             if fl & 2:
                 raise ValueError("a segment column must be set in both Ri and Ro or in neither")
-        self = cls.__new__(cls)
-        self.n_hits, self.n_features, self.n_segments = B * N, F, B * E
-        self.hit_ptr = np.arange(B + 1, dtype=np.int64) * N
-        self.seg_ptr = np.arange(B + 1, dtype=np.int64) * E
-        self.n_graphs = B
-        self.dense_shape = (B, N, E)
-        self.X = f32(Xt).reshape(B * N, F)
-        self.src, self.dst = src, dst
-        self._csr = None
-        self._src_host = self._dst_host = None
-        self.y = None if y is None else (y.detach() if torch.is_tensor(y) else torch.from_numpy(np.asarray(y))
-                                         ).to(torch.float32).reshape(-1).to(Xt.device)
-        self.plan = None
+        if y is not None:
+            y = (y.detach() if torch.is_tensor(y) else torch.from_numpy(np.asarray(y))
+                 ).to(torch.float32).reshape(-1).to(Xt.device)
         # block-diagonal by construction: no host check of the endpoints
-        self._event = (_EventLayout(self.hit_ptr, self.seg_ptr, Xt.device),)
-        return self
+        return cls.__new__(cls)._set(f32(Xt).reshape(B * N, F), src, dst, y, np.arange(B + 1, dtype=np.int64) * N,
+                                     np.arange(B + 1, dtype=np.int64) * E, (B, N, E),
+                                     host={"event": (N, E) if B else (0, 0)})
 
     @classmethod
-    def _from_device_arrays(cls, X, src, dst, y, hit_ptr, seg_ptr, dense_shape=None):
+    def _from_device_arrays(cls, X, src, dst, y, hit_ptr, seg_ptr, dense_shape=None, layout_ptrs=None):
         """A batch from arrays that already live where they will be used (batcher.GraphStore): torch tensors X
         [N, F] float32, src / dst [E] int32 in batch numbering (-1 = padded), y [E] or None; hit_ptr / seg_ptr host
-        arrays.  The endpoints were checked when the store was built: block-diagonal by construction."""
-        self = cls.__new__(cls)
-        self.n_hits, self.n_features, self.n_segments = int(X.shape[0]), int(X.shape[1]), int(src.shape[0])
-        self.hit_ptr = np.asarray(hit_ptr, dtype=np.int64)
-        self.seg_ptr = np.asarray(seg_ptr, dtype=np.int64)
-        self.n_graphs = len(self.hit_ptr) - 1
-        self.dense_shape = dense_shape
-        self.X = X.to(torch.float32).contiguous()
-        self.src, self.dst = src.to(torch.int32).contiguous(), dst.to(torch.int32).contiguous()
-        self._csr = None
-        self._src_host = self._dst_host = None
-        self.y = None if y is None else y.to(torch.float32).contiguous()
-        self.plan = None
+        arrays; layout_ptrs: the two as one int32 [2, G+1] tensor on X's device, where the maker has it.  The
+        endpoints were checked when the store was built: block-diagonal by construction (a CPU batch checks)."""
+        self = cls.__new__(cls)._set(X.to(torch.float32).contiguous(), src.to(torch.int32).contiguous(),
+                                     dst.to(torch.int32).contiguous(), None if y is None else y.to(torch.float32).contiguous(),
+                                     np.asarray(hit_ptr, dtype=np.int64), np.asarray(seg_ptr, dtype=np.int64), dense_shape)
         if X.is_cuda:
-            self._event = (_EventLayout(self.hit_ptr, self.seg_ptr, X.device),)
-        else:                        # a CPU batch builds its lists on the host from these
-            self._src_host, self._dst_host = self.src.numpy(), self.dst.numpy()
+            lay = _EventLayout(self.hit_ptr, self.seg_ptr, X.device, both=layout_ptrs)
+            self.remember("host", "event", (lay.max_hits, lay.max_segments))
+            self.remember("device", "layout", lay)
         return self
 
     # -- device movement -----------------------------------------------------------------
     def to(self, device):
+        d = self._derived
+        if torch.device(device).type == "cuda" and not self.X.is_cuda and self.n_segments < (1 << 20):
+            # for the event layout's check: views of the tensors about to go (large graphs never take those kernels)
+            d["host"].setdefault("ends", (self.src.numpy(), self.dst.numpy()))
         for k in self._TENSORS:
             v = getattr(self, k)
             if v is not None:
                 setattr(self, k, v.to(device))
-        if torch.device(device).type == "cuda" and self.n_segments >= (1 << 20):
-            # the host copies served the host CSR builder and the event layout's endpoint check (graphs of this size
-            # never take the event kernels): freed with the upload, not inside the first forward
-            self._src_host = self._dst_host = None
-        if self._csr is not None:
-            self._csr = tuple(a.to(device) for a in self._csr)
         if self.plan is not None:
             self.plan.to(device)
-        self._gstruct = None         # cached C struct of raw device pointers (_lib.cached_graph_struct)
-        self._gstruct_raw = None
-        self._twin = None            # the level-ordered twin lives on the old device
+        # "device": the lists go along, the rest is made again at next use; "features": pointers into the old device
+        move = lambda v: v.to(device) if torch.is_tensor(v) else tuple(a.to(device) for a in v)      # noqa: E731
+        d["device"] = {k: move(v) for k, v in d["device"].items() if k in ("csr", "csr_status")}
+        d["features"] = {}
         return self
 
     def cuda(self, device=None):
-        return self.to(torch.device("cuda", torch.cuda.current_device() if device is None
-                                    else device))
+        return self.to(torch.device("cuda", torch.cuda.current_device() if device is None else device))
 
     @property
     def device(self):

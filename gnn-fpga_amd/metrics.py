@@ -273,13 +273,10 @@ def _host(t):
 
 
 def _device_seg_ptr(batch, device):
-    """The batch's seg_ptr as a device int64 tensor, uploaded once per batch and device."""
-    cached = getattr(batch, "_metrics_seg_ptr", None)
-    if cached is None or cached.device != device:
-        sp = _check_seg_ptr(batch.seg_ptr, batch.n_segments)
-        cached = torch.from_numpy(sp).to(device)
-        batch._metrics_seg_ptr = cached
-    return cached
+    """The batch's seg_ptr as an int64 tensor on `device` (the counters', which an `include_padding` update does not
+    compare with the batch's: hence the device in the entry's name), uploaded once."""
+    return batch.derived("device", ("seg_ptr", device),
+                         lambda b: torch.from_numpy(_check_seg_ptr(b.seg_ptr, b.n_segments)).to(device))
 
 
 _CTOR_KW = ("bins_per_octave", "device")

@@ -347,12 +347,13 @@ class SegmentClassifier(nn.Module):
         if not self.exp_product:
             return 0
         key = self._param_key()
-        cached = getattr(plan, "_xp", None)
+        cached = plan.derived("features", "xp")
         if cached is None or cached[0] is not self or cached[1] != key:
             # the width the kernels RUN at: `weights` are the compacted tensors when masks have killed
             # whole units (W1' is [D_run, 2 (F + D_run)]), not the module's hidden_dim
             bound = _lib.exp_product_bound(weights, self.input_dim, int(weights[2].shape[0]), plan.x_absmax)
-            cached = plan._xp = (self, key, _lib.GNN_FLAG_EXP_PRODUCT if bound <= 60.0 else 0)
+            cached = (self, key, _lib.GNN_FLAG_EXP_PRODUCT if bound <= 60.0 else 0)
+            plan.remember("features", "xp", cached)
         self._xp_cache = (key, cached[2])       # last decision taken (tests / diagnostics)
         return cached[2]
 

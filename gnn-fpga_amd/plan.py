@@ -29,6 +29,8 @@ NULL hit has id `n_pad`.
 import numpy as np
 import torch
 
+from .hitgraph import DerivedStores
+
 SLICE = 16
 TILE_DESC = 8    # ints per tile:  slice_begin, slice_end, in_lo, in_cnt, out_lo, out_cnt, mode, sched_base
 CHUNK_DESC = 8   # ints per chunk: seg_begin, seg_end, src_lo, src_cnt, dst_lo, dst_cnt, mode, 0
@@ -171,7 +173,7 @@ def _chunk_bounds(key, ok, E, CH):
     return np.concatenate(out)
 
 
-class SellPlan:
+class SellPlan(DerivedStores):
     def __init__(self, batch, limits):
         """batch: HitGraphBatch; limits: dict(tile_hits, iter_records, chunk_segments,
         edge_records) from the library (`_lib.plan_limits(F, D)`): LDS budgets in records."""
@@ -415,19 +417,31 @@ class SellPlan:
         # host copies for tests
         self.src_abs, self.dst_abs = src_new, dst_new
         self.level = level
+        self._declare()
 
     _TENSORS = ("X", "src", "dst", "in_off", "in_nbr", "out_off", "out_nbr", "in_off16", "in_nbr16",
                 "out_off16", "out_nbr16", "tiles", "chunks", "sched_a", "sched_b", "perm",
                 "x_absmax", "sd16")
 
+    def _declare(self):
+        """What every builder ends with: the width the plan is for (HitGraphBatch.build_plan sets it) and two stores -
+        "structure": from the arrays but X (workspace size, with_features' row map), "features": from X too (GnnPlan
+        struct, the model's exp-product decision).  `to` empties both, `with_features` shares the first only."""
+        self.hidden_dim = None
+        self._derived = {"structure": {}, "features": {}}
+
+    _xp = property(lambda self: self.derived("features", "xp"))      # (read-only view: tests and diagnostics)
+
     def to(self, device):
         for k in self._TENSORS:
             setattr(self, k, getattr(self, k).to(device))
-        # cached C structs hold raw device pointers of the tensors just replaced
-        self._struct = None
-        self._ws_need = None
-        self._xp = None
+        self._derived = {"structure": {}, "features": {}}
         return self
+
+    def _feature_rows(self):
+        perm = self.perm.to(torch.int64)                # padded id -> caller's hit id, -1 = dummy
+        slots = torch.nonzero(perm >= 0).reshape(-1)
+        return slots, perm[slots]
 
     def with_features(self, X):
         """The same plan for OTHER hit features of the same graphs (a re-calibrated or re-scaled read-out of the same
@@ -441,17 +455,12 @@ class SellPlan:
         if X.device != self.X.device:
             raise ValueError("X is on %s, the plan on %s" % (X.device, self.X.device))
         new = copy.copy(self)
+        new._derived = {"structure": self._derived["structure"], "features": {}}
         Xp = torch.zeros_like(self.X)
-        where = getattr(self, "_feature_rows", None)        # (structure: found once, shared by the copies)
-        if where is None or where[0].device != X.device:
-            perm = self.perm.to(torch.int64)                # padded id -> caller's hit id, -1 = dummy
-            slots = torch.nonzero(perm >= 0).reshape(-1)
-            where = self._feature_rows = (slots, perm[slots])
+        where = self.derived("structure", "feature_rows", SellPlan._feature_rows)     # (found once, shared by the copies)
         Xp[where[0]] = X[where[1]]
         new.X = Xp
         new.x_absmax = Xp.abs().max(dim=0).values if self.n_hits else torch.zeros_like(self.x_absmax)
-        new._struct = None               # cached C struct (raw pointers), exp-product decision: of the old features
-        new._xp = None
         return new
 
     @property

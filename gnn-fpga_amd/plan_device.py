@@ -383,6 +383,7 @@ class DeviceSellPlan(SellPlan):
         self.lds_tile_fraction = float(lds_mode.double().mean()) if n_tiles else 1.0
         self.lds_chunk_fraction = float(c_lds.double().mean()) if n_chunks else 1.0
         self._src_abs, self._dst_abs, self._level = src_new, dst_new, level
+        self._declare()
 
     # host copies for tests (plan.SellPlan keeps them as arrays; here they are made on demand)
     src_abs = property(lambda self: self._src_abs.cpu().numpy())

@@ -105,6 +105,7 @@ class HipSellPlan(SellPlan):
         self.lds_tile_fraction = float(np.float64(sz.n_lds_tiles) / np.float64(sz.n_tiles)) if sz.n_tiles else 1.0
         self.lds_chunk_fraction = float(np.float64(sz.n_lds_chunks) / np.float64(sz.n_chunks)) if sz.n_chunks else 1.0
         self._dbg = (a.get("src_abs"), a.get("dst_abs"), a.get("level"))
+        self._declare()
 
     # host copies for tests (debug=True)
     src_abs = property(lambda self: self._dbg[0].cpu().numpy().astype(np.int64))

@@ -122,15 +122,16 @@ class GradBucket:
             # (the loss below is taken in the twin's segment order: no copy of the scores in the caller's order)
             e_all, H_all, Q_all, _ = train_forward(route, w, F, D, T, want_out=False)
             yv = y.detach().to(torch.float32).contiguous().reshape(-1)
-            order = getattr(batch, "seg_order", None)      # level-ordered twin: its segments are sorted
+            order = batch.seg_order                        # level-ordered twin: its segments are sorted
             if order is not None:
                 # targets in the twin's order, kept with the twin while the caller's tensor is unchanged
                 # (a 4-byte gather over every segment is 35 us at 3.2 M segments)
                 # (the entry holds `y` itself: an address-and-version key would also match a NEW tensor
                 # the allocator placed at a freed one's address - stale labels, silently)
-                kept = getattr(batch, "_y_sorted", None)
+                kept = batch.derived("device", "y_sorted")
                 if kept is None or kept[0] is not y or kept[1] != y._version:
-                    kept = batch._y_sorted = (y, y._version, yv.index_select(0, order))
+                    kept = (y, y._version, yv.index_select(0, order))
+                    batch.remember("device", "y_sorted", kept)
                 yv = kept[2]
             loss_sum, ge = _lib.bce_loss(e_all[T], yv, 1.0)
             into = [p.grad for p in self.params]

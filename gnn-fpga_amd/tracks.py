@@ -276,15 +276,6 @@ class Tracks:
                           t(spec["matched"]), t(spec["counts"]))
 
 
-def _device_hit_ptr(batch, hp, device):
-    """The batch's hit_ptr as a device int64 tensor, uploaded once per batch and device."""
-    cached = getattr(batch, "_tracks_hit_ptr", None)
-    if cached is None or cached.device != device or cached.numel() != hp.size:
-        cached = torch.from_numpy(hp).to(device)
-        batch._tracks_hit_ptr = cached
-    return cached
-
-
 def build_tracks(batch, scores, threshold=0.5, mode="components", min_hits=3):
     """Tracks of a HitGraphBatch from its segments' scores (float32 [n_segments], or [B, E] as SegmentClassifier
     returns them for a dense-shaped batch).  CUDA scores (the batch on the same device) run the kernels,
@@ -309,7 +300,7 @@ def build_tracks(batch, scores, threshold=0.5, mode="components", min_hits=3):
             raise ValueError("the scores are on %s, the batch on %s" % (dev, batch.src.device))
         e = scores.detach().reshape(-1)
         e = e if e.dtype == torch.float32 and e.is_contiguous() else e.to(torch.float32).contiguous()
-        hpd = _device_hit_ptr(batch, hp, dev)
+        hpd = batch.derived("device", "hit_ptr", lambda b: torch.from_numpy(hp).to(dev))    # uploaded once per device
         ws, root, track_of_hit, sizes = _lib.track_build_labels(batch.src, batch.dst, e, batch.n_hits, hpd, threshold,
                                                                 mode, min_hits)
         return Tracks(track_of_hit, root, sizes, hp, mode, threshold, min_hits, ws=ws, hit_ptr_dev=hpd)

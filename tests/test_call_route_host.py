@@ -25,7 +25,16 @@ class StubBatch:
         self.n_graphs, self.n_hits, self.n_segments = n_graphs, n_hits, n_segments
         self.plan = None if plan_dim is None else types.SimpleNamespace(hidden_dim=plan_dim)
         self._layout, self._twin_kind, self._twin_attrs = layout, twin, dict(twin_attrs)
+        self._fused = self._fused_dim = None
+        self.kept = {}
         self.calls = {"event_layout": 0, "build_plan": 0, "level_ordered": 0}
+
+    def derived(self, kind, name, make=None):
+        assert make is None
+        return self.kept.get((kind, name))
+
+    def remember(self, kind, name, value):
+        self.kept[kind, name] = value
 
     def event_layout(self):
         self.calls["event_layout"] += 1
@@ -39,15 +48,15 @@ class StubBatch:
 
     def level_ordered(self, D):
         self.calls["level_ordered"] += 1
-        if getattr(self, "_twin", None) is None:
+        if self.derived("features", "twin") is None:
             if self._twin_kind == "self":
-                self._twin = self
+                self.remember("features", "twin", self)
             else:
                 plan = self.build_plan(D)
                 attrs = dict(n_hits=plan.n_pad, n_segments=plan.n_segments, _fused=plan, _fused_dim=D)
                 attrs.update(self._twin_attrs)
-                self._twin = types.SimpleNamespace(**attrs)
-        return self._twin
+                self.remember("features", "twin", types.SimpleNamespace(**attrs))
+        return self.derived("features", "twin")
 
 
 def model(F=3, D=8, **knobs):
@@ -100,14 +109,14 @@ def test_inference_route_on_stub_batches():
     b = StubBatch(n_segments=2000)
     kinds = [cr.inference_route(m, b, 8).kind for _ in range(3)]
     assert kinds == ["per_module", "plan", "plan"] and m._route.kind == "plan"
-    assert b._forwards == 2                                          # (the third call found the plan: no bump)
+    assert b.derived("host", "forwards") == 2                                          # (the third call found the plan: no bump)
     assert b.calls == {"event_layout": 3, "build_plan": 2, "level_ordered": 0}
     big = StubBatch(n_segments=2001)
     r = cr.inference_route(m, big, 8)
-    assert r.kind == "plan" and r.plan is big.plan and r.batch is big and big._forwards == 1
+    assert r.kind == "plan" and r.plan is big.plan and r.batch is big and big.derived("host", "forwards") == 1
     ev = StubBatch(n_graphs=8, layout=lay(40, 150))
     r = cr.inference_route(m, ev, 8)
-    assert r == ("events", ev._layout, None, ev) and not hasattr(ev, "_forwards") and ev.calls["event_layout"] == 1
+    assert r == ("events", ev._layout, None, ev) and ev.derived("host", "forwards") is None and ev.calls["event_layout"] == 1
     many = StubBatch(n_graphs=1025, layout=lay(40, 150))
     assert cr.inference_route(m, many, 8).kind == "per_module" and many.calls["event_layout"] == 0
     # the width the kernels run at decides, not the module's
@@ -120,7 +129,7 @@ def test_trace_is_per_module_whatever_the_knobs(use_events, use_plan):
     m = model(use_events=use_events, use_plan=use_plan)
     b = StubBatch(layout=lay(40, 150), plan_dim=8)
     r = cr.inference_route(m, b, 8, trace=True)
-    assert r == ("per_module", None, None, b) and not hasattr(b, "_forwards")
+    assert r == ("per_module", None, None, b) and b.derived("host", "forwards") is None
     assert b.calls == {"event_layout": 0, "build_plan": 0, "level_ordered": 0}
 
 
@@ -164,16 +173,17 @@ def test_training_route_on_stub_batches():
     m = model(level_order_training="auto")
     b = StubBatch(n_hits=20000, n_segments=90000)
     routes = [cr.training_route(m, b) for _ in range(3)]
-    assert [r.kind for r in routes] == ["pass", "twin", "twin"] and b._train_uses == 2
-    assert routes[0].batch is b and routes[1].batch is b._twin and routes[2].batch is b._twin and m._route.kind == "twin"
+    assert [r.kind for r in routes] == ["pass", "twin", "twin"] and b.derived("host", "train_uses") == 2
+    twin = b.derived("features", "twin")
+    assert routes[0].batch is b and routes[1].batch is twin and routes[2].batch is twin and m._route.kind == "twin"
     assert b.calls == {"event_layout": 3, "build_plan": 1, "level_ordered": 2}
     assert cr.training_route(model(level_order_training=True), StubBatch(n_hits=19999)).kind == "pass"
     own = StubBatch(n_hits=20000, twin="self")                       # nothing to gain: level_ordered returns the batch
     r = cr.training_route(model(level_order_training=True), own)
-    assert r.kind == "pass" and r.batch is own and own.calls["level_ordered"] == 1 and not hasattr(own, "_train_uses")
+    assert r.kind == "pass" and r.batch is own and own.calls["level_ordered"] == 1 and own.derived("host", "train_uses") is None
     ev = StubBatch(n_graphs=8, n_hits=30000, layout=lay(40, 150))
     r = cr.training_route(m, ev)
-    assert r == ("events", ev._layout, None, ev) and not hasattr(ev, "_train_uses") and ev.calls["level_ordered"] == 0
+    assert r == ("events", ev._layout, None, ev) and ev.derived("host", "train_uses") is None and ev.calls["level_ordered"] == 0
 
 
 @pytest.mark.parametrize("broken", ["_fused", "_fused_dim", "env", "n_hits", "n_segments", None])
@@ -184,7 +194,7 @@ def test_each_condition_of_the_fused_training_forward(broken, monkeypatch):
     if broken == "env":
         monkeypatch.setenv("GNN_NO_FUSED_TRAIN", "1")
     r = cr.training_route(m, b)
-    assert r.kind == ("twin" if broken is None else "twin_pp") and r.batch is b._twin and r.batch is not b
+    assert r.kind == ("twin" if broken is None else "twin_pp") and r.batch is b.derived("features", "twin") and r.batch is not b
 
 
 @pytest.mark.parametrize("F,D,kind", [(3, 8, "twin"), (11, 16, "twin"), (3, 32, "twin_pp"), (3, 64, "twin_pp"),

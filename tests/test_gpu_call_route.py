@@ -170,7 +170,7 @@ def test_a_model_does_not_keep_its_last_batch_alive(hip):
 
 def _tensor_bytes(obj):
     seen, total = set(), 0
-    for v in list(vars(obj).values()) + list(getattr(obj, "_csr", None) or ()):
+    for v in [getattr(obj, k) for k in obj.__slots__ if k != "__weakref__"] + list(obj._csr or ()):
         if torch.is_tensor(v) and v.is_cuda and v.data_ptr() not in seen:
             seen.add(v.data_ptr())
             total += v.numel() * v.element_size()

@@ -9,30 +9,18 @@ from gnn_fpga_amd import HitGraphBatch, synth, _lib
 from gnn_fpga_amd.model import SegmentClassifier
 
 
-def fresh(host, X, src, dst):
-    b = HitGraphBatch.__new__(HitGraphBatch)          # fresh batch object over resident arrays
-    b.__dict__.update(host.__dict__)
-    b.X, b.src, b.dst, b._csr, b.plan, b._event = X, src, dst, None, None, None
-    b._src_host = b._dst_host = None
-    b._gstruct = None
-    return b
-
-
 def one_shot(name, graphs, F, D, T, reps=10, events=False):
     torch.manual_seed(0)
     m = SegmentClassifier(input_dim=F, hidden_dim=D, n_iters=T).cuda().eval()
     m.use_events = events
-    host = HitGraphBatch.from_graphs(graphs)
-    X, src, dst = host.X.cuda(), host.src.cuda(), host.dst.cuda()
+    host = HitGraphBatch.from_graphs(graphs).cuda()
     out = {}
     for route, plan, builder in (("first", "auto", "hip"), ("plan", True, "hip"), ("torch-csr", False, "torch")):
         m.use_plan = plan
         os.environ["GNN_CSR_BUILDER"] = builder
         ts = []
         for _ in range(reps + 2):
-            b = fresh(host, X, src, dst)
-            if events:
-                b._event = None
+            b = host.forget()                         # a never-seen batch over resident arrays
             torch.cuda.synchronize(); t0 = time.perf_counter()
             with torch.no_grad():
                 m(b)
@@ -40,7 +28,7 @@ def one_shot(name, graphs, F, D, T, reps=10, events=False):
         out[route] = sorted(ts[2:])[len(ts[2:]) // 2] * 1e3
     os.environ["GNN_CSR_BUILDER"] = "hip"
     m.use_plan = "auto"
-    b = fresh(host, X, src, dst)
+    b = host.forget()
     with torch.no_grad(), _lib.profile(128) as prof:
         m(b)
     per = {}

@@ -39,18 +39,13 @@ def one_shot(name, graphs, F, D, T, reps=10):
     torch.manual_seed(0)
     m = SegmentClassifier(input_dim=F, hidden_dim=D, n_iters=T).cuda().eval()
     m.use_events = False
-    host = HitGraphBatch.from_graphs(graphs)
-    X, src, dst = host.X.cuda(), host.src.cuda(), host.dst.cuda()
+    b = HitGraphBatch.from_graphs(graphs).cuda()
     out = {}
     for plan in (True, False):
         m.use_plan = plan
         ts = []
         for _ in range(reps + 2):
-            b = HitGraphBatch.__new__(HitGraphBatch)          # fresh batch object over resident arrays
-            b.__dict__.update(host.__dict__)
-            b.X, b.src, b.dst, b._csr, b.plan, b._event = X, src, dst, None, None, None
-            b._src_host = b._dst_host = None
-            b._gstruct = None
+            b.forget()                                        # a never-seen batch over resident arrays
             torch.cuda.synchronize(); t0 = time.perf_counter()
             with torch.no_grad():
                 m(b)
