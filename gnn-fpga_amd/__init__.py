@@ -6,7 +6,7 @@ batch/loader, `synth.py` synthetic inputs, `shard.py` event-batch sharding over 
 `graph_build.py` segment graphs from detector hits, `hit_samples.py` the hit classifier's track samples from
 detector hits, `muon_graph.py` the muon trigger graphs from EMTF hits, `event_graphs.py` the ACTS full-event graphs
 from cluster hits, `select_hits.py` the TrackML barrel hit selection from raw event tables, `metrics.py` confusion
-counts, ROC and AUC, `tracks.py` track candidates from scored segments and their matching to particles, `gcn.py` the toy notebooks' graph-convolution classifiers and their compressed adjacency,
+counts, ROC and AUC, `tracks.py` track candidates from scored segments, their matching to particles and their fit, `gcn.py` the toy notebooks' graph-convolution classifiers and their compressed adjacency,
 `toy_graphs.py` the toy notebooks' segment and hit graphs built straight into that compressed adjacency,
 `cut_study.py` the all-pair histograms and the layer census that choose `build_graphs`' arguments.
 """
@@ -19,7 +19,7 @@ from .muon_graph import MuonGraphs, build_muon_graphs  # noqa: F401,E402
 from .event_graphs import EventGraphs, build_event_graphs  # noqa: F401,E402
 from .select_hits import BARREL_VLIDS, SelectedHits, select_hits  # noqa: F401,E402
 from .metrics import SegmentMetrics, evaluate  # noqa: F401,E402
-from .tracks import Tracks, TrackMatch, build_tracks  # noqa: F401,E402
+from .tracks import Tracks, TrackFit, TrackMatch, build_tracks  # noqa: F401,E402
 from .gcn import (GraphConv, GraphConvSelfInt, GCNBinaryClassifier, GCRNBinaryClassifier,  # noqa: F401,E402
                   SparseAdjacency, compress_adjacency)
 from .toy_graphs import (ToyHitGraphs, ToySegmentGraphs, build_toy_hit_graphs,  # noqa: F401,E402

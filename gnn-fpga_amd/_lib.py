@@ -213,6 +213,7 @@ SIGNATURES = {
     "gnn_track_build_lists": (ctypes.c_int, [_f, _i64, _f, _i64, _i64, _i64, _f, _sz, _f, _f, _f, _f, _f]),
     "gnn_track_match_workspace_bytes": (_sz, [_i64, _i64]),
     "gnn_track_match": (ctypes.c_int, [_f, _f, _i64, _f, _i64, _f, _i64, _i32, _f, _sz, _f, _f, _f, _f, _f, _f]),
+    "gnn_track_fit": (ctypes.c_int, [_f, _f, _i64, _i64, _f, _f, _f, _i64, _i32, _f, _f, _f, _f, _f]),
     "gnn_gcn_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
     "gnn_gcn_compress_count": (ctypes.c_int, [_f, _i64, _i32, _f, _f, _f, _f]),
     "gnn_gcn_compress_fill": (ctypes.c_int, [_f, _i64, _i32, _i32, _f, _f, _f, _f, _f]),
@@ -1314,6 +1315,26 @@ def track_match(track_of_hit, particle_id, hit_ptr, track_ptr, n_tracks, min_hit
             ws.numel(), maj.data_ptr(), maj_hits.data_ptr(), part_hits.data_ptr(), matched.data_ptr(), counts.data_ptr(),
             st))
     return maj, maj_hits, part_hits, matched, counts
+
+
+def track_fit(track_ptr, track_hits, x, y, z, max_hits):
+    """gnn_track_fit (csrc/track_fit.hip): (moments float64 [n_tracks, 13], params float64 [n_tracks, 8], n_fit int32
+    [n_tracks], status int32 [n_tracks]) on the device, asynchronous, nothing read back.  track_ptr, track_hits: device
+    int32; x, y, z: device float64 [n_hits]."""
+    dev, i32, f64 = track_ptr.device, torch.int32, torch.float64
+    n_tracks, n_track_hits, n = int(track_ptr.numel()) - 1, int(track_hits.numel()), int(x.numel())
+    if int(y.numel()) != n or int(z.numel()) != n or n_tracks < 0:
+        raise GnnHipError("track_fit: x, y and z must have one entry per hit, track_ptr at least one")
+    moments = torch.empty((n_tracks, 13), dtype=f64, device=dev)
+    params = torch.empty((n_tracks, 8), dtype=f64, device=dev)
+    n_fit = torch.empty(n_tracks, dtype=i32, device=dev)
+    status = torch.empty(n_tracks, dtype=i32, device=dev)
+    with _on(track_ptr) as st:
+        _check(load().gnn_track_fit(
+            _dev(track_ptr, i32, "track_ptr"), _dev(track_hits, i32, "track_hits"), n_tracks, n_track_hits,
+            _dev(x, f64, "x"), _dev(y, f64, "y"), _dev(z, f64, "z"), n, int(max_hits), moments.data_ptr(),
+            params.data_ptr(), n_fit.data_ptr(), status.data_ptr(), st))
+    return moments, params, n_fit, status
 
 
 # ---- choosing the graph builder's arguments (csrc/graph_build.hip gnn_cut_study, csrc/layer_census.hip) -----------------

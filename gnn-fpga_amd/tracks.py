@@ -27,6 +27,10 @@ noise; majority_hits - its hits in the track; particle_hits - all its hits in th
 matched - 2 majority_hits > track size and 2 majority_hits > particle_hits (the strict double majority: at most one
 track matches a particle).  counts int64 [4]: tracks, matched tracks, reconstructable particles (at least min_hits
 hits in their graph), reconstructable particles that are the majority of a matched track.
+
+Fit: `Tracks.fit(x, y, z)` gives every track its curvature, direction, impact parameter, z0, cot(theta) and two chi2
+(`TrackFit`); `fit_tracks_numpy` is the specification and csrc/track_fit.hip equals it bit for bit - see the comment
+above it.  `TrackFit.good(...)` is the quality cut, `TrackMatch.select(mask)` the counts after it.
 """
 import numpy as np
 import torch
@@ -178,6 +182,157 @@ def match_tracks_numpy(track_of_hit, n_tracks, particle_id, hit_ptr, min_hits=3)
             "particle_hits": part_hits.astype(np.int32), "matched": matched, "counts": counts}
 
 
+# ---- the track fit -----------------------------------------------------------------------------------------------------
+# Per track, from its hits' (x, y, z) in mm: Karimaki's non-iterative circle fit (NIM A305 (1991) 187), unweighted, and a
+# straight line z = z0 + cot r in (r, z) - the reference's own z0 variable (the segment cut of gnn/graph.py), not the
+# arc-length fit of a true helix.  `fit_tracks_numpy` is the specification and csrc/track_fit.hip restates it operation
+# for operation: float64 throughout, every operation rounded on its own (no FMA), every sum sequential over the
+# track's hits in list order from 0.0.
+# Sign convention: the point of closest approach to the origin is (d s, -d c), (c, s) is the direction there, pointing
+# from the innermost hit to the outermost, and rho > 0 bends clockwise.
+FIT_MOMENTS = ("x", "y", "z", "r2", "xx", "xy", "yy", "xr2", "yr2", "r2r2", "r", "rz", "zz")
+FIT_PARAMS = ("rho", "c", "s", "d", "chi2_circle", "cot", "z0", "chi2_line")
+FIT_STATUS_FEW, FIT_STATUS_MANY, FIT_STATUS_NONFINITE = 1, 2, 4
+FIT_STATUS_CIRCLE, FIT_STATUS_LINE, FIT_STATUS_RANGE = 8, 16, 32
+_FIT_UNFIT = FIT_STATUS_FEW | FIT_STATUS_MANY | FIT_STATUS_NONFINITE | FIT_STATUS_RANGE
+_FIT_BLANK = FIT_STATUS_MANY | FIT_STATUS_NONFINITE | FIT_STATUS_RANGE
+PT_GEV_PER_TESLA_MM = 2.99792458e-4            # pt [GeV] = 0.299792458 B [T] R [m]
+
+
+def _check_max_hits(max_hits):
+    if int(max_hits) != max_hits or max_hits < 3 or max_hits >= 2 ** 31:
+        raise ValueError("max_hits must be an integer >= 3, got %r" % (max_hits,))
+    return int(max_hits)
+
+
+def fit_tracks_numpy(track_ptr, track_hits, x, y, z, max_hits=32):
+    """The specification of the fit on host arrays (see the comment above).  track t owns
+    track_hits[track_ptr[t]:track_ptr[t+1]]; x, y, z [n_hits] are cast to float64.  Returns a dict: moments float64
+    [n_tracks, 13] (FIT_MOMENTS), params float64 [n_tracks, 8] (FIT_PARAMS), n_hits int32 [n_tracks], status int32
+    [n_tracks]: 0 fitted; bit 1 fewer than 3 hits (moments only); bit 2 more than max_hits hits (hits not visited,
+    all NaN); bit 4 a non-finite coordinate (all NaN); bit 8 degenerate circle (its five parameters NaN); bit 16
+    degenerate line (its three parameters NaN); bit 32 a hit id outside [0, n_hits) (not read, all NaN).  Bits 8 and 16
+    are decided only where none of 1, 2, 4 and 32 is set."""
+    max_hits = _check_max_hits(max_hits)
+    ptr = np.asarray(track_ptr).reshape(-1).astype(np.int64)
+    hits = np.asarray(track_hits).reshape(-1).astype(np.int64)
+    x, y, z = (np.ascontiguousarray(np.asarray(v).reshape(-1), dtype=np.float64) for v in (x, y, z))
+    if not (x.shape == y.shape == z.shape):
+        raise ValueError("x, y and z differ in size")
+    if ptr.size < 1 or ptr[0] != 0 or ptr[-1] != hits.size or np.any(np.diff(ptr) < 0):
+        raise ValueError("track_ptr must run non-decreasing from 0 to the number of track hits (%d)" % hits.size)
+    n_hits, T = x.size, ptr.size - 1
+    n = ptr[1:] - ptr[:-1]
+    status = np.where(n < 3, FIT_STATUS_FEW, 0) | np.where(n > max_hits, FIT_STATUS_MANY, 0)
+    visit = n <= max_hits
+    S = np.zeros((13, T))
+    xi, yi, ri = np.zeros(T), np.zeros(T), np.zeros(T)             # the hit of smallest r2 so far, the earlier on a tie
+    xo, yo, ro = np.zeros(T), np.zeros(T), np.zeros(T)             # the hit of largest r2
+    with np.errstate(all="ignore"):
+        for k in range(int(n[visit].max()) if np.any(visit) else 0):
+            on = np.flatnonzero(visit & (k < n))
+            h = hits[ptr[on] + k]
+            inside = (h >= 0) & (h < n_hits)
+            status[on[~inside]] |= FIT_STATUS_RANGE
+            on, h = on[inside], h[inside]
+            hx, hy, hz = x[h], y[h], z[h]
+            status[on[~(np.isfinite(hx) & np.isfinite(hy) & np.isfinite(hz))]] |= FIT_STATUS_NONFINITE
+            r2 = hx * hx + hy * hy
+            r = np.sqrt(r2)
+            for m, term in enumerate((hx, hy, hz, r2, hx * hx, hx * hy, hy * hy, hx * r2, hy * r2, r2 * r2, r, r * hz,
+                                      hz * hz)):
+                S[m, on] = S[m, on] + term
+            lo = (r2 < ri[on]) | (k == 0)
+            hi = (r2 > ro[on]) | (k == 0)
+            xi[on], yi[on], ri[on] = np.where(lo, hx, xi[on]), np.where(lo, hy, yi[on]), np.where(lo, r2, ri[on])
+            xo[on], yo[on], ro[on] = np.where(hi, hx, xo[on]), np.where(hi, hy, yo[on]), np.where(hi, r2, ro[on])
+        nf = n.astype(np.float64)
+        mx, my, mz, mr2, mxx, mxy, myy, mxr, myr, mrr, mr, mrz, mzz = (S[m] / nf for m in range(13))
+        Cxx, Cxy, Cyy = mxx - mx * mx, mxy - mx * my, myy - my * my
+        Cxr, Cyr, Crr = mxr - mx * mr2, myr - my * mr2, mrr - mr2 * mr2
+        a = 2.0 * (Crr * Cxy - Cxr * Cyr)
+        b = Crr * (Cxx - Cyy) - Cxr * Cxr + Cyr * Cyr
+        h = np.sqrt(a * a + b * b)
+        cp = np.sqrt((1.0 + b / h) / 2.0)                          # b >= 0: the cosine first
+        sp = (a / h) / (2.0 * cp)
+        sq = np.sqrt((1.0 - b / h) / 2.0)                          # b < 0: the sine first, with the sign of a
+        sn = np.where(a >= 0, sq, -sq)
+        cn = (a / h) / (2.0 * sn)
+        c, s = np.where(b >= 0, cp, cn), np.where(b >= 0, sp, sn)
+        flip = c * (xo - xi) + s * (yo - yi) < 0
+        c, s = np.where(flip, -c, c), np.where(flip, -s, s)
+        kappa = (s * Cxr - c * Cyr) / Crr
+        delta = -kappa * mr2 + s * mx - c * my
+        w = 1.0 - 4.0 * delta * kappa
+        u = np.sqrt(w)
+        rho = 2.0 * kappa / u
+        d = 2.0 * delta / (1.0 + u)
+        f = 1.0 + rho * d
+        chi2c = nf * f * f * (s * s * Cxx - 2.0 * s * c * Cxy + c * c * Cyy - kappa * kappa * Crr)
+        Crz, Cr, Czz = mrz - mr * mz, mr2 - mr * mr, mzz - mz * mz
+        cot = Crz / Cr
+        z0 = mz - cot * mr
+        chi2l = nf * (Czz - cot * Crz)
+        fit = (status & _FIT_UNFIT) == 0
+        status |= np.where(fit & ~((Crr > 0) & (h > 0) & (w > 0)), FIT_STATUS_CIRCLE, 0)
+        status |= np.where(fit & ~(Cr > 0), FIT_STATUS_LINE, 0)
+    nan = np.float64("nan")
+    no_circle = (status & (_FIT_UNFIT | FIT_STATUS_CIRCLE)) != 0
+    no_line = (status & (_FIT_UNFIT | FIT_STATUS_LINE)) != 0
+    params = np.stack([np.where(no_circle, nan, v) for v in (rho, c, s, d, chi2c)] +
+                      [np.where(no_line, nan, v) for v in (cot, z0, chi2l)], axis=1) if T else np.zeros((0, 8))
+    moments = np.where(((status & _FIT_BLANK) != 0)[:, None], nan, S.T)
+    return {"moments": np.ascontiguousarray(moments), "params": np.ascontiguousarray(params),
+            "n_hits": n.astype(np.int32), "status": status.astype(np.int32)}
+
+
+def xy_from_polar(r, phi):
+    """float64 (x, y) = (r cos phi, r sin phi) of select_hits' columns, after the cast to float64; tensors stay tensors
+    on their device, anything else comes back as numpy."""
+    if torch.is_tensor(r) or torch.is_tensor(phi):
+        r, phi = (torch.as_tensor(v).to(torch.float64) for v in (r, phi))
+        return r * torch.cos(phi), r * torch.sin(phi)
+    r, phi = np.asarray(r, dtype=np.float64), np.asarray(phi, dtype=np.float64)
+    return r * np.cos(phi), r * np.sin(phi)
+
+
+class TrackFit:
+    """The fit of every track of a batch (`Tracks.fit`), on the tracks' device: `moments` float64 [n_tracks, 13]
+    (FIT_MOMENTS), `params` float64 [n_tracks, 8] (FIT_PARAMS), `n_hits` and `status` int32 [n_tracks] (0: fitted, see
+    `fit_tracks_numpy`).  Views of params: `curvature` (1/mm, > 0 bends clockwise), `direction` [n_tracks, 2] (the unit
+    vector at the point of closest approach), `d0`, `z0` (mm), `cot_theta`, `chi2_circle`, `chi2_line` (mm^2).  `phi`
+    and `pt()` are derived by torch ops."""
+
+    def __init__(self, moments, params, n_hits, status):
+        self.moments, self.params, self.n_hits, self.status = moments, params, n_hits, status
+
+    curvature = property(lambda self: self.params[:, 0])
+    direction = property(lambda self: self.params[:, 1:3])
+    d0 = property(lambda self: self.params[:, 3])
+    chi2_circle = property(lambda self: self.params[:, 4])
+    cot_theta = property(lambda self: self.params[:, 5])
+    z0 = property(lambda self: self.params[:, 6])
+    chi2_line = property(lambda self: self.params[:, 7])
+
+    @property
+    def phi(self):
+        """The direction's angle, atan2(s, c)."""
+        return torch.atan2(self.params[:, 2], self.params[:, 1])
+
+    def pt(self, b_field_tesla=2.0):
+        """Transverse momentum in GeV for lengths in mm: 2.99792458e-4 B / |rho|; inf for a straight track, NaN where
+        the circle was not fitted."""
+        return PT_GEV_PER_TESLA_MM * float(b_field_tesla) / self.curvature.abs()
+
+    def good(self, max_chi2_circle_per_hit, max_chi2_line_per_hit, min_hits=3):
+        """bool [n_tracks]: status 0, at least min_hits hits, chi2_circle <= max_chi2_circle_per_hit * n and
+        chi2_line <= max_chi2_line_per_hit * n."""
+        n = self.n_hits.to(torch.float64)
+        return ((self.status == 0) & (self.n_hits >= int(min_hits))
+                & (self.chi2_circle <= float(max_chi2_circle_per_hit) * n)
+                & (self.chi2_line <= float(max_chi2_line_per_hit) * n))
+
+
 def _status_error(status):
     return ValueError("track builder status %d (%s)" % (status, "; ".join(w for b, w in _STATUS_WORDS if status & b)
                                                          or "unknown bits"))
@@ -189,9 +344,22 @@ class TrackMatch:
     particles, reconstructable particles found - on the device of the tracks.  The counts add across batches, and
     across ranks with one all_reduce.  `efficiency` and `fake_rate` read the counts back."""
 
-    def __init__(self, majority_particle, majority_hits, particle_hits, matched, counts):
+    def __init__(self, majority_particle, majority_hits, particle_hits, matched, counts, min_hits=3):
         self.majority_particle, self.majority_hits = majority_particle, majority_hits
         self.particle_hits, self.matched, self.counts = particle_hits, matched, counts
+        self.min_hits = int(min_hits)
+
+    def select(self, mask):
+        """The counts of the tracks where `mask` (bool [n_tracks], a TrackFit.good(...) say) is true: int64 [4] =
+        selected tracks, matched ones among them, the reconstructable particles (unchanged), those of them found by a
+        selected track.  `rates(match.select(mask))` is the efficiency and fake rate after the cut.  Torch ops on the
+        tracks' device, nothing read back."""
+        mask = torch.as_tensor(mask).to(device=self.matched.device, dtype=torch.bool).reshape(-1)
+        if mask.shape != self.matched.shape:
+            raise ValueError("the mask has %d entries, there are %d tracks" % (mask.numel(), self.matched.numel()))
+        hit = self.matched & mask
+        return torch.stack([mask.sum(), hit.sum(), self.counts[2].to(torch.int64),
+                            (hit & (self.particle_hits >= self.min_hits)).sum()])
 
     @staticmethod
     def rates(counts):
@@ -269,11 +437,30 @@ class Tracks:
             pid = torch.as_tensor(particle_id).reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
             maj, mh, ph, matched, counts = _lib.track_match(self.track_of_hit, pid, self._hit_ptr_dev, self.track_ptr,
                                                             n_tracks, self.min_hits)
-            return TrackMatch(maj, mh, ph, matched.to(torch.bool), counts)
+            return TrackMatch(maj, mh, ph, matched.to(torch.bool), counts, self.min_hits)
         spec = match_tracks_numpy(self.track_of_hit.numpy(), n_tracks, _host(particle_id), self.hit_ptr, self.min_hits)
         t = torch.from_numpy
         return TrackMatch(t(spec["majority_particle"]), t(spec["majority_hits"]), t(spec["particle_hits"]),
-                          t(spec["matched"]), t(spec["counts"]))
+                          t(spec["matched"]), t(spec["counts"]), self.min_hits)
+
+    def fit(self, x, y, z, max_hits=32):
+        """Fit every track: x, y, z [n_hits] in the batch's hit order, in mm (col[batch.hit_index] for a batch of
+        build_graphs; `xy_from_polar` makes x, y of select_hits' r, phi), tensors or numpy, float32 or float64.  CUDA
+        tracks run csrc/track_fit.hip, CPU tracks `fit_tracks_numpy`; tracks of more than `max_hits` hits are flagged,
+        not fitted.  Returns a TrackFit."""
+        max_hits = _check_max_hits(max_hits)
+        for name, v in (("x", x), ("y", y), ("z", z)):
+            n = int(v.numel() if torch.is_tensor(v) else np.asarray(v).size)
+            if n != self.n_hits:
+                raise ValueError("%s has %d entries, the batch %d hits" % (name, n, self.n_hits))
+        track_ptr, track_hits = self.track_ptr, self.track_hits          # (the one read-back, if not yet made)
+        if self.track_of_hit.is_cuda:
+            from . import _lib
+            cols = [torch.as_tensor(v).reshape(-1).to(device=self.device, dtype=torch.float64).contiguous()
+                    for v in (x, y, z)]
+            return TrackFit(*_lib.track_fit(track_ptr, track_hits, *cols, max_hits))
+        spec = fit_tracks_numpy(track_ptr.numpy(), track_hits.numpy(), _host(x), _host(y), _host(z), max_hits)
+        return TrackFit(*(torch.from_numpy(spec[k]) for k in ("moments", "params", "n_hits", "status")))
 
 
 def build_tracks(batch, scores, threshold=0.5, mode="components", min_hits=3):

@@ -737,6 +737,33 @@ int gnn_track_match(const int32_t *track_of_hit, const int64_t *particle_id, int
                     size_t workspace_bytes, int64_t *majority_particle, int32_t *majority_hits, int32_t *particle_hits,
                     int32_t *matched, int64_t *counts, void *stream);
 
+/* ---- the fit of track candidates: curvature, impact parameter, z0, chi2 per track (csrc/track_fit.hip; ABI 7) --------
+ * The reference has no counterpart: it ends at segment scores, and a track candidate of gnn_track_build_lists is a
+ * list of hit ids.  gnn-fpga_amd/tracks.py fit_tracks_numpy is the specification and the kernel restates it operation
+ * for operation in float64 without contraction: every output equals it bit for bit.
+ * Track t owns track_hits[track_ptr[t] .. track_ptr[t+1]) (int32, as gnn_track_build_lists writes them), visited in
+ * that order; x, y, z double [n_hits] in mm, in the batch's hit order; all DEVICE memory.  Per hit r2 = x x + y y,
+ * r = sqrt(r2); every sum runs over the track's hits in list order from 0.0.
+ *   moments [n_tracks, 13]  the sums of x, y, z, r2, x x, x y, y y, x r2, y r2, r2 r2, r, r z, z z
+ *   params  [n_tracks, 8]   rho, c, s, d, chi2_circle - Karimaki's non-iterative circle fit (NIM A305 (1991) 187),
+ *                           unweighted: curvature, the direction (cos, sin) at the point of closest approach (d s, -d c),
+ *                           oriented from the hit of smallest r2 to the one of largest, the signed distance of closest
+ *                           approach; rho > 0 bends clockwise - and cot, z0, chi2_line of the straight line
+ *                           z = z0 + cot r (gnn/graph.py's z0 variable, not the arc-length fit of a helix)
+ *   n_fit   [n_tracks]      int32, the track's number of hits
+ *   status  [n_tracks]      int32, 0 = fitted; bit 1 fewer than 3 hits (moments only, params NaN); 2 more than max_hits
+ *                           hits (not visited, all NaN); 4 a coordinate that is not finite (all NaN); 8 a degenerate
+ *                           circle (its five parameters NaN); 16 a degenerate line (its three NaN); 32 a hit id outside
+ *                           [0, n_hits), not read, or a track_ptr pair that leaves track_hits (all NaN).  8 and 16 are
+ *                           decided only where 1, 2, 4 and 32 are clear.
+ * max_hits is part of the definition: one lane owns one track, and the components of 10 k hits that
+ * GNN_TRACKS_COMPONENTS can make are not tracks.  Asynchronous on `stream`, caller-allocated outputs, no workspace,
+ * nothing read back; n_tracks == 0 returns 0 without a launch.  GNN_ERR_BADARG names the argument: sizes negative or
+ * >= 2^31, max_hits < 3, a missing pointer with a non-zero size. */
+int gnn_track_fit(const int32_t *track_ptr, const int32_t *track_hits, int64_t n_tracks, int64_t n_track_hits,
+                  const double *x, const double *y, const double *z, int64_t n_hits, int32_t max_hits, double *moments,
+                  double *params, int32_t *n_fit, int32_t *status, void *stream);
+
 /* ---- graph-convolution classifiers (csrc/gcn.hip; ABI 7) ------------------------------------------------------------
  * Stand in for GraphConv / GraphConvSelfInt (gnn/GCN_Seg_Toy2D.ipynb cell 20, gnn/GCN_Toy2D.ipynb cell 11),
  * GCNBinaryClassifier (Seg cell 21, Toy2D cell 13) and GCRNBinaryClassifier (Toy2D cell 14), which multiply a dense
