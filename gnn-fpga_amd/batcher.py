@@ -24,7 +24,7 @@ y - what `load_graphs(filenames, SparseGraph)` returns, gnn/graph.py:188-194) or
 import numpy as np
 import torch
 
-from .hitgraph import HitGraphBatch
+from .hitgraph import HitGraphBatch, check_ends, graph_sizes
 from .synth import HitGraph
 
 
@@ -46,17 +46,19 @@ def as_hit_graph(g):
                     None if y is None else np.asarray(y, dtype=np.float32))
 
 
-def merge_graphs(graphs, layout="padded"):
+def merge_graphs(graphs, layout="padded", first=0, n_features=None):
     """One batch from a list of graphs, composition order = list order (reference
     gnn/trainSegmentClassifier.py:66-95).  Returns (HitGraphBatch, y) with y float32 of shape
-    [B, E_max] (padded) or [E_total] (flat), or None when a graph has no labels."""
+    [B, E_max] (padded) or [E_total] (flat), or None when a graph has no labels.  A malformed graph is
+    refused with a ValueError naming it (`first`: where graphs[0] stands in the caller's dataset;
+    `n_features`: the dataset's feature count, default graphs[0]'s)."""
     gs = [as_hit_graph(g) for g in graphs]
     if layout == "flat":
-        b = HitGraphBatch.from_graphs(gs)
+        b = HitGraphBatch.from_graphs(gs, first=first, n_features=n_features)
         return b, (None if b.y is None else b.y.clone())
     if layout != "padded":
         raise ValueError("layout must be 'padded' or 'flat'")
-    b = HitGraphBatch.from_graphs(gs, pad_segments=True)
+    b = HitGraphBatch.from_graphs(gs, pad_segments=True, first=first, n_features=n_features)
     return b, (None if b.y is None else b.y.view(b.dense_shape[0], b.dense_shape[2]).clone())
 
 
@@ -71,32 +73,35 @@ class GraphStore:
     thousand events is tens of GB in index form - it fits the 288 GB of one MI355X many times over.
 
     `batch(j, batch_size, layout)` = the reference's `graphs[j:j + batch_size]` in list order (`layout` as in
-    `merge_graphs`); endpoints are checked once, graph by graph, when the store is built (works on CPU tensors too:
-    that is how the CPU tests hold it equal to `HitGraphBatch.from_graphs`)."""
+    `merge_graphs`); every graph is checked once, when the store is built, by the checks of `from_graphs` (X width,
+    integer endpoints below n_hits and negative only in pairs - stored as (-1, -1) -, len(y)): a ValueError names the
+    graph, on the host, before anything is uploaded (works on CPU tensors too: that is how the CPU tests hold it equal
+    to `HitGraphBatch.from_graphs`)."""
 
     def __init__(self, graphs, device=None):
         gs = [as_hit_graph(g) for g in graphs]
         self.n_graphs = len(gs)
         hp = np.zeros(self.n_graphs + 1, dtype=np.int64)
         sp = np.zeros(self.n_graphs + 1, dtype=np.int64)
-        for i, g in enumerate(gs):
-            hp[i + 1] = hp[i] + g.X.shape[0]
-            sp[i + 1] = sp[i] + np.asarray(g.src).shape[0]
+        shape0 = np.shape(gs[0].X) if gs else (0, 0)
+        n_feat = int(shape0[1]) if len(shape0) == 2 else None
+        for i, g in enumerate(gs):                       # X width, endpoint dtype, len(y): refused here, by name
+            n_g, e = graph_sizes(i, g, n_feat)
+            hp[i + 1], sp[i + 1] = hp[i] + n_g, sp[i] + e
         self.hit_ptr, self.seg_ptr = hp, sp
         src = np.empty(int(sp[-1]), dtype=np.int32)
         dst = np.empty(int(sp[-1]), dtype=np.int32)
         for i, g in enumerate(gs):                       # local ids, checked while the graph is in cache
             a, b = np.asarray(g.src), np.asarray(g.dst)
-            if a.ndim != 1 or a.shape != b.shape:
-                raise ValueError("expected src [E], dst [E]")
             if a.shape[0] == 0:
                 continue
-            if int(a.max()) >= g.X.shape[0] or int(b.max()) >= g.X.shape[0]:
-                raise ValueError("segment endpoint out of range")
-            if (int(a.min()) < 0 or int(b.min()) < 0) and np.any((a < 0) != (b < 0)):
-                raise ValueError("a padded segment must have src = dst = -1")
+            own_padding = check_ends(i, a, b, int(hp[i + 1] - hp[i]))
             src[sp[i]:sp[i + 1]] = a
             dst[sp[i]:sp[i + 1]] = b
+            if own_padding:                              # any negative pair is (-1, -1), as in from_graphs
+                pa = a < 0
+                src[sp[i]:sp[i + 1]][pa] = -1
+                dst[sp[i]:sp[i + 1]][pa] = -1
         ys = [getattr(g, "y", None) for g in gs]
         t = torch.from_numpy
         dev = torch.device("cpu") if device is None else torch.device(device)
@@ -146,9 +151,14 @@ class GraphStore:
         return store
 
     def batch(self, j, batch_size=1, layout="padded"):
-        """(HitGraphBatch, y) of graphs j ... j + batch_size - 1, like `merge_graphs(graphs[j:j + batch_size], layout)`."""
+        """(HitGraphBatch, y) of graphs j ... j + batch_size - 1, like `merge_graphs(graphs[j:j + batch_size], layout)`.
+        The window is the slice `graphs[j:j + batch_size]`: it ends where the dataset ends, and one that starts there or
+        beyond is a batch without graphs (`n_graphs == 0`), not an error."""
         if layout not in ("padded", "flat"):
             raise ValueError("layout must be 'padded' or 'flat'")
+        if j < 0 or batch_size < 0:
+            raise ValueError("a window starts at j >= 0 and takes batch_size >= 0 graphs")
+        j = min(j, self.n_graphs)
         j1 = min(j + batch_size, self.n_graphs)
         B = j1 - j
         hp = self.hit_ptr[j:j1 + 1] - self.hit_ptr[j]
@@ -206,18 +216,36 @@ def batch_generator(graphs, n_samples=1, batch_size=1, train=True, device=None, 
     plans and level-ordered twins with them - while the estimated bytes they pin (`_batch_bytes`: twin
     and plans included) stay under `max_cached_bytes` (default 8 GiB of the 288); what does not fit is
     rebuilt each epoch and holds nothing between uses, like every batch of the reference's generator
-    (`cache=False`)."""
+    (`cache=False`).
+    Batch b of an epoch is the slice `graphs[j:j + batch_size]`, j = b * batch_size < n_samples, from a list and from a
+    `GraphStore` alike: `n_samples` decides where windows START, the last one is not clipped to it (it ends with
+    the dataset).  A configuration with a window that holds no graph (the reference fails in its merge_graphs
+    there), `n_samples < 1` or `batch_size < 1` is refused with a ValueError when the generator is made."""
     del train
-    idxs = np.arange(0, n_samples, batch_size)
+    n_graphs = graphs.n_graphs if isinstance(graphs, GraphStore) else len(graphs)
+    if n_samples < 1 or batch_size < 1:
+        raise ValueError("batch_generator needs n_samples >= 1 and batch_size >= 1, got %r and %r"
+                         % (n_samples, batch_size))
+    if ((n_samples - 1) // batch_size) * batch_size >= n_graphs:           # the start of the epoch's last window
+        raise ValueError("n_samples=%d, batch_size=%d: the window at graph %d holds none of the %d graphs"
+                         % (n_samples, batch_size, -(-n_graphs // batch_size) * batch_size, n_graphs))
+    return _batches(graphs, np.arange(0, n_samples, batch_size), batch_size, device, layout, cache, max_cached_bytes)
+
+
+def _batches(graphs, idxs, batch_size, device, layout, cache, max_cached_bytes):
+    width = None
+    if not isinstance(graphs, GraphStore):                # a list: every window holds the width of the DATASET's graph 0
+        shape0 = np.shape(graphs[0].X)
+        width = int(shape0[1]) if len(shape0) == 2 else None
     kept, kept_bytes = {}, 0
     while True:
         for j in idxs:
             item = kept.get(int(j))
             if item is None:
                 if isinstance(graphs, GraphStore):        # assembled where the dataset lives
-                    b, y = graphs.batch(int(j), min(batch_size, n_samples - int(j)), layout)
+                    b, y = graphs.batch(int(j), batch_size, layout)
                 else:
-                    b, y = merge_graphs(graphs[j:j + batch_size], layout)
+                    b, y = merge_graphs(graphs[j:j + batch_size], layout, first=int(j), n_features=width)
                 if device is not None:
                     b = b.to(device)
                     y = None if y is None else y.to(device)

@@ -56,6 +56,36 @@ def _csr_by_device(key, other, n_hits):
     return ptr.to(torch.int32), eid.to(torch.int32), other[eid].to(torch.int32)
 
 
+def graph_sizes(i, g, n_feat=None):
+    """(hits, segments) of graph `i` of a list, after the checks that need no pass over its arrays: X [N, F] of the
+    list's width (`n_feat`: graph 0's), src / dst [E] of an integer dtype (a float array would be cast silently), and
+    y - where the graph has labels - [E].  A ValueError names the graph; `from_graphs` and `batcher.GraphStore`
+    both go through here, so neither lets numpy broadcast, truncate or leave unwritten what does not fit."""
+    X, a, b = np.asarray(g.X), np.asarray(g.src), np.asarray(g.dst)
+    if X.ndim != 2 or (n_feat is not None and X.shape[1] != n_feat):
+        raise ValueError("graph %d: expected X [N, %s], got %s" % (i, "F" if n_feat is None else n_feat, X.shape))
+    if a.ndim != 1 or a.shape != b.shape:
+        raise ValueError("graph %d: expected src [E], dst [E], got %s and %s" % (i, a.shape, b.shape))
+    if not (np.issubdtype(a.dtype, np.integer) and np.issubdtype(b.dtype, np.integer)):
+        raise ValueError("graph %d: src / dst must be integer arrays, got %s and %s" % (i, a.dtype, b.dtype))
+    y = getattr(g, "y", None)
+    if y is not None and np.shape(y) != a.shape:
+        raise ValueError("graph %d: %d segments but y of shape %s" % (i, a.shape[0], np.shape(y)))
+    return int(X.shape[0]), int(a.shape[0])
+
+
+def check_ends(i, a, b, n_hits):
+    """Endpoints of graph `i` (ids local to it, not empty): below n_hits, negative only in pairs.  True if it has
+    such pairs - padded segments of its own - which the caller writes as (-1, -1)."""
+    if int(a.max()) >= n_hits or int(b.max()) >= n_hits:
+        raise ValueError("graph %d: segment endpoint out of range (%d hits)" % (i, n_hits))
+    if int(a.min()) >= 0 and int(b.min()) >= 0:
+        return False
+    if np.any((a < 0) != (b < 0)):
+        raise ValueError("graph %d: a padded segment must have src = dst = -1" % i)
+    return True
+
+
 class _EventLayout:
     """Per-graph offsets of a block-diagonal batch (HitGraphBatch.event_layout): max_hits, max_segments and - as
     device tensors, uploaded at first use (one copy for both; a single-graph forward never needs them) -
@@ -156,6 +186,8 @@ class HitGraphBatch(DerivedStores):
         if X.ndim != 2 or src.ndim != 1 or src.shape != dst.shape:
             raise ValueError("expected X [N,F], src [E], dst [E]")
         n = X.shape[0]
+        if y is not None and np.shape(y) != src.shape:
+            raise ValueError("%d segments but y of shape %s" % (src.shape[0], np.shape(y)))
         if not _checked:                             # (from_graphs checks graph by graph, while a graph is in cache)
             if np.any((src ^ dst) < 0):              # signs differ: exactly one end negative
                 raise ValueError("a padded segment must have src = dst = -1")
@@ -335,7 +367,7 @@ class HitGraphBatch(DerivedStores):
 
     # -- constructors ------------------------------------------------------------------
     @classmethod
-    def from_graphs(cls, graphs, pad_segments=False, pin_memory=None):
+    def from_graphs(cls, graphs, pad_segments=False, pin_memory=None, first=0, n_features=None):
         """Index-form batcher: block-diagonal concatenation.
 
         Replaces the zero-padding `merge_graphs` (reference
@@ -346,14 +378,21 @@ class HitGraphBatch(DerivedStores):
         `src = dst = -1` columns and `dense_shape = (B, N_max, E_max)` is set, so the model
         returns the reference's [B, E_max] layout (padded columns score sigmoid(W2 tanh(b1) + b2)
         and carry target 0, exactly like merge_graphs' zero columns); hits are never padded.
+        A graph whose arrays do not fit together (`graph_sizes`, `check_ends`) is refused with a ValueError that
+        names it: its place in the list plus `first`, the place of graphs[0] in the caller's dataset.
+        `n_features`: the width every X must have (default: graphs[0]'s; a dataset's batches pass the dataset's).
         """
         B = len(graphs)
         hit_ptr = np.zeros(B + 1, dtype=np.int64)
         seg_ptr = np.zeros(B + 1, dtype=np.int64)
-        e_max = max((int(np.asarray(g.src).shape[0]) for g in graphs), default=0)
-        for i, g in enumerate(graphs):
-            hit_ptr[i + 1] = hit_ptr[i] + g.X.shape[0]
-            seg_ptr[i + 1] = seg_ptr[i] + (e_max if pad_segments else g.src.shape[0])
+        shape0 = np.shape(graphs[0].X) if graphs else (0, 0)
+        n_feat = int(shape0[1]) if len(shape0) == 2 else None           # (None: graph 0 is refused for its X)
+        n_feat = n_feat if n_features is None else int(n_features)
+        sizes = [graph_sizes(first + i, g, n_feat) for i, g in enumerate(graphs)]     # (before anything is allocated)
+        e_max = max((e for _, e in sizes), default=0)
+        for i, (n_g, e) in enumerate(sizes):
+            hit_ptr[i + 1] = hit_ptr[i] + n_g
+            seg_ptr[i + 1] = seg_ptr[i] + (e_max if pad_segments else e)
         # Large batches are put together in PINNED host memory when a GPU is there to receive them (pin_memory=None:
         # from 1 M segments on; torch's caching host allocator hands the same blocks out again batch after batch): the
         # upload of 256 detector graphs then runs at the link's rate, 21 -> 6 ms.
@@ -368,7 +407,6 @@ class HitGraphBatch(DerivedStores):
                 return a
             return np.empty(shape, dtype=dtype) if fill is None else np.full(shape, fill, dtype=dtype)
 
-        n_feat = int(np.asarray(graphs[0].X).shape[1]) if graphs else 0
         X = host((int(hit_ptr[-1]), n_feat), np.float32)
         for i, g in enumerate(graphs):
             X[hit_ptr[i]:hit_ptr[i + 1]] = np.asarray(g.X, dtype=np.float32)
@@ -387,31 +425,24 @@ class HitGraphBatch(DerivedStores):
         dst = host(E_tot, _I32, -1 if pad_segments else None)
         for i, g in enumerate(graphs):
             a, b = np.asarray(g.src), np.asarray(g.dst)
-            if a.ndim != 1 or a.shape != b.shape:
-                raise ValueError("expected src [E], dst [E]")
-            e, o, off, n_g = a.shape[0], int(seg_ptr[i]), int(hit_ptr[i]), int(g.X.shape[0])
+            (n_g, e), o, off = sizes[i], int(seg_ptr[i]), int(hit_ptr[i])
             if e == 0:
                 continue
-            amin, bmin = int(a.min()), int(b.min())
-            if int(a.max()) >= n_g or int(b.max()) >= n_g:
-                raise ValueError("segment endpoint out of range")
+            own_padding = check_ends(first + i, a, b, n_g)
             np.add(a, off, out=src[o:o + e], casting="unsafe")
             np.add(b, off, out=dst[o:o + e], casting="unsafe")
-            if amin < 0 or bmin < 0:                     # padded segments of the graph itself stay -1
+            if own_padding:                              # padded segments of the graph itself stay -1
                 pa = a < 0
-                if np.any(pa != (b < 0)):
-                    raise ValueError("a padded segment must have src = dst = -1")
                 src[o:o + e][pa] = -1
                 dst[o:o + e][pa] = -1
         y = None
         if have_y:
             y = host(E_tot, np.float32, 0.0 if pad_segments else None)
-            for i, v in enumerate(ys):
-                v = np.asarray(v, dtype=np.float32)
-                y[int(seg_ptr[i]):int(seg_ptr[i]) + v.shape[0]] = v
+            for i, v in enumerate(ys):                   # (graph_sizes: exactly the graph's segment count)
+                y[int(seg_ptr[i]):int(seg_ptr[i]) + sizes[i][1]] = np.asarray(v, dtype=np.float32)
         dense_shape = None
         if pad_segments:
-            n_max = max((int(g.X.shape[0]) for g in graphs), default=0)
+            n_max = max((n_g for n_g, _ in sizes), default=0)
             dense_shape = (B, n_max, e_max)
         return cls(X, src, dst, y=y, hit_ptr=hit_ptr, seg_ptr=seg_ptr, dense_shape=dense_shape, _checked=True)
 

@@ -281,6 +281,10 @@ def round2():
                                                    for i in range(5)], n_samples=5, batch_size=2, D=8, T=3, seed=13)
     batch_generator_fixture("batchgen_muon_b4", [synth.muon_graph(20 + s) for s in range(8)],
                             n_samples=8, batch_size=4, D=8, T=3, seed=14)
+    # the reference's own tail: n_samples = 5 of SIX graphs, so its last window graphs[4:6] reaches past n_samples
+    batch_generator_fixture("batchgen_sector_tail", [synth.layered_graph(50 + 15 * i, 120 + 35 * i, 3, seed=50 + i)
+                                                     for i in range(5)] + [synth.layered_graph(125, 295, 3, seed=55)],
+                            n_samples=5, batch_size=2, D=8, T=3, seed=13)
 
 
 def estimator_fixtures():

@@ -61,7 +61,7 @@ def test_file_written_by_the_reference_loads_as_csr(kind):
     assert np.abs(ref - d["scores"]).max() < 1e-5
 
 
-@pytest.mark.parametrize("name", ["batchgen_sector_b2", "batchgen_muon_b4"])
+@pytest.mark.parametrize("name", ["batchgen_sector_b2", "batchgen_muon_b4", "batchgen_sector_tail"])
 @pytest.mark.parametrize("layout", ["padded", "flat"])
 def test_batch_generator_yields_the_reference_batches(name, layout):
     d = _fx(name)
@@ -96,7 +96,7 @@ def test_batch_generator_yields_the_reference_batches(name, layout):
     assert seen[:nb] == seen[nb:]                 # epochs reuse the batches (plans / CSRs with them)
 
 
-@pytest.mark.parametrize("name", ["batchgen_sector_b2", "batchgen_muon_b4"])
+@pytest.mark.parametrize("name", ["batchgen_sector_b2", "batchgen_muon_b4", "batchgen_sector_tail"])
 @pytest.mark.parametrize("layout", ["padded", "flat"])
 def test_graph_store_assembles_the_reference_batches(name, layout):
     """batcher.GraphStore: the dataset concatenated once (here on the CPU), every batch assembled from slices + one
