@@ -31,28 +31,10 @@
 // rows in row order, 32 rows per chunk, chunks in order: every float addition of a backward happens
 // in a fixed order, and two runs give bit-identical gradients (deterministic by default).
 #include "common.h"
+#include "lane_ops.h"
 
 namespace {
 using namespace gnn;
-
-// row of LDH floats (16-byte aligned: LDH % 4 == 0) as float4 loads
-template <int N4>
-__device__ __forceinline__ void load_row4(const float *__restrict__ row, float *v)
-{
-    const float4 *r = reinterpret_cast<const float4 *>(row);
-#pragma unroll
-    for (int i = 0; i < N4; ++i) {
-        const float4 a = r[i];
-        v[4 * i] = a.x; v[4 * i + 1] = a.y; v[4 * i + 2] = a.z; v[4 * i + 3] = a.w;
-    }
-}
-template <int N4>
-__device__ __forceinline__ void store_row4(float *__restrict__ row, const float *v)
-{
-    float4 *r = reinterpret_cast<float4 *>(row);
-#pragma unroll
-    for (int i = 0; i < N4; ++i) r[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-}
 
 // Sum over the workgroup's 256 items of L (x) [R | 1], added into g[i * ldg + col0 + k] and (the
 // ones column, gb != null) into gb[i].  The items' factors are parked in LDS TRANSPOSED - row c holds
@@ -186,7 +168,6 @@ __device__ __forceinline__ void accum_outer_mfma(const float *L, const float *R,
                                                  int ldg, int col0, float *gb, float *lds)
 {
     static_assert(NL % 16 == 0 && NL + 16 <= kOuterCap, "left factor: whole 16-row tiles");
-    typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr bool ONES = (C0 == 0);
     constexpr int ROOM = ((kOuterCap - NL) / 16) * 16 - (ONES ? 1 : 0);     // columns per chunk (tiles are whole)
     constexpr int CH = (NR - C0 <= ROOM) ? NR - C0 : ROOM, RS = kOuterStride;
@@ -203,7 +184,7 @@ __device__ __forceinline__ void accum_outer_mfma(const float *L, const float *R,
     for (int t = wv; t < RT * CT; t += kBlock / 64) {
         const int it = t / CT, jt = t % CT;
         const float *a = lds + (16 * it + r16) * RS + g4, *b = lds + (NL + 16 * jt + r16) * RS + g4;
-        f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
+        f4_t c = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 8
         for (int st = 0; st < kBlock / 4; ++st) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * st], b[4 * st], c, 0, 0, 0);
         const int col = 16 * jt + r16;
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(kBlock) void kb_pq(const float *__restrict__ H, int
     const int64_t n = xcd_block() * kBlock + threadIdx.x;
     if (n >= n_hits) return;
     float h[Shape<F, D>::LDH], pq[2 * D];
-    load_row4<Shape<F, D>::LDH / 4>(H + n * ldh, h);
+    load_vec<Shape<F, D>::LDH>(H + n * ldh, h);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         float p = b1[d], q = 0.0f;
@@ -242,7 +223,7 @@ __global__ __launch_bounds__(kBlock) void kb_pq(const float *__restrict__ H, int
         pq[d] = p;
         pq[D + d] = q;
     }
-    store_row4<2 * D / 4>(PQ + n * 2 * D, pq);
+    store_vec<2 * D>(PQ + n * 2 * D, pq);
 }
 
 // Per-segment kernels are grid-stride with a bounded grid: every thread keeps private sums of its
@@ -289,10 +270,10 @@ __global__ __launch_bounds__(kBlock) void k_edge_bwd(
             gej = ge[j];
         } else if (s >= 0) {
             float hs[LDH], hd[LDH], gmi_d[LDH], gmo_s[LDH];
-            load_row4<LDH / 4>(H + (int64_t)s * LDH, hs);
-            load_row4<LDH / 4>(H + (int64_t)d * LDH, hd);
-            load_row4<LDH / 4>(gmio + (int64_t)d * 2 * LDH, gmi_d);
-            load_row4<LDH / 4>(gmio + (int64_t)s * 2 * LDH + LDH, gmo_s);
+            load_vec<LDH>(H + (int64_t)s * LDH, hs);
+            load_vec<LDH>(H + (int64_t)d * LDH, hd);
+            load_vec<LDH>(gmio + (int64_t)d * 2 * LDH, gmi_d);
+            load_vec<LDH>(gmio + (int64_t)s * 2 * LDH + LDH, gmo_s);
 #pragma unroll
             for (int c = 0; c < C; ++c) gej = fmaf(gmi_d[c], hs[c], gej);
 #pragma unroll
@@ -372,7 +353,7 @@ __global__ __launch_bounds__(kBlock) void k_pq_bwd(
         // (E x D floats through HBM, twice)
         constexpr int U = D <= 16 ? 4 : 2;
         float own[2 * D], w2[D];
-        load_row4<2 * D / 4>(PQ + n * 2 * D, own);
+        load_vec<2 * D>(PQ + n * 2 * D, own);
 #pragma unroll
         for (int i = 0; i < D; ++i) w2[i] = W2[i];
         csr_walk<D / 4, U>(out_ptr[n], out_ptr[n + 1],
@@ -396,8 +377,8 @@ __global__ __launch_bounds__(kBlock) void k_pq_bwd(
                                }
                            });
         float hr[LDH], gh[LDH];
-        load_row4<LDH / 4>(H + n * ldh, hr);
-        load_row4<LDH / 4>(gH + n * ldh, gh);
+        load_vec<LDH>(H + n * ldh, hr);
+        load_vec<LDH>(gH + n * ldh, gh);
 #pragma unroll
         for (int k = 0; k < C; ++k) h[k] = hr[k];
 #pragma unroll
@@ -410,7 +391,7 @@ __global__ __launch_bounds__(kBlock) void k_pq_bwd(
             }
             gh[k] += acc;
         }
-        store_row4<LDH / 4>(gH + n * ldh, gh);
+        store_vec<LDH>(gH + n * ldh, gh);
     }
     if constexpr (2 * D + C + 1 <= kOuterJobRows) {
         accum_outer2<D, C>(gP, gQ, h, active, gW1, 2 * C, 0, C, gb1, lds);
@@ -463,7 +444,7 @@ __global__ __launch_bounds__(kBlock) void k_node_bwd(
                              });
         {
             float hp[LDH];
-            load_row4<LDH / 4>(H + n * ldh, hp);
+            load_vec<LDH>(H + n * ldh, hp);
 #pragma unroll
             for (int c = 0; c < C; ++c) M[2 * C + c] = hp[c];
         }
@@ -476,8 +457,8 @@ __global__ __launch_bounds__(kBlock) void k_node_bwd(
         }
         {
             float hn[D], gn[D];
-            load_row4<D / 4>(Hn + n * ldh, hn);
-            load_row4<D / 4>(gHn + n * ldh, gn);
+            load_vec<D>(Hn + n * ldh, hn);
+            load_vec<D>(gHn + n * ldh, gn);
 #pragma unroll
             for (int i = 0; i < D; ++i) gr[i] = gn[i] * (1.0f - hn[i] * hn[i]);
         }
@@ -498,9 +479,9 @@ __global__ __launch_bounds__(kBlock) void k_node_bwd(
             for (int i = 0; i < D; ++i) acc = fmaf(W3[i * 3 * C + k], gp[i], acc);
             gm[k / C][k % C] = acc;
         }
-        store_row4<LDH / 4>(gmio + n * 2 * LDH, gm[0]);          // [gmi | gmo], rows of LDH
-        store_row4<LDH / 4>(gmio + n * 2 * LDH + LDH, gm[1]);
-        store_row4<LDH / 4>(gH + n * ldh, gm[2]);                // gHself initialises gH_prev
+        store_vec<LDH>(gmio + n * 2 * LDH, gm[0]);          // [gmi | gmo], rows of LDH
+        store_vec<LDH>(gmio + n * 2 * LDH + LDH, gm[1]);
+        store_vec<LDH>(gH + n * ldh, gm[2]);                // gHself initialises gH_prev
     }
     accum_outer<D, 3 * C>(gp, M, active, gW3, 3 * C, 0, gb3, lds);
     accum_outer<D, D>(gr, q, active, gW4, D, 0, gb4, lds);
@@ -518,7 +499,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_bwd_n(
     const int64_t n = xcd_block() * kBlock + threadIdx.x;
     if (n >= n_hits) return;
     float acc[LDH];
-    load_row4<LDH / 4>(gH + n * ldh, acc);
+    load_vec<LDH>(gH + n * ldh, acc);
     float sum[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) sum[c] = 0.0f;
@@ -537,7 +518,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_bwd_n(
                          [&](int k) { return e[in_eid[k]]; }, add);
 #pragma unroll
     for (int c = 0; c < C; ++c) acc[c] += sum[c];
-    store_row4<LDH / 4>(gH + n * ldh, acc);
+    store_vec<LDH>(gH + n * ldh, acc);
 }
 
 template <int F, int D>
@@ -613,14 +594,13 @@ __global__ __launch_bounds__(kBlock) void kb_prs(const float *__restrict__ H, in
         }
         a[i] = pp; a[D + i] = rr; b[i] = qq; b[D + i] = ss;
     }
-    store_row4<2 * D / 4>(A + n * 3 * D, a);
-    store_row4<2 * D / 4>(B + n * 3 * D, b);
+    store_vec<2 * D>(A + n * 3 * D, a);
+    store_vec<2 * D>(B + n * 3 * D, b);
 }
 
-template <int F, int D, bool KEPT>
+template <int F, int D>
 __global__ __launch_bounds__(kBlock) void k_hit_bwd(
-    const float *__restrict__ H, const float *__restrict__ Hn, const float *__restrict__ Qk, int ldh,
-    const float *__restrict__ e,
+    const float *__restrict__ H, const float *__restrict__ Hn, int ldh, const float *__restrict__ e,
     const int32_t *__restrict__ in_ptr, const int32_t *__restrict__ in_eid, const int32_t *__restrict__ in_nbr,
     const int32_t *__restrict__ out_ptr, const int32_t *__restrict__ out_eid, const int32_t *__restrict__ out_nbr,
     const float *__restrict__ W3, const float *__restrict__ b3, const float *__restrict__ W4,
@@ -642,36 +622,32 @@ __global__ __launch_bounds__(kBlock) void k_hit_bwd(
     for (int i = 0; i < D; ++i) q[i] = gr[i] = gp[i] = 0.0f;
     if (active) {
         float hp[LDH];
-        load_row4<LDH / 4>(H + n * ldh, hp);
+        load_vec<LDH>(H + n * ldh, hp);
 #pragma unroll
         for (int k = 0; k < C; ++k) h[k] = hp[k];
-        if constexpr (KEPT) {
-            load_row4<D / 4>(Qk + n * D, q);                     // kept by the training forward (k_node)
-        } else {
-            float acc[D];
-    #pragma unroll
-            for (int i = 0; i < D; ++i) {
-                float u = b3[i];
-    #pragma unroll
-                for (int k = 0; k < C; ++k) u = fmaf(W3[i * 3 * C + 2 * C + k], h[k], u);
-                acc[i] = u;
-            }
-            auto add = [&](float w, const float *r) {
-    #pragma unroll
-                for (int i = 0; i < D; ++i) acc[i] = fmaf(w, r[i], acc[i]);
-            };
-            csr_walk<D / 4, 4>(in_ptr[n], in_ptr[n + 1],
-                               [&](int k) { return A + (int64_t)in_nbr[k] * 3 * D + D; },            // R[s]
-                               [&](int k) { return e[in_eid[k]]; }, add);
-            csr_walk<D / 4, 4>(out_ptr[n], out_ptr[n + 1],
-                               [&](int k) { return B + (int64_t)out_nbr[k] * 3 * D + D; },           // S[d]
-                               [&](int k) { return e[out_eid[k]]; }, add);
-    #pragma unroll
-            for (int i = 0; i < D; ++i) q[i] = tanh_f(acc[i]);
+        float acc[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            float u = b3[i];
+#pragma unroll
+            for (int k = 0; k < C; ++k) u = fmaf(W3[i * 3 * C + 2 * C + k], h[k], u);
+            acc[i] = u;
         }
+        auto add = [&](float w, const float *r) {
+#pragma unroll
+            for (int i = 0; i < D; ++i) acc[i] = fmaf(w, r[i], acc[i]);
+        };
+        csr_walk<D / 4, 4>(in_ptr[n], in_ptr[n + 1],
+                           [&](int k) { return A + (int64_t)in_nbr[k] * 3 * D + D; },            // R[s]
+                           [&](int k) { return e[in_eid[k]]; }, add);
+        csr_walk<D / 4, 4>(out_ptr[n], out_ptr[n + 1],
+                           [&](int k) { return B + (int64_t)out_nbr[k] * 3 * D + D; },           // S[d]
+                           [&](int k) { return e[out_eid[k]]; }, add);
+#pragma unroll
+        for (int i = 0; i < D; ++i) q[i] = tanh_f(acc[i]);
         float hn[D], gn[D];
-        load_row4<D / 4>(Hn + n * ldh, hn);
-        load_row4<D / 4>(gHn + n * ldh, gn);
+        load_vec<D>(Hn + n * ldh, hn);
+        load_vec<D>(gHn + n * ldh, gn);
 #pragma unroll
         for (int i = 0; i < D; ++i) gr[i] = gn[i] * (1.0f - hn[i] * hn[i]);
 #pragma unroll
@@ -691,13 +667,13 @@ __global__ __launch_bounds__(kBlock) void k_hit_bwd(
             for (int i = 0; i < D; ++i) s = fmaf(W3[i * 3 * C + 2 * C + k], gp[i], s);
             gh[k] = s;
         }
-        store_row4<LDH / 4>(gH + n * ldh, gh);                     // gHself initialises gH_prev
+        store_vec<LDH>(gH + n * ldh, gh);                     // gHself initialises gH_prev
     }
     // every lane has finished READING neighbours' R / S before anyone writes its gp next to them?
     // R / S and gp are different words of a record: no ordering is needed.
     if (active) {
-        store_row4<D / 4>(A + n * 3 * D + 2 * D, gp);
-        store_row4<D / 4>(B + n * 3 * D + 2 * D, gp);
+        store_vec<D>(A + n * 3 * D + 2 * D, gp);
+        store_vec<D>(B + n * 3 * D + 2 * D, gp);
     }
     accum_outer<D, C>(gp, h, active, gW3, 3 * C, 2 * C, gb3, lds);
     accum_outer<D, D>(gr, q, active, gW4, D, 0, gb4, lds);
@@ -730,8 +706,8 @@ __global__ __launch_bounds__(kBlock) void k_seg_bwd(
     for (int k = 0; k < C; ++k) h[k] = 0.0f;
     if (active) {
         float a[3 * D], b[3 * D], w2[D];                 // own [P | R | gp], [Q | S | gp]
-        load_row4<3 * D / 4>(A + n * 3 * D, a);
-        load_row4<3 * D / 4>(B + n * 3 * D, b);
+        load_vec<3 * D>(A + n * 3 * D, a);
+        load_vec<3 * D>(B + n * 3 * D, b);
 #pragma unroll
         for (int i = 0; i < D; ++i) w2[i] = W2[i];
         constexpr int U = 2;                             // (4 rows of 3D floats in flight cost half the occupancy)
@@ -774,8 +750,8 @@ __global__ __launch_bounds__(kBlock) void k_seg_bwd(
                                    sw2[D] += gu;
                                });
         float hr[LDH], gh[LDH];
-        load_row4<LDH / 4>(H + n * ldh, hr);
-        load_row4<LDH / 4>(gH + n * ldh, gh);
+        load_vec<LDH>(H + n * ldh, hr);
+        load_vec<LDH>(gH + n * ldh, gh);
 #pragma unroll
         for (int k = 0; k < C; ++k) h[k] = hr[k];
 #pragma unroll
@@ -790,7 +766,7 @@ __global__ __launch_bounds__(kBlock) void k_seg_bwd(
             }
             gh[k] += s;
         }
-        store_row4<LDH / 4>(gH + n * ldh, gh);
+        store_vec<LDH>(gH + n * ldh, gh);
     }
     accum_outer<D, C>(gP, h, active, gW1, 2 * C, 0, gb1, lds);
     accum_outer<D, C>(gQ, h, active, gW1, 2 * C, C, nullptr, lds);
@@ -827,49 +803,6 @@ __global__ __launch_bounds__(kBlock) void k_seg_bwd(
 //   k_hit_bwd4  per hit (1 lane): P R Q S from H, gp from the kept q -> A, B;  gH_prev = W3c^T gp; gW3c, gb3, gW4, gb4
 //   k_seg_bwd4  per hit (4 lanes): both list walks -> G4 = [gP gQ Gout Gin];  gW2, gb2
 //   k_seg_fin   per hit (1 lane): gH_prev += W1a^T gP + W1b^T gQ + W3a^T Gout + W3b^T Gin;  gW1, gb1, gW3a, gW3b
-template <int SEL>
-__device__ __forceinline__ float quad_bcast(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), SEL * 0x55, 0xf, 0xf, true));
-}
-template <int SEL>
-__device__ __forceinline__ int quad_bcast(int x) { return __builtin_amdgcn_mov_dpp(x, SEL * 0x55, 0xf, 0xf, true); }
-__device__ __forceinline__ float quad_sum(float x)
-{
-    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));   // lane ^ 1
-    x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));   // lane ^ 2
-    return x;
-}
-template <int N>
-__device__ __forceinline__ void load_vec(const float *__restrict__ p, float *v)
-{
-    if constexpr (N == 1) {
-        v[0] = p[0];
-    } else if constexpr (N == 2) {
-        const float2 a = *reinterpret_cast<const float2 *>(p);
-        v[0] = a.x; v[1] = a.y;
-    } else {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i) {
-            const float4 a = reinterpret_cast<const float4 *>(p)[i];
-            v[4 * i] = a.x; v[4 * i + 1] = a.y; v[4 * i + 2] = a.z; v[4 * i + 3] = a.w;
-        }
-    }
-}
-template <int N>
-__device__ __forceinline__ void store_vec(float *__restrict__ p, const float *v)
-{
-    if constexpr (N == 1) {
-        p[0] = v[0];
-    } else if constexpr (N == 2) {
-        *reinterpret_cast<float2 *>(p) = make_float2(v[0], v[1]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i)
-            reinterpret_cast<float4 *>(p)[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-    }
-}
-
 // LDS floats of the per-hit kernels' outer-product stagings (hit: gp | gr | h | q | ones when that fits, fin: two left
 // factors | h | ones)
 template <int F, int D>
@@ -897,10 +830,10 @@ __device__ __forceinline__ void hit_bwd4_core(
     for (int i = 0; i < D; ++i) q[i] = gr[i] = gp[i] = 0.0f;
     if (active) {
         float hp[LDH];
-        load_row4<LDH / 4>(H + n * ldh, hp);
+        load_vec<LDH>(H + n * ldh, hp);
 #pragma unroll
         for (int k = 0; k < C; ++k) h[k] = hp[k];
-        load_row4<D / 4>(Qk + n * D, q);
+        load_vec<D>(Qk + n * D, q);
 #pragma unroll
         for (int i = 0; i < D; ++i) gr[i] = gn[i] * (1.0f - hn[i] * hn[i]);
 #pragma unroll
@@ -920,7 +853,7 @@ __device__ __forceinline__ void hit_bwd4_core(
             for (int i = 0; i < D; ++i) s = fmaf(W3[i * 3 * C + 2 * C + k], gp[i], s);
             gh[k] = s;
         }
-        store_row4<LDH / 4>(gH + n * ldh, gh);                     // gHself initialises gH_prev
+        store_vec<LDH>(gH + n * ldh, gh);                     // gHself initialises gH_prev
         float a[3 * D], b[3 * D];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -936,8 +869,8 @@ __device__ __forceinline__ void hit_bwd4_core(
             a[at] = pp; a[at + DL] = rr; b[at] = qq; b[at + DL] = ss;
             a[2 * D + i] = gp[i]; b[2 * D + i] = gp[i];
         }
-        store_row4<3 * D / 4>(A + n * 3 * D, a);
-        store_row4<3 * D / 4>(B + n * 3 * D, b);
+        store_vec<3 * D>(A + n * 3 * D, a);
+        store_vec<3 * D>(B + n * 3 * D, b);
     }
     if constexpr (3 * D + C + 1 <= kOuterJobRows) {
         // both sums in one staging: rows gp | gr | h | q | ones
@@ -975,8 +908,8 @@ __global__ __launch_bounds__(kBlock) void k_hit_bwd4(
 #pragma unroll
     for (int i = 0; i < D; ++i) hn[i] = gn[i] = 0.0f;
     if (active) {
-        load_row4<D / 4>(Hn + n * ldh, hn);
-        load_row4<D / 4>(gHn + n * ldh, gn);
+        load_vec<D>(Hn + n * ldh, hn);
+        load_vec<D>(gHn + n * ldh, gn);
     }
     hit_bwd4_core<F, D>(n, active, H, Qk, ldh, hn, gn, W1, b1, W3, W4, gH, A, B, my_replica(gW3, rep_stride),
                         my_replica(gb3, rep_stride), my_replica(gW4, rep_stride), my_replica(gb4, rep_stride), lds);
@@ -1107,13 +1040,13 @@ __device__ __forceinline__ void seg_fin_core(int64_t n, bool active, const float
     for (int k = 0; k < C; ++k) h[k] = 0.0f;
     if (active) {
         float g4[4 * D];
-        load_row4<D>(G4 + n * 4 * D, g4);
+        load_vec<4 * D>(G4 + n * 4 * D, g4);
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             const int at = (i / DL) * 4 * DL + (i % DL);
             gP[i] = g4[at]; gQ[i] = g4[at + DL]; Gout[i] = g4[at + 2 * DL]; Gin[i] = g4[at + 3 * DL];
         }
-        load_row4<LDH / 4>(H + n * ldh, hr);
+        load_vec<LDH>(H + n * ldh, hr);
 #pragma unroll
         for (int k = 0; k < C; ++k) h[k] = hr[k];
 #pragma unroll
@@ -1146,10 +1079,10 @@ __global__ __launch_bounds__(kBlock) void k_seg_fin(
     float gh[LDH], hr[LDH];
 #pragma unroll
     for (int k = 0; k < LDH; ++k) gh[k] = hr[k] = 0.0f;
-    if (active) load_row4<LDH / 4>(gH + n * ldh, gh);
+    if (active) load_vec<LDH>(gH + n * ldh, gh);
     seg_fin_core<F, D>(n, active, H, ldh, G4, W1, W3, gh, hr, my_replica(gW1, rep_stride), my_replica(gb1, rep_stride),
                        my_replica(gW3, rep_stride), lds);
-    if (active) store_row4<LDH / 4>(gH + n * ldh, gh);
+    if (active) store_vec<LDH>(gH + n * ldh, gh);
 }
 
 // k_seg_fin of iteration u and k_hit_bwd4 of iteration u - 1 in one launch: both are one lane per hit, and what the
@@ -1174,7 +1107,7 @@ __global__ __launch_bounds__(kBlock) void k_fin_hit(
     float gh[LDH], hr[LDH];
 #pragma unroll
     for (int k = 0; k < LDH; ++k) gh[k] = hr[k] = 0.0f;
-    if (active) load_row4<LDH / 4>(gH + n * ldh, gh);
+    if (active) load_vec<LDH>(gH + n * ldh, gh);
     float *const gW3r = my_replica(gW3, rep_stride);
     seg_fin_core<F, D>(n, active, H, ldh, G4, W1, W3, gh, hr, my_replica(gW1, rep_stride), my_replica(gb1, rep_stride),
                        gW3r, lds);
@@ -1192,11 +1125,6 @@ __global__ __launch_bounds__(kBlock) void k_fin_hit(
 //   k_hit_bwdW  per hit (1 lane): P R Q S from H, gp from the kept q -> A, B; gH_prev = W3c^T gp; gW3c, gb3, gW4, gb4
 //   k_seg_bwdW  per hit (16 lanes): both list walks -> G4 = [gP gQ Gout Gin] and the hit's W2 / b2 terms
 //   k_seg_finW  per hit (1 lane): gH_prev += W^T G4;  gW1, gb1, gW3a, gW3b, gW2, gb2
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 
 // the dense wide kernels run 512 threads for their 256 hits: eight waves share the tiles, two per SIMD instead of one
 constexpr int kFinThreads = 512;
@@ -1238,7 +1166,6 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
     gb3 = my_replica(gb3, rep_stride);
     gW4 = my_replica(gW4, rep_stride);
     gb4 = my_replica(gb4, rep_stride);
-    typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH, DL = D / 16, RS = kOuterStride;
     constexpr int RT = D / 16, CT = (C + 1 + 15) / 16, KT = (LDH + 15) / 16, YR = 16 * CT;
     static_assert(D + 1 <= YR && LDH <= YR, "the [q | 1] block and the padded h rows fit the [h | 1] rows");
@@ -1255,9 +1182,9 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
 #pragma unroll
         for (int i = 0; i < D; ++i) qv[i] = hn[i] = gn[i] = 0.0f;
         if (active) {
-            load_row4<D / 4>(Qk + n * D, qv);
-            load_row4<D / 4>(Hn + n * ldh, hn);
-            load_row4<D / 4>(gHn + n * ldh, gn);
+            load_vec<D>(Qk + n * D, qv);
+            load_vec<D>(Hn + n * ldh, hn);
+            load_vec<D>(gHn + n * ldh, gn);
         }
 #pragma unroll
         for (int i = 0; i < D; ++i) {
@@ -1274,7 +1201,7 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
         for (int t = wv; t < RT * ct; t += NW) {
             const int it = t / ct, jt = t % ct;
             const float *a = X + (16 * it + r16) * RS + g4, *b = Y + (16 * jt + r16) * RS + g4;
-            f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
+            f4_t c = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 8
             for (int st = 0; st < kBlock / 4; ++st) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * st], b[4 * st], c, 0, 0, 0);
             const int col = 16 * jt + r16;
@@ -1288,11 +1215,11 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
         }
     };
     outer(D, gW4, D, 0, gb4);
-    f4v gp[RT][HT];                                       // gp rows 16 kt + 4 g4 + r of hits hcol + 16 ht
+    f4_t gp[RT][HT];                                       // gp rows 16 kt + 4 g4 + r of hits hcol + 16 ht
 #pragma unroll
     for (int kt = 0; kt < RT; ++kt) {
 #pragma unroll
-        for (int ht = 0; ht < HT; ++ht) gp[kt][ht] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int ht = 0; ht < HT; ++ht) gp[kt][ht] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 4
         for (int st = 0; st < D / 4; ++st) {
             const float aw = W4[(4 * st + g4) * D + 16 * kt + r16];
@@ -1328,9 +1255,9 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
     // gH_prev = W3c^T gp (initialises the row; k_seg_finW adds the segment terms)
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt) {
-        f4v c[HT];
+        f4_t c[HT];
 #pragma unroll
-        for (int ht = 0; ht < HT; ++ht) c[ht] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int ht = 0; ht < HT; ++ht) c[ht] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
         const int k = 16 * kt + r16;
 #pragma unroll 4
         for (int st = 0; st < D / 4; ++st) {
@@ -1343,7 +1270,7 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
 #pragma unroll
         for (int ht = 0; ht < HT; ++ht) {
             const int64_t nn = n0 + hcol + 16 * ht;
-            if (nn < n_hits && k0 < LDH) *reinterpret_cast<f4v *>(gH + nn * ldh + k0) = c[ht];
+            if (nn < n_hits && k0 < LDH) *reinterpret_cast<f4_t *>(gH + nn * ldh + k0) = c[ht];
         }
     }
     // records: [P R] -> A, [Q S] -> B (rows i of the products = dims; the ones row of Y carries b1 into P)
@@ -1353,9 +1280,9 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
         const int i = 16 * it + r16;
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {           // 0: P, R (W1a, W3a) -> A;  1: Q, S (W1b, W3b) -> B
-            f4v c1[HT], c3[HT];
+            f4_t c1[HT], c3[HT];
 #pragma unroll
-            for (int ht = 0; ht < HT; ++ht) c1[ht] = c3[ht] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int ht = 0; ht < HT; ++ht) c1[ht] = c3[ht] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 4
             for (int st = 0; st < KS; ++st) {
                 const int kk = 4 * st + g4;
@@ -1383,12 +1310,12 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
                 // this lane holds dims i0 .. i0 + 3 (i0 = 16 it + 4 g4): lane share i0 / DL (+1 at DL = 2)
                 const int i0 = 16 * it + 4 * g4;
                 if constexpr (DL == 4) {
-                    *reinterpret_cast<f4v *>(rec + (i0 / 4) * 8) = c1[ht];
-                    *reinterpret_cast<f4v *>(rec + (i0 / 4) * 8 + 4) = c3[ht];
+                    *reinterpret_cast<f4_t *>(rec + (i0 / 4) * 8) = c1[ht];
+                    *reinterpret_cast<f4_t *>(rec + (i0 / 4) * 8 + 4) = c3[ht];
                 } else {
                     static_assert(DL == 2 || DL == 4, "record shares of 2 or 4 dims");
-                    *reinterpret_cast<f4v *>(rec + (i0 / 2) * 4) = f4v{c1[ht].x, c1[ht].y, c3[ht].x, c3[ht].y};
-                    *reinterpret_cast<f4v *>(rec + (i0 / 2 + 1) * 4) = f4v{c1[ht].z, c1[ht].w, c3[ht].z, c3[ht].w};
+                    *reinterpret_cast<f4_t *>(rec + (i0 / 2) * 4) = f4_t{c1[ht].x, c1[ht].y, c3[ht].x, c3[ht].y};
+                    *reinterpret_cast<f4_t *>(rec + (i0 / 2 + 1) * 4) = f4_t{c1[ht].z, c1[ht].w, c3[ht].z, c3[ht].w};
                 }
             }
         }
@@ -1400,8 +1327,8 @@ __global__ __launch_bounds__(kFinThreads) void k_hit_bwdW(
         for (int ht = 0; ht < HT; ++ht) {
             const int64_t nn = n0 + hcol + 16 * ht;
             if (nn < n_hits) {
-                *reinterpret_cast<f4v *>(A + nn * 3 * D + 2 * D + 16 * kt + 4 * g4) = gp[kt][ht];
-                *reinterpret_cast<f4v *>(B + nn * 3 * D + 2 * D + 16 * kt + 4 * g4) = gp[kt][ht];
+                *reinterpret_cast<f4_t *>(A + nn * 3 * D + 2 * D + 16 * kt + 4 * g4) = gp[kt][ht];
+                *reinterpret_cast<f4_t *>(B + nn * 3 * D + 2 * D + 16 * kt + 4 * g4) = gp[kt][ht];
             }
         }
 }
@@ -1445,11 +1372,11 @@ __device__ __forceinline__ void row_walk(int beg, int end, int n, int p, const i
         const bool odd = q & 1, hi = q & 2;
         const float s0 = odd ? part[0] : part[1], s1 = odd ? part[2] : part[3];
         const float k0 = odd ? part[1] : part[0], k1 = odd ? part[3] : part[2];
-        const float t0 = k0 + dppf<0xB1>(s0), t1 = k1 + dppf<0xB1>(s1);
+        const float t0 = k0 + dpp<0xB1>(s0), t1 = k1 + dpp<0xB1>(s1);
         const float give = hi ? t0 : t1, keep = hi ? t1 : t0;
-        float ge = keep + dppf<0x4E>(give);
-        ge += dppf<0x124>(ge);                                 // row_ror:4
-        ge += dppf<0x128>(ge);                                 // row_ror:8
+        float ge = keep + dpp<0x4E>(give);
+        ge += dpp<0x124>(ge);                                 // row_ror:4
+        ge += dpp<0x128>(ge);                                 // row_ror:8
         ge += gx;
         const float gu = ge * ev * (1.0f - ev);
 #pragma unroll
@@ -1529,7 +1456,6 @@ __global__ __launch_bounds__(kFinThreads) void k_seg_finW(
     gW2 = my_replica(gW2, rep_stride);
     gb2 = my_replica(gb2, rep_stride);
     gW3 = my_replica(gW3, rep_stride);
-    typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH, DL = D / 16, RS = kOuterStride;
     constexpr int RT = D / 16, CT = (C + 1 + 15) / 16, KT = (LDH + 15) / 16, ROWS = D + 16 * CT;
     __shared__ __attribute__((aligned(16))) float lds[ROWS * RS];   // [v (D rows) | h (C) | ones | zero pad] x 256 hits
@@ -1544,11 +1470,11 @@ __global__ __launch_bounds__(kFinThreads) void k_seg_finW(
 #pragma unroll
         for (int k = C; k < 16 * CT; ++k) lds[(D + k) * RS + threadIdx.x] = (k == C && active) ? 1.0f : 0.0f;   // ones row, zero pad
     }
-    f4v cg[KT][HT];                                      // gh rows 16 kt + 4 g4 + r of hits HW wv + 16 ht + r16
+    f4_t cg[KT][HT];                                      // gh rows 16 kt + 4 g4 + r of hits HW wv + 16 ht + r16
 #pragma unroll
     for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
-        for (int ht = 0; ht < HT; ++ht) cg[kt][ht] = f4v{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int ht = 0; ht < HT; ++ht) cg[kt][ht] = f4_t{0.0f, 0.0f, 0.0f, 0.0f};
     // the four per-hit vectors one at a time: m = 0 gP (W1a, gb1), 1 gQ (W1b), 2 Gout (W3a), 3 Gin (W3b)
 #pragma unroll 1
     for (int m = 0; m < 4; ++m) {
@@ -1562,7 +1488,7 @@ __global__ __launch_bounds__(kFinThreads) void k_seg_finW(
         for (int t = wv; t < RT * CT; t += NW) {
             const int it = t / CT, jt = t % CT;
             const float *a = lds + (16 * it + r16) * RS + g4, *b = lds + (D + 16 * jt + r16) * RS + g4;
-            f4v c = {0.0f, 0.0f, 0.0f, 0.0f};
+            f4_t c = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 8
             for (int st = 0; st < kBlock / 4; ++st) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * st], b[4 * st], c, 0, 0, 0);
             const int col = 16 * jt + r16;
@@ -1595,7 +1521,7 @@ __global__ __launch_bounds__(kFinThreads) void k_seg_finW(
             const int64_t nn = n0 + HW * wv + 16 * ht + r16;
             const int k0 = 16 * kt + 4 * g4;
             if (nn < n_hits && k0 < LDH) {
-                f4v *dst = reinterpret_cast<f4v *>(gH + nn * ldh + k0);
+                f4_t *dst = reinterpret_cast<f4_t *>(gH + nn * ldh + k0);
                 *dst = *dst + cg[kt][ht];
             }
         }
@@ -1632,10 +1558,10 @@ __global__ __launch_bounds__(kBlock) void k_seg_grad(const int32_t *__restrict__
         float g = 0.0f;
         if (s >= 0) {
             float hs[LDH], hd[LDH], gmi_d[LDH], gmo_s[LDH];
-            load_row4<LDH / 4>(H + (int64_t)s * LDH, hs);
-            load_row4<LDH / 4>(H + (int64_t)d * LDH, hd);
-            load_row4<LDH / 4>(gmio + (int64_t)d * 2 * LDH, gmi_d);
-            load_row4<LDH / 4>(gmio + (int64_t)s * 2 * LDH + LDH, gmo_s);
+            load_vec<LDH>(H + (int64_t)s * LDH, hs);
+            load_vec<LDH>(H + (int64_t)d * LDH, hd);
+            load_vec<LDH>(gmio + (int64_t)d * 2 * LDH, gmi_d);
+            load_vec<LDH>(gmio + (int64_t)s * 2 * LDH + LDH, gmo_s);
 #pragma unroll
             for (int c = 0; c < C; ++c) g = fmaf(gmi_d[c], hs[c], g);
 #pragma unroll
@@ -1781,10 +1707,10 @@ __global__ __launch_bounds__(kBlock) void k_head_bwd(const float *__restrict__ H
     if (n < n_hits) {
         const float yn = y[n], dz = gy[n] * (1.0f - yn) * yn;
         float h[LDH], g[LDH];
-        load_row4<LDH / 4>(H + n * LDH, h);
+        load_vec<LDH>(H + n * LDH, h);
 #pragma unroll
         for (int k = 0; k < LDH; ++k) g[k] = k < D ? dz * Wo[k] : 0.0f;
-        store_row4<LDH / 4>(gH + n * LDH, g);
+        store_vec<LDH>(gH + n * LDH, g);
 #pragma unroll
         for (int k = 0; k < C; ++k) v[k] = dz * h[k];
         v[C] = dz;
@@ -1926,8 +1852,8 @@ struct BwdRun {
     {
         if constexpr (D <= 16) if (N > 0) {
             GNN_LAUNCH("kb_prs", (kb_prs<F, D>), grid_for(N), kBlock, s, Hp, LDH, p->W1, p->b1, p->W3, w.A, w.B, N);
-            GNN_LAUNCH("k_hit_bwd", (k_hit_bwd<F, D, false>), grid_for(N), kBlock, s, Hp, Hu, nullptr, LDH, ep, BWD_LISTS, p->W3,
-                       p->b3, p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
+            GNN_LAUNCH("k_hit_bwd", (k_hit_bwd<F, D>), grid_for(N), kBlock, s, Hp, Hu, LDH, ep, BWD_LISTS, p->W3, p->b3,
+                       p->W4, gH, gHprev, w.A, w.B, rp + GL::oW3, rp + GL::ob3, rp + GL::oW4, rp + GL::ob4, RS, N);
             GNN_LAUNCH("k_seg_bwd", (k_seg_bwd<F, D>), grid_for(N), kBlock, s, Hp, LDH, w.A, w.B, ep, BWD_LISTS, p->W1,
                        p->W2, p->W3, gHprev, rp + GL::oW1, rp + GL::ob1, rp + GL::oW2, rp + GL::ob2, rp + GL::oW3, RS, N);
         }

@@ -27,6 +27,7 @@
 //   node pass   k_node;  wide at >= 2048 hits, and with a NodeClassifier's head at every size: k_node_walkW, k_node_mlpW
 //   gnn_input_fwd / gnn_edge_fwd (k_pq, k_edge) / gnn_node_fwd: one lane per item at every size
 #include "common.h"
+#include "lane_ops.h"
 
 #include <type_traits>
 
@@ -133,14 +134,6 @@ __device__ __forceinline__ void store_pq(const float *h, const float *__restrict
         o[v] = make_float4(pq[4 * v], pq[4 * v + 1], pq[4 * v + 2], pq[4 * v + 3]);
 }
 
-template <int N4>
-__device__ __forceinline__ void store_row4(float *__restrict__ row, const float *v)
-{
-    float4 *o = reinterpret_cast<float4 *>(row);
-#pragma unroll
-    for (int i = 0; i < N4; ++i) o[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-}
-
 // NodeClassifier's output network on a finished hit row h = [H'_T | X]: sigmoid(Wo h + bo), Wo [1, C]
 // (gnn/MPNN_HitClassifier.ipynb cell 21), k ascending from the bias in every kernel that runs it
 template <int C>
@@ -183,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void k_input(const float *__restrict__ X,
         for (int k = 0; k < F; ++k) acc = fmaf(Win[d * F + k], h[D + k], acc);
         h[d] = tanh_f(acc);
     }
-    store_row4<LDH / 4>(H + n * ldh, h);
+    store_vec<LDH>(H + n * ldh, h);
     if (PQ) store_pq<F, D>(h, W1, b1, PQ + n * 2 * D);
     if (y) y[n] = head_score<F + D>(h, Wo, bo);           // n_iters = 0: the output network reads H0
 }
@@ -301,7 +294,7 @@ __global__ __launch_bounds__(kBlock) void k_node(
         for (int k = 0; k < C; ++k) acc = fmaf(W3[d * 3 * C + 2 * C + k], M[2 * LDH + k], acc);
         q[d] = tanh_f(acc);
     }
-    if (Qkeep) store_row4<D / 4>(Qkeep + n * D, q);         // training: the backward needs no second list walk
+    if (Qkeep) store_vec<D>(Qkeep + n * D, q);         // training: the backward needs no second list walk
     float hn[LDH];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
@@ -312,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void k_node(
     }
 #pragma unroll
     for (int k = D; k < LDH; ++k) hn[k] = M[2 * LDH + k];   // skip concat of X (model.py:154)
-    store_row4<LDH / 4>(Hn + n * ldhn, hn);
+    store_vec<LDH>(Hn + n * ldhn, hn);
     if (PQ) store_pq<F, D>(hn, W1, b1, PQ + n * 2 * D);
     if (y) y[n] = head_score<C>(hn, Wo, bo);             // last node pass of a NodeClassifier: its output network
 }
@@ -327,14 +320,6 @@ __global__ __launch_bounds__(kBlock) void k_node(
 // store mi | mo; (2) k_node_mlpW: the MLP of 256 hits as exact fp32 matrix-core products
 // (v_mfma_f32_16x16x4_f32 accumulates in k order from the bias: the same fma chain as k_node's loops)
 // from transposed LDS stagings of mi, mo, h, then q, then [H' | x].
-template <int SEL>
-__device__ __forceinline__ int qb_i(int x) { return __builtin_amdgcn_mov_dpp(x, SEL * 0x55, 0xf, 0xf, true); }
-template <int SEL>
-__device__ __forceinline__ float qb_f(float x)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), SEL * 0x55, 0xf, 0xf, true));
-}
-
 template <int LDH>
 __device__ __forceinline__ void row16_walk(int beg, int end, int n, int p, const int32_t *__restrict__ nbr,
                                            const int32_t *__restrict__ eid, const float *__restrict__ e,
@@ -350,7 +335,10 @@ __device__ __forceinline__ void row16_walk(int beg, int end, int n, int p, const
         float4 r[4][CPL];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int nbj = j == 0 ? qb_i<0>(nb) : j == 1 ? qb_i<1>(nb) : j == 2 ? qb_i<2>(nb) : qb_i<3>(nb);
+            const int nbj = j == 0   ? quad_bcast<0>(nb)
+                            : j == 1 ? quad_bcast<1>(nb)
+                            : j == 2 ? quad_bcast<2>(nb)
+                                     : quad_bcast<3>(nb);
             const float4 *row = reinterpret_cast<const float4 *>(H + (int64_t)nbj * ldh);
 #pragma unroll
             for (int c = 0; c < CPL; ++c)
@@ -358,7 +346,10 @@ __device__ __forceinline__ void row16_walk(int beg, int end, int n, int p, const
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float w = j == 0 ? qb_f<0>(ev) : j == 1 ? qb_f<1>(ev) : j == 2 ? qb_f<2>(ev) : qb_f<3>(ev);
+            const float w = j == 0   ? quad_bcast<0>(ev)
+                            : j == 1 ? quad_bcast<1>(ev)
+                            : j == 2 ? quad_bcast<2>(ev)
+                                     : quad_bcast<3>(ev);
             if (k + j < end) {                              // (row-uniform; the sums are those of k_node)
 #pragma unroll
                 for (int c = 0; c < CPL; ++c) {
@@ -415,7 +406,6 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
     float *__restrict__ PQ, float *__restrict__ Qkeep, int64_t n_hits, const float *__restrict__ Wo,
     const float *__restrict__ bo, float *__restrict__ y)
 {
-    typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH, RS = kBlock + 4;
     constexpr int RT = D / 16, KS = (C + 3) / 4, ROWS = 4 * KS > D ? 4 * KS : D;
     __shared__ __attribute__((aligned(16))) float lds[ROWS * RS];   // [k][hit]: one operand block at a time
@@ -435,10 +425,10 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
         }
     }
     // ---- q = tanh(W3 [mi | mo | h] + b3): three k-chunks of C rows            (model.py:120)
-    f4v cq[RT][4];
+    f4_t cq[RT][4];
 #pragma unroll
     for (int it = 0; it < RT; ++it) {
-        const f4v bias = *reinterpret_cast<const f4v *>(b3 + 16 * it + 4 * g4);
+        const f4_t bias = *reinterpret_cast<const f4_t *>(b3 + 16 * it + 4 * g4);
 #pragma unroll
         for (int ht = 0; ht < 4; ++ht) cq[it][ht] = bias;
     }
@@ -484,18 +474,18 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
     for (int it = 0; it < RT; ++it)
 #pragma unroll
         for (int ht = 0; ht < 4; ++ht) {
-            const f4v q = {tanh_f(cq[it][ht].x), tanh_f(cq[it][ht].y), tanh_f(cq[it][ht].z), tanh_f(cq[it][ht].w)};
+            const f4_t q = {tanh_f(cq[it][ht].x), tanh_f(cq[it][ht].y), tanh_f(cq[it][ht].z), tanh_f(cq[it][ht].w)};
             float *x = lds + (16 * it + 4 * g4) * RS + hcol + 16 * ht;
             x[0] = q.x; x[RS] = q.y; x[2 * RS] = q.z; x[3 * RS] = q.w;
             const int64_t nn = n0 + hcol + 16 * ht;
-            if (Qkeep && nn < n_hits) *reinterpret_cast<f4v *>(Qkeep + nn * D + 16 * it + 4 * g4) = q;
+            if (Qkeep && nn < n_hits) *reinterpret_cast<f4_t *>(Qkeep + nn * D + 16 * it + 4 * g4) = q;
         }
     __syncthreads();
     // ---- H' = tanh(W4 q + b4)                                                   (model.py:94-98)
-    f4v hn[RT][4];
+    f4_t hn[RT][4];
 #pragma unroll
     for (int it = 0; it < RT; ++it) {
-        const f4v bias = *reinterpret_cast<const f4v *>(b4 + 16 * it + 4 * g4);
+        const f4_t bias = *reinterpret_cast<const f4_t *>(b4 + 16 * it + 4 * g4);
 #pragma unroll
         for (int ht = 0; ht < 4; ++ht) hn[it][ht] = bias;
         const int i = 16 * it + r16;
@@ -508,9 +498,9 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
         }
 #pragma unroll
         for (int ht = 0; ht < 4; ++ht) {
-            hn[it][ht] = f4v{tanh_f(hn[it][ht].x), tanh_f(hn[it][ht].y), tanh_f(hn[it][ht].z), tanh_f(hn[it][ht].w)};
+            hn[it][ht] = f4_t{tanh_f(hn[it][ht].x), tanh_f(hn[it][ht].y), tanh_f(hn[it][ht].z), tanh_f(hn[it][ht].w)};
             const int64_t nn = n0 + hcol + 16 * ht;
-            if (nn < n_hits) *reinterpret_cast<f4v *>(Hn + nn * ldhn + 16 * it + 4 * g4) = hn[it][ht];
+            if (nn < n_hits) *reinterpret_cast<f4_t *>(Hn + nn * ldhn + 16 * it + 4 * g4) = hn[it][ht];
         }
     }
     if (active) {                                        // skip concat of X (and the row's padding), model.py:154
@@ -552,10 +542,10 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
 #pragma unroll 1
     for (int it = 0; it < RT; ++it) {
         const int i = 16 * it + r16;
-        f4v cp[4], cqq[4];
-        const f4v bias = *reinterpret_cast<const f4v *>(b1 + 16 * it + 4 * g4);
+        f4_t cp[4], cqq[4];
+        const f4_t bias = *reinterpret_cast<const f4_t *>(b1 + 16 * it + 4 * g4);
 #pragma unroll
-        for (int ht = 0; ht < 4; ++ht) { cp[ht] = bias; cqq[ht] = f4v{0.0f, 0.0f, 0.0f, 0.0f}; }
+        for (int ht = 0; ht < 4; ++ht) { cp[ht] = bias; cqq[ht] = f4_t{0.0f, 0.0f, 0.0f, 0.0f}; }
 #pragma unroll 4
         for (int st = 0; st < KS; ++st) {
             const int kk = 4 * st + g4;
@@ -572,8 +562,8 @@ __global__ __launch_bounds__(kBlock) void k_node_mlpW(
         for (int ht = 0; ht < 4; ++ht) {
             const int64_t nn = n0 + hcol + 16 * ht;
             if (nn < n_hits) {
-                *reinterpret_cast<f4v *>(PQ + nn * 2 * D + 16 * it + 4 * g4) = cp[ht];
-                *reinterpret_cast<f4v *>(PQ + nn * 2 * D + D + 16 * it + 4 * g4) = cqq[ht];
+                *reinterpret_cast<f4_t *>(PQ + nn * 2 * D + 16 * it + 4 * g4) = cp[ht];
+                *reinterpret_cast<f4_t *>(PQ + nn * 2 * D + D + 16 * it + 4 * g4) = cqq[ht];
             }
         }
     }
@@ -586,7 +576,6 @@ template <int F, int D>
 __global__ __launch_bounds__(kBlock) void k_pq_mlpW(const float *__restrict__ H, int ldh, const float *__restrict__ W1,
                                                     const float *__restrict__ b1, float *__restrict__ PQ, int64_t n_hits)
 {
-    typedef float f4v __attribute__((ext_vector_type(4)));
     constexpr int C = Shape<F, D>::C, LDH = Shape<F, D>::LDH, RS = kBlock + 4;
     constexpr int RT = D / 16, KS = (C + 3) / 4;
     static_assert(LDH == 4 * KS, "a padded H row is the k-steps of the products");
@@ -606,10 +595,10 @@ __global__ __launch_bounds__(kBlock) void k_pq_mlpW(const float *__restrict__ H,
 #pragma unroll 1
     for (int it = 0; it < RT; ++it) {
         const int i = 16 * it + r16;
-        f4v cp[4], cq[4];
-        const f4v bias = *reinterpret_cast<const f4v *>(b1 + 16 * it + 4 * g4);
+        f4_t cp[4], cq[4];
+        const f4_t bias = *reinterpret_cast<const f4_t *>(b1 + 16 * it + 4 * g4);
 #pragma unroll
-        for (int ht = 0; ht < 4; ++ht) { cp[ht] = bias; cq[ht] = f4v{0.0f, 0.0f, 0.0f, 0.0f}; }
+        for (int ht = 0; ht < 4; ++ht) { cp[ht] = bias; cq[ht] = f4_t{0.0f, 0.0f, 0.0f, 0.0f}; }
 #pragma unroll 4
         for (int st = 0; st < KS; ++st) {
             const int kk = 4 * st + g4;
@@ -626,8 +615,8 @@ __global__ __launch_bounds__(kBlock) void k_pq_mlpW(const float *__restrict__ H,
         for (int ht = 0; ht < 4; ++ht) {
             const int64_t nn = n0 + hcol + 16 * ht;
             if (nn < n_hits) {
-                *reinterpret_cast<f4v *>(PQ + nn * 2 * D + 16 * it + 4 * g4) = cp[ht];
-                *reinterpret_cast<f4v *>(PQ + nn * 2 * D + D + 16 * it + 4 * g4) = cq[ht];
+                *reinterpret_cast<f4_t *>(PQ + nn * 2 * D + 16 * it + 4 * g4) = cp[ht];
+                *reinterpret_cast<f4_t *>(PQ + nn * 2 * D + D + 16 * it + 4 * g4) = cq[ht];
             }
         }
     }

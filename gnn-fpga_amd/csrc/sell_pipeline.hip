@@ -48,6 +48,7 @@
 // gather from global memory instead, with workgroups renumbered so that each XCD walks a
 // contiguous range of tiles (whole graphs stay in one XCD's L2).
 #include "common.h"
+#include "lane_ops.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -191,23 +192,6 @@ __global__ __launch_bounds__(256) void k_pack(gnn_params_t p, float *__restrict_
 // ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v)
-{
-    // quad_perm reads only lanes of the own quad (always valid), so no "old" value is needed:
-    // mov_dpp (old = undef) saves the v_mov that update_dpp(0, ...) needs to set it up
-    return __builtin_bit_cast(
-        float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
-// sum over the 4 lanes of a quad, identical bits in all 4 lanes
-__device__ __forceinline__ float quad_sum(float v)
-{
-    v += dpp<0xB1>(v);   // quad_perm [1,0,3,2]
-    v += dpp<0x4E>(v);   // quad_perm [2,3,0,1]
-    return v;
-}
-
 // all-gather inside a quad: out[j*N + i] = loc[i] of lane j
 template <int N>
 __device__ __forceinline__ void quad_allgather(const float (&loc)[N], float *out)
@@ -218,44 +202,6 @@ __device__ __forceinline__ void quad_allgather(const float (&loc)[N], float *out
         out[1 * N + i] = dpp<0x55>(loc[i]);
         out[2 * N + i] = dpp<0xAA>(loc[i]);
         out[3 * N + i] = dpp<0xFF>(loc[i]);
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void load_vec(const float *__restrict__ src, float *dst)
-{
-    if constexpr (N == 1) {
-        dst[0] = src[0];
-    } else if constexpr (N == 2) {
-        const float2 v = *reinterpret_cast<const float2 *>(src);
-        dst[0] = v.x; dst[1] = v.y;
-    } else {
-        static_assert(N % 4 == 0, "vector length");
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i) {
-            const float4 v = reinterpret_cast<const float4 *>(src)[i];
-            dst[4 * i] = v.x; dst[4 * i + 1] = v.y; dst[4 * i + 2] = v.z; dst[4 * i + 3] = v.w;
-        }
-    }
-}
-
-typedef float f2_t __attribute__((ext_vector_type(2)));
-typedef float f3_t __attribute__((ext_vector_type(3)));
-typedef float f4_t __attribute__((ext_vector_type(4)));
-
-template <int N>
-__device__ __forceinline__ void store_vec(float *__restrict__ dst, const float *src)
-{
-    if constexpr (N == 1) {
-        dst[0] = src[0];
-    } else if constexpr (N == 2) {
-        *reinterpret_cast<float2 *>(dst) = make_float2(src[0], src[1]);
-    } else {
-        static_assert(N % 4 == 0, "vector length");
-#pragma unroll
-        for (int i = 0; i < N / 4; ++i)
-            reinterpret_cast<float4 *>(dst)[i] =
-                make_float4(src[4 * i], src[4 * i + 1], src[4 * i + 2], src[4 * i + 3]);
     }
 }
 
@@ -697,7 +643,6 @@ __device__ __forceinline__ void mfma_tail_scratch(const unsigned *tb, const floa
 {
     using B = BL<F, D>;
     constexpr int NT1 = B::NT1, KS1 = B::KS1;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     const bf16x8_t *T4 = reinterpret_cast<const bf16x8_t *>(tb);
     const bf16x8_t *Tm = T4 + NT1 * KS1 * 64;
     const float *b4 = reinterpret_cast<const float *>(tb + NT1 * KS1 * 256 + B::template tm_words<LAST>());
@@ -707,7 +652,7 @@ __device__ __forceinline__ void mfma_tail_scratch(const unsigned *tb, const floa
     float v[NT1][4];
 #pragma unroll
     for (int t = 0; t < NT1; ++t) {
-        const f4v r = *reinterpret_cast<const f4v *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
+        const f4_t r = *reinterpret_cast<const f4_t *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
         v[t][0] = r.x; v[t][1] = r.y; v[t][2] = r.z; v[t][3] = r.w;
     }
     bf16x8_t xb;                                                   // the X step's B fragment
@@ -722,7 +667,7 @@ __device__ __forceinline__ void mfma_tail_scratch(const unsigned *tb, const floa
     for (int st = 0; st < KS1; ++st) qb[st] = act_frag<NT1>(v, st);
 #pragma unroll
     for (int T = 0; T < NT1; ++T) {
-        f4v c = *reinterpret_cast<const f4v *>(b4 + 16 * T + 4 * g);
+        f4_t c = *reinterpret_cast<const f4_t *>(b4 + 16 * T + 4 * g);
 #pragma unroll
         for (int st = 0; st < KS1; ++st)
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(T4[(T * KS1 + st) * 64 + lane], qb[st], c, 0, 0, 0);
@@ -744,7 +689,6 @@ __device__ __forceinline__ void mfma_records(const bf16x8_t *Tm, const float *bm
     using B = BL<F, D>;
     constexpr int d4 = D / 4, NT1 = B::NT1, KS1 = B::KS1, KS2 = B::KS2;
     constexpr int NT2 = LAST ? B::NT2L : B::NT2N;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     const int hit = lane & 15, g = lane >> 4;
     bf16x8_t hb[KS1];
 #pragma unroll
@@ -755,7 +699,7 @@ __device__ __forceinline__ void mfma_records(const bf16x8_t *Tm, const float *bm
     for (int Tu = 0; Tu < NT2; ++Tu) {
         if (TS != 1 && (Tu % 4) != T0) continue;                   // (TS is 1 or 4; wave-uniform)
         const int T = Tu;
-        f4v c = *reinterpret_cast<const f4v *>(bm + 16 * T + 4 * g);
+        f4_t c = *reinterpret_cast<const f4_t *>(bm + 16 * T + 4 * g);
 #pragma unroll
         for (int st = 0; st < KS2; ++st)
             c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Tm[(T * KS2 + st) * 64 + lane],
@@ -786,7 +730,7 @@ __device__ __forceinline__ void mfma_records(const bf16x8_t *Tm, const float *bm
             unsigned *row = reinterpret_cast<unsigned *>(o < 2 * D ? PRn : QSn) + n * D + (o % (2 * D)) / 2;
             *reinterpret_cast<uint2 *>(row) = make_uint2(pack_bf16(c.x, c.y), pack_bf16(c.z, c.w));
         } else {
-            *reinterpret_cast<f4v *>(dst) = c;
+            *reinterpret_cast<f4_t *>(dst) = c;
         }
     }
 }
@@ -872,13 +816,12 @@ __device__ __forceinline__ void mfma_records_x(const float *Tm, const float *bm,
 {
     using B = BX<F, D>;
     constexpr int KS1 = B::KS1, KS2 = B::KS2, NT2 = LAST ? B::NT2L : B::NT2N;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     const int hit = lane & 15, g = lane >> 4;
     const int64_t n = n0 + hit;
 #pragma unroll
     for (int T = 0; T < NT2; ++T) {
         if (TS != 1 && (T % 4) != T0) continue;                    // (TS is 1 or 4; wave-uniform)
-        f4v c = *reinterpret_cast<const f4v *>(bm + 16 * T + 4 * g);
+        f4_t c = *reinterpret_cast<const f4_t *>(bm + 16 * T + 4 * g);
 #pragma unroll
         for (int st = 0; st < KS1; ++st)
             c = __builtin_amdgcn_mfma_f32_16x16x4f32(Tm[(T * KS2 + st) * 64 + lane], h[st / 4][st % 4], c, 0, 0, 0);
@@ -907,7 +850,7 @@ __device__ __forceinline__ void mfma_records_x(const float *Tm, const float *bm,
             c.x = __builtin_amdgcn_exp2f(c.x); c.y = __builtin_amdgcn_exp2f(c.y);
             if (!expo_half) { c.z = __builtin_amdgcn_exp2f(c.z); c.w = __builtin_amdgcn_exp2f(c.w); }
         }
-        *reinterpret_cast<f4v *>(dst) = c;
+        *reinterpret_cast<f4_t *>(dst) = c;
     }
 }
 
@@ -919,25 +862,24 @@ __device__ __forceinline__ void mfma_hidden_x(const float *tf, const float *tr, 
 {
     using B = BX<F, D>;
     constexpr int NT1 = B::NT1, KS1 = B::KS1;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     const float *T4 = tf, *b4 = tf + NT1 * KS1 * 64 + B::template tm_words<LAST>();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const int hit = lane & 15, g = lane >> 4;
     float v[NT1][4];
 #pragma unroll
     for (int t = 0; t < NT1; ++t) {
-        const f4v r = *reinterpret_cast<const f4v *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
+        const f4_t r = *reinterpret_cast<const f4_t *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
         v[t][0] = r.x; v[t][1] = r.y; v[t][2] = r.z; v[t][3] = r.w;
     }
 #pragma unroll
     for (int T = 0; T < NT1; ++T) {
         if ((T & 3) != T0) continue;                              // (wave-uniform)
-        f4v c = *reinterpret_cast<const f4v *>(b4 + 16 * T + 4 * g);
+        f4_t c = *reinterpret_cast<const f4_t *>(b4 + 16 * T + 4 * g);
 #pragma unroll
         for (int st = 0; st < KS1; ++st)
             c = __builtin_amdgcn_mfma_f32_16x16x4f32(T4[(T * KS1 + st) * 64 + lane], v[st / 4][st % 4], c, 0, 0, 0);
-        *reinterpret_cast<f4v *>(th + hit * B::tr_stride + 16 * T + 4 * g) =
-            f4v{tanh_f(c.x), tanh_f(c.y), tanh_f(c.z), tanh_f(c.w)};
+        *reinterpret_cast<f4_t *>(th + hit * B::tr_stride + 16 * T + 4 * g) =
+            f4_t{tanh_f(c.x), tanh_f(c.y), tanh_f(c.z), tanh_f(c.w)};
     }
 }
 
@@ -950,14 +892,13 @@ __device__ __forceinline__ void mfma_tail_scratch_x(const float *tf, const float
 {
     using B = BX<F, D>;
     constexpr int NT1 = B::NT1, KS1 = B::KS1;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     const float *Tm = tf + NT1 * KS1 * 64;
     const float *bm = Tm + B::template tm_words<LAST>() + D;
     const int hit = lane & 15, g = lane >> 4;
     float h[NT1][4];
 #pragma unroll
     for (int t = 0; t < NT1; ++t) {
-        const f4v r = *reinterpret_cast<const f4v *>(th + hit * B::tr_stride + 16 * t + 4 * g);
+        const f4_t r = *reinterpret_cast<const f4_t *>(th + hit * B::tr_stride + 16 * t + 4 * g);
         h[t][0] = r.x; h[t][1] = r.y; h[t][2] = r.z; h[t][3] = r.w;
     }
     const float xb = g < F ? tr[hit * B::tr_stride + D + (g < F ? g : 0)] : 0.0f;
@@ -983,7 +924,6 @@ __global__ __launch_bounds__(256) void k_input4_bf(const float *__restrict__ X,
     using B = BL<F, D>;
     constexpr int d4 = L::d4, NT1 = B::NT1;
     constexpr int nm = B::template tm_words<LAST>(), nb = (LAST ? 2 : 5) * D;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float smem_in[];
     unsigned *tb = reinterpret_cast<unsigned *>(smem_in);           // [Tm | bm]
     for (int i = threadIdx.x; i < nm; i += 256) tb[i] = t16[(LAST ? B::o_tml : B::o_tmn) + i];
@@ -1003,8 +943,8 @@ __global__ __launch_bounds__(256) void k_input4_bf(const float *__restrict__ X,
             const int hit = lane >> 2;
 #pragma unroll
             for (int i = 0; i < d4; i += 4)
-                *reinterpret_cast<f4v *>(tr + hit * B::tr_stride + q * d4 + i) =
-                    f4v{tanh_f(hl[i]), tanh_f(hl[i + 1]), tanh_f(hl[i + 2]), tanh_f(hl[i + 3])};
+                *reinterpret_cast<f4_t *>(tr + hit * B::tr_stride + q * d4 + i) =
+                    f4_t{tanh_f(hl[i]), tanh_f(hl[i + 1]), tanh_f(hl[i + 2]), tanh_f(hl[i + 3])};
             if (q == 0)
 #pragma unroll
                 for (int k = 0; k < F; ++k) tr[hit * B::tr_stride + D + k] = x[k];
@@ -1014,7 +954,7 @@ __global__ __launch_bounds__(256) void k_input4_bf(const float *__restrict__ X,
         float v[NT1][4];
 #pragma unroll
         for (int t = 0; t < NT1; ++t) {
-            const f4v r = *reinterpret_cast<const f4v *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
+            const f4_t r = *reinterpret_cast<const f4_t *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
             v[t][0] = r.x; v[t][1] = r.y; v[t][2] = r.z; v[t][3] = r.w;
         }
         bf16x8_t xb;
@@ -1045,7 +985,6 @@ __global__ __launch_bounds__(1024) void k_input4_x(const float *__restrict__ X,
     using B = BX<F, D>;
     constexpr int d4 = L::d4, NT1 = B::NT1;
     constexpr int nm = B::template tm_words<LAST>(), nb = (LAST ? 2 : 5) * D;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float smem_inx[];
     float *tb = smem_inx;                                           // [Tm | bm]
     for (int i = threadIdx.x; i < nm; i += 1024) tb[i] = tfg[(LAST ? B::o_tml : B::o_tmn) + i];
@@ -1063,8 +1002,8 @@ __global__ __launch_bounds__(1024) void k_input4_x(const float *__restrict__ X,
             const int hit = lane >> 2;
 #pragma unroll
             for (int i = 0; i < d4; i += 4)
-                *reinterpret_cast<f4v *>(tr + hit * B::tr_stride + q * d4 + i) =
-                    f4v{tanh_f(hl[i]), tanh_f(hl[i + 1]), tanh_f(hl[i + 2]), tanh_f(hl[i + 3])};
+                *reinterpret_cast<f4_t *>(tr + hit * B::tr_stride + q * d4 + i) =
+                    f4_t{tanh_f(hl[i]), tanh_f(hl[i + 1]), tanh_f(hl[i + 2]), tanh_f(hl[i + 3])};
             if (q == 0)
 #pragma unroll
                 for (int k = 0; k < F; ++k) tr[hit * B::tr_stride + D + k] = x[k];
@@ -1074,7 +1013,7 @@ __global__ __launch_bounds__(1024) void k_input4_x(const float *__restrict__ X,
         float h[NT1][4];
 #pragma unroll
         for (int t = 0; t < NT1; ++t) {
-            const f4v r = *reinterpret_cast<const f4v *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
+            const f4_t r = *reinterpret_cast<const f4_t *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
             h[t][0] = r.x; h[t][1] = r.y; h[t][2] = r.z; h[t][3] = r.w;
         }
         const float xb = g < F ? tr[hit * B::tr_stride + D + (g < F ? g : 0)] : 0.0f;
@@ -1267,17 +1206,6 @@ __device__ __forceinline__ void a_fence(T (&r)[N])
 // SELL-16 entries of one list of a 16-hit slice.  The 4 lanes of a quad need the same entry at
 // every step, so they load 4 DIFFERENT steps with one instruction (lane q takes step 4c+q of
 // chunk c) and broadcast inside the quad with DPP.
-template <int J>
-__device__ __forceinline__ int quad_bcast_i(int v)
-{
-    return __builtin_amdgcn_mov_dpp(v, J * 0x55, 0xF, 0xF, true);
-}
-template <int J>
-__device__ __forceinline__ float quad_bcast_f(float v)
-{
-    return dpp<J * 0x55>(v);
-}
-
 constexpr int MAXC = 6;   // chunks (of 4 steps) of a list held in registers; longer lists stream
 
 // The 4 neighbour records of one chunk (this lane's 2*D/4-float piece of each).
@@ -1287,8 +1215,8 @@ struct Recs {
     __device__ __forceinline__ void read(int cur, const float *REC, int q)
     {
         constexpr int d4 = D / 4;
-        const int nb[4] = {quad_bcast_i<0>(cur), quad_bcast_i<1>(cur), quad_bcast_i<2>(cur),
-                           quad_bcast_i<3>(cur)};
+        const int nb[4] = {quad_bcast<0>(cur), quad_bcast<1>(cur), quad_bcast<2>(cur),
+                           quad_bcast<3>(cur)};
 #ifdef GNN_ABLATE_LDS
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -1388,8 +1316,8 @@ __device__ __forceinline__ void score4(const float (*rec)[2 * D4], const float *
     const float e = r_f(mine + b2);
     if constexpr (ES)
         if (ok) *eo = e;
-    const float e4[4] = {quad_bcast_f<0>(e), quad_bcast_f<1>(e), quad_bcast_f<2>(e),
-                         quad_bcast_f<3>(e)};
+    const float e4[4] = {quad_bcast<0>(e), quad_bcast<1>(e), quad_bcast<2>(e),
+                         quad_bcast<3>(e)};
     if constexpr (use_pk_wide) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -1476,8 +1404,8 @@ __device__ __forceinline__ void sweep16(int (&c)[NC], const int32_t *__restrict_
     typedef __attribute__((address_space(3))) const float lds_cf;
     const unsigned rec0 = (unsigned)(uintptr_t)(lds_cf *)(REC + q * 2 * d4);
     auto issue = [&](float (*r)[2 * d4], int w, bool hi) {
-        const int wa = hi ? quad_bcast_i<2>(w) : quad_bcast_i<0>(w);
-        const int wb = hi ? quad_bcast_i<3>(w) : quad_bcast_i<1>(w);
+        const int wa = hi ? quad_bcast<2>(w) : quad_bcast<0>(w);
+        const int wb = hi ? quad_bcast<3>(w) : quad_bcast<1>(w);
         unsigned ad[4];
         static_assert(8 * D <= 64, "record size must be an inline constant");
         asm("v_mad_u32_u16 %0, %1, %2, %3" : "=v"(ad[0]) : "v"(wa), "n"(8 * D), "v"(rec0));
@@ -1813,12 +1741,6 @@ __global__ __launch_bounds__((Cfg<F, D>::NT)) void k_iter(
 // time, whose records fit the XCD's L2), wave w of a workgroup taking slice (w + k) & 15 of the
 // k-th tile it visits - no barrier after the staging.  The hit update runs on the matrix cores
 // from the wave's own LDS scratch (mfma_tail_scratch), 16 hits at a time.
-template <int CTRL>
-__device__ __forceinline__ float dpp_row(float v)     // row_ror:n etc.: all 16 lanes of a row are valid sources
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-
 // DL = D / 16 dims per lane; a lane's piece of a record row is [P(DL) R(DL)] bf16: 16 bytes at
 // D = 64, 8 bytes at D = 32 - one load
 template <int DL> struct PieceW;
@@ -1876,7 +1798,7 @@ struct RecW {                   // one step group (4 list steps): this lane's pi
     // of a 64-bit multiply-add; the host checks that the table is below 4 GB)
     __device__ __forceinline__ void read(int cur, const void *__restrict__ REC, unsigned lane_off)
     {
-        const int nb[4] = {quad_bcast_i<0>(cur), quad_bcast_i<1>(cur), quad_bcast_i<2>(cur), quad_bcast_i<3>(cur)};
+        const int nb[4] = {quad_bcast<0>(cur), quad_bcast<1>(cur), quad_bcast<2>(cur), quad_bcast<3>(cur)};
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             r[j].load(reinterpret_cast<const char *>(REC) + ((unsigned)nb[j] * row_bytes + lane_off));
@@ -1928,10 +1850,10 @@ __device__ __forceinline__ void score_w(const RecW<D, EX> &g, const float *own, 
     const float t0 = k0 + dpp<0xB1>(s0), t1 = k1 + dpp<0xB1>(s1);
     const float give = hi ? t0 : t1, keep = hi ? t1 : t0;
     float mine = keep + dpp<0x4E>(give);               // segment q: sum over this quad's 4 DL dims
-    mine += dpp_row<0x124>(mine);                      // row_ror:4
-    mine += dpp_row<0x128>(mine);                      // row_ror:8  -> all D dims
+    mine += dpp<0x124>(mine);                      // row_ror:4
+    mine += dpp<0x128>(mine);                      // row_ror:8  -> all D dims
     const float e = r_f(mine + b2);
-    const float e4[4] = {quad_bcast_f<0>(e), quad_bcast_f<1>(e), quad_bcast_f<2>(e), quad_bcast_f<3>(e)};
+    const float e4[4] = {quad_bcast<0>(e), quad_bcast<1>(e), quad_bcast<2>(e), quad_bcast<3>(e)};
 #pragma unroll
     for (int j = 0; j < REM; ++j) {
         float R[DL];
@@ -1993,7 +1915,7 @@ __device__ __forceinline__ void sweep_w(const int32_t *__restrict__ lst, int i16
         // share of the sum is e * 0).  `len` is wave-uniform (the slice's step count): scalar branches, no predication.
         // (k_iter2's sweep16 scores whole groups: its padding steps are LDS reads - profiles/trim_walk_ab.txt.)
         auto read_n = [&](RecW<D, EX> &g, int idx, int n) {
-            const int nb[4] = {quad_bcast_i<0>(idx), quad_bcast_i<1>(idx), quad_bcast_i<2>(idx), quad_bcast_i<3>(idx)};
+            const int nb[4] = {quad_bcast<0>(idx), quad_bcast<1>(idx), quad_bcast<2>(idx), quad_bcast<3>(idx)};
             const char *base = reinterpret_cast<const char *>(REC);
             constexpr unsigned rb = RecW<D, EX>::row_bytes;
             g.r[0].load(base + ((unsigned)nb[0] * rb + lane_off));
@@ -2036,6 +1958,120 @@ __device__ __forceinline__ void load_own_w(const unsigned *__restrict__ REC, int
     }
 }
 
+// ---- what k_iter_w and k_iter_wx share: their LDS behind the staged tables, and the walk ---------------------
+// The LDS of the two kernels behind the tables (B::lds_words<LAST>() words), in 4-byte words: the kernels lay their LDS
+// out from these, launch_wide sizes the allocation from them.  B = BL<F, D> or BX<F, D> (EX).
+template <class B, bool EX>
+struct WideLds {               // k_iter_w: scratch | sync
+    // rows of 16 hits: the double-buffered q scratch of the 4 teams (+ the 4 teams' hl scratch: exact)
+    static constexpr int scratch_rows = EX ? 2 * 4 + 4 : 2 * 4, hl_row0 = 2 * 4;
+    static constexpr int scratch_words = scratch_rows * 16 * B::tr_stride;
+    static constexpr int sync_words = 4;                        // grp[3]: the group word
+    static constexpr int words = scratch_words + sync_words;
+};
+template <class B>
+struct RingLds {               // k_iter_wx: ring | sync
+    static constexpr int NSLOT = 12, NSW = 12, NMX = 4;         // slots, sweep waves, matrix-core waves
+    static constexpr int ring_words = NSLOT * 16 * B::tr_stride;
+    static constexpr int sync_used = 3 * NSLOT + 2;             // prod[12] cons[12] meta[12] fin pha
+    static constexpr int sync_words = 40;                       // their block
+    static constexpr int words = ring_words + sync_words;
+    static_assert(sync_used <= sync_words, "the counters fit their block");
+};
+
+// the workgroup stages the bf16 (EX: fp32) fragment tables and biases of the hit update from t16 into tb (no barrier)
+template <int F, int D, bool LAST, bool EX>
+__device__ __forceinline__ void stage_wide_tables(unsigned *tb, const unsigned *__restrict__ t16)
+{
+    using B = std::conditional_t<EX, BX<F, D>, BL<F, D>>;
+    constexpr int n1 = B::NT1 * B::KS1 * (EX ? 64 : 256), nm = B::template tm_words<LAST>();
+    for (int i = threadIdx.x; i < n1; i += 1024) tb[i] = t16[B::o_t4 + i];
+    for (int i = threadIdx.x; i < nm; i += 1024) tb[n1 + i] = t16[(LAST ? B::o_tml : B::o_tmn) + i];
+    for (int i = threadIdx.x; i < D; i += 1024) tb[n1 + nm + i] = t16[B::o_b4 + i];
+    for (int i = threadIdx.x; i < (LAST ? 2 : 5) * D; i += 1024)
+        tb[n1 + nm + D + i] = t16[(LAST ? B::o_bml : B::o_bmn) + i];
+}
+
+// the group that starts at tile t (see k_iter_w), worked out by one whole wave: slices s0 .. s1 - 1, cnt tiles
+struct WideGroup { int s0, s1, cnt; };
+__device__ __forceinline__ WideGroup wide_group(const int32_t *__restrict__ tiles, int t, int t_end, int lane, int wmax)
+{
+    const int tt = t + lane;
+    const bool in = tt < t_end;
+    const int32_t *d = tiles + (int64_t)(in ? tt : t) * DESC;
+    const int s1 = d[1];
+    int ilo = in && d[3] > 0 ? d[2] : 0x7FFFFFFF, ihi = in && d[3] > 0 ? d[2] + d[3] : -1;
+    int olo = in && d[5] > 0 ? d[4] : 0x7FFFFFFF, ohi = in && d[5] > 0 ? d[4] + d[5] : -1;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {                 // inclusive prefix union of the windows
+        const int a = __shfl_up(ilo, o, 64), b = __shfl_up(ihi, o, 64);
+        const int c = __shfl_up(olo, o, 64), e = __shfl_up(ohi, o, 64);
+        if (lane >= o) {
+            ilo = a < ilo ? a : ilo; ihi = b > ihi ? b : ihi;
+            olo = c < olo ? c : olo; ohi = e > ohi ? e : ohi;
+        }
+    }
+    const bool ok = in && (lane == 0 || ((int64_t)ihi - ilo <= wmax && (int64_t)ohi - olo <= wmax));
+    const unsigned long long m = ~__ballot(ok);        // (ok is monotone along the lanes)
+    const int cnt = m ? __builtin_ctzll(m) : 64;
+    return {__shfl(d[0], 0, 64), __shfl(s1, cnt - 1, 64), cnt};
+}
+
+// phase A for hit i16 of slice sl (lane p of its 16): the segments ENDING at the hit - P[start] with the hit's own Q,
+// adds e R[start] - on top of U, parked in U again (re-read by this same lane in phase B)
+template <int D, bool XP, bool EX, bool TRIM>
+__device__ __forceinline__ void wide_in_sweep(int sl, int i16, int p, const int32_t *__restrict__ in_off,
+                                              const int32_t *__restrict__ in_nbr, const unsigned *__restrict__ PR,
+                                              const unsigned *__restrict__ QS, float *__restrict__ U, int64_t n_pad,
+                                              const float *w2, float b2)
+{
+    constexpr int DL = D / 16;
+    const int ib = __builtin_amdgcn_readfirstlane(in_off[sl]);
+    const int il = (__builtin_amdgcn_readfirstlane(in_off[sl + 1]) - ib) >> 4;
+    if (il <= 0) return;                               // (wave-uniform; U keeps the start value)
+    const int64_t n = (int64_t)sl * SLICE + i16;
+    float acc[DL], ownQ[DL];
+    load_vec<DL>(U + n * D + DL * p, acc);
+    load_own_w<D, EX>(QS, n, p, ownQ);
+#ifndef GNN_ABLATE_W_SWEEP
+    sweep_w<D, XP, EX, TRIM>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
+#endif
+    store_vec<DL>(U + n * D + DL * p, acc);
+}
+
+// phase B for the same hit up to acc = tanh(the forward's sum): U, the in-sweep when the group is not SPLIT into
+// phases, then the segments STARTING at the hit - Q[end] with the hit's own P, adds e S[end]
+template <int D, bool XP, bool EX, bool TRIM, bool SPLIT>
+__device__ __forceinline__ void wide_hit_sweeps(int sl, int i16, int p, const int32_t *__restrict__ in_off,
+                                                const int32_t *__restrict__ in_nbr,
+                                                const int32_t *__restrict__ out_off,
+                                                const int32_t *__restrict__ out_nbr, const unsigned *__restrict__ PR,
+                                                const unsigned *__restrict__ QS, const float *__restrict__ U,
+                                                int64_t n_pad, const float *w2, float b2, float *acc)
+{
+    constexpr int DL = D / 16;
+    const int ob = __builtin_amdgcn_readfirstlane(out_off[sl]);
+    const int ol = (__builtin_amdgcn_readfirstlane(out_off[sl + 1]) - ob) >> 4;
+    const int64_t n = (int64_t)sl * SLICE + i16;
+    float ownP[DL];
+    load_vec<DL>(U + n * D + DL * p, acc);
+    if constexpr (!SPLIT) {
+        const int ib = __builtin_amdgcn_readfirstlane(in_off[sl]);
+        const int il = (__builtin_amdgcn_readfirstlane(in_off[sl + 1]) - ib) >> 4;
+        float ownQ[DL];
+        load_own_w<D, EX>(QS, n, p, ownQ);
+        load_own_w<D, EX>(PR, n, p, ownP);
+        sweep_w<D, XP, EX, TRIM>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
+    } else {
+        load_own_w<D, EX>(PR, n, p, ownP);
+    }
+#ifndef GNN_ABLATE_W_SWEEP
+    sweep_w<D, XP, EX, TRIM>(out_nbr + ob, i16, ol, (int)n_pad, QS, p, ownP, w2, b2, acc);
+#endif
+#pragma unroll
+    for (int i = 0; i < DL; ++i) acc[i] = tanh_f(acc[i]);
+}
+
 // (hidden_dim 16: registers and LDS allow TWO workgroups per CU - 8 waves per SIMD - and the sweeps
 // there are bound by the latency of their dependent loads: 0.147 -> see DESIGN ms per launch at c3 x 32)
 template <int F, int D, bool LAST, bool XP, bool EX = false>
@@ -2054,23 +2090,17 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
     static_assert(D % 16 == 0, "16 lanes x D / 16 dims per hit, matrix-core tail");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // (no static LDS: the opt-in for > 64 KB of dynamic LDS is for the whole 160 KB)
-    int *grp = reinterpret_cast<int *>(smem + B::template lds_words<LAST>() + (EX ? 12 : 8) * 16 * B::tr_stride);
+    using W = WideLds<B, EX>;
+    float *scratch = smem + B::template lds_words<LAST>();
+    int *grp = reinterpret_cast<int *>(scratch + W::scratch_words);
     unsigned *tb = reinterpret_cast<unsigned *>(smem);
-    {
-        constexpr int n1 = B::NT1 * B::KS1 * (EX ? 64 : 256), nm = B::template tm_words<LAST>();
-        for (int i = threadIdx.x; i < n1; i += 1024) tb[i] = t16[B::o_t4 + i];
-        for (int i = threadIdx.x; i < nm; i += 1024) tb[n1 + i] = t16[(LAST ? B::o_tml : B::o_tmn) + i];
-        for (int i = threadIdx.x; i < D; i += 1024) tb[n1 + nm + i] = t16[B::o_b4 + i];
-        for (int i = threadIdx.x; i < (LAST ? 2 : 5) * D; i += 1024)
-            tb[n1 + nm + D + i] = t16[(LAST ? B::o_bml : B::o_bmn) + i];
-    }
+    stage_wide_tables<F, D, LAST, EX>(tb, t16);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int hs = lane >> 4, p = lane & 15;
     // Teams: 4 waves share a slice (wave m of team t sweeps hits 4m .. 4m+3), so only 4 slices per
     // CU = 2048 hits per XCD are in progress at a time.  The team's scratch is double-buffered: one
     // barrier per round.
     const int team = wv >> 2, mem = wv & 3;
-    float *scratch = smem + B::template lds_words<LAST>();
     constexpr int DL = D / 16;                         // dims per lane
     float w2[DL];
 #pragma unroll
@@ -2095,26 +2125,8 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
     int buf = 0, rot = 0;
     for (int t = t_begin; t < t_end;) {
         if (wv == 0) {                                 // the next group: tiles t .. t + cnt - 1
-            const int tt = t + lane;
-            const bool in = tt < t_end;
-            const int32_t *d = tiles + (int64_t)(in ? tt : t) * DESC;
-            const int s1 = d[1];
-            int ilo = in && d[3] > 0 ? d[2] : 0x7FFFFFFF, ihi = in && d[3] > 0 ? d[2] + d[3] : -1;
-            int olo = in && d[5] > 0 ? d[4] : 0x7FFFFFFF, ohi = in && d[5] > 0 ? d[4] + d[5] : -1;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {         // inclusive prefix union of the windows
-                const int a = __shfl_up(ilo, o, 64), b = __shfl_up(ihi, o, 64);
-                const int c = __shfl_up(olo, o, 64), e = __shfl_up(ohi, o, 64);
-                if (lane >= o) {
-                    ilo = a < ilo ? a : ilo; ihi = b > ihi ? b : ihi;
-                    olo = c < olo ? c : olo; ohi = e > ohi ? e : ohi;
-                }
-            }
-            const bool ok = in && (lane == 0 || ((int64_t)ihi - ilo <= wmax && (int64_t)ohi - olo <= wmax));
-            const unsigned long long m = ~__ballot(ok);          // (ok is monotone along the lanes)
-            const int cnt = m ? __builtin_ctzll(m) : 64;
-            const int send = __shfl(s1, cnt - 1, 64);
-            if (lane == 0) { grp[0] = d[0]; grp[1] = send; grp[2] = t + cnt; }
+            const WideGroup g = wide_group(tiles, t, t_end, lane, wmax);
+            if (lane == 0) { grp[0] = g.s0; grp[1] = g.s1; grp[2] = t + g.cnt; }
         }
         __syncthreads();
         const int sg0 = grp[0], sg1 = grp[1];
@@ -2135,18 +2147,7 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
         for (int q = q0; SPLIT && x0 + 4 * q < sg1; q += per_xcd) {
             const int sl = x0 + 4 * q + team;
             if (sl < sg0 || sl >= sg1) continue;
-            const int ib = __builtin_amdgcn_readfirstlane(in_off[sl]);
-            const int il = (__builtin_amdgcn_readfirstlane(in_off[sl + 1]) - ib) >> 4;
-            if (il <= 0) continue;                     // (wave-uniform; U keeps the start value)
-            const int i16 = 4 * mem + hs;
-            const int64_t n = (int64_t)sl * SLICE + i16;
-            float acc[DL], ownQ[DL];
-            load_vec<DL>(U + n * D + DL * p, acc);
-            load_own_w<D, EX>(QS, n, p, ownQ);
-#ifndef GNN_ABLATE_W_SWEEP
-            sweep_w<D, XP, EX, TRIMW>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
-#endif
-            store_vec<DL>(U + n * D + DL * p, acc);    // (re-read by this same lane in phase B)
+            wide_in_sweep<D, XP, EX, TRIMW>(sl, 4 * mem + hs, p, in_off, in_nbr, PR, QS, U, n_pad, w2, b2);
         }
         // ---- phase B: segments STARTING at the hit, then the hit update and the next records
         for (int q = q0; x0 + 4 * q < sg1; q += per_xcd, buf ^= 1) {   // workgroup-uniform trip count
@@ -2154,27 +2155,11 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
             const bool on = sl >= sg0 && sl < sg1;
             float *tr = scratch + (buf * 4 + team) * 16 * B::tr_stride;
             if (on) {
-                const int ob = __builtin_amdgcn_readfirstlane(out_off[sl]);
-                const int ol = (__builtin_amdgcn_readfirstlane(out_off[sl + 1]) - ob) >> 4;
                 const int i16 = 4 * mem + hs;
                 const int64_t n = (int64_t)sl * SLICE + i16;
-                float acc[DL], ownP[DL];
-                load_vec<DL>(U + n * D + DL * p, acc);
-                if constexpr (!SPLIT) {
-                    const int ib = __builtin_amdgcn_readfirstlane(in_off[sl]);
-                    const int il = (__builtin_amdgcn_readfirstlane(in_off[sl + 1]) - ib) >> 4;
-                    float ownQ[DL];
-                    load_own_w<D, EX>(QS, n, p, ownQ);
-                    load_own_w<D, EX>(PR, n, p, ownP);
-                    sweep_w<D, XP, EX, TRIMW>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
-                } else {
-                    load_own_w<D, EX>(PR, n, p, ownP);
-                }
-#ifndef GNN_ABLATE_W_SWEEP
-                sweep_w<D, XP, EX, TRIMW>(out_nbr + ob, i16, ol, (int)n_pad, QS, p, ownP, w2, b2, acc);
-#endif
-#pragma unroll
-                for (int i = 0; i < DL; ++i) acc[i] = tanh_f(acc[i]);
+                float acc[DL];
+                wide_hit_sweeps<D, XP, EX, TRIMW, SPLIT>(sl, i16, p, in_off, in_nbr, out_off, out_nbr, PR, QS, U,
+                                                         n_pad, w2, b2, acc);
                 store_vec<DL>(tr + i16 * B::tr_stride + DL * p, acc);
                 if (p < F) tr[i16 * B::tr_stride + D + p] = X[n * F + p];
             }
@@ -2183,7 +2168,7 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_w(
             // the next pass (model.py:94-98,125)
             if constexpr (EX) {
                 // exact fp32: the team splits the tiles of hl = tanh(W4 q + b4) and meets again in th
-                float *th = scratch + (8 + team) * 16 * B::tr_stride;
+                float *th = scratch + (W::hl_row0 + team) * 16 * B::tr_stride;
 #ifndef GNN_ABLATE_W_TAIL
                 if (on) mfma_hidden_x<F, D, LAST>(smem, tr, th, lane, mem);
 #endif
@@ -2243,22 +2228,15 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_wx(
 {
     using L = TL<F, D>;
     using B = std::conditional_t<EX, BX<F, D>, BL<F, D>>;
-    constexpr int DL = D / 16, NSLOT = 12, NSW = 12, NMX = 4, NTEAM = NSW / 4;   // slots, sweep waves, matrix-core waves
+    using W = RingLds<B>;
+    constexpr int DL = D / 16, NSLOT = W::NSLOT, NSW = W::NSW, NMX = W::NMX, NTEAM = NSW / 4;
     constexpr int n1 = B::NT1 * B::KS1 * (EX ? 64 : 256), nm = B::template tm_words<LAST>();
-    typedef float f4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *ring = smem + B::template lds_words<LAST>();
-    int *sync = reinterpret_cast<int *>(ring + NSLOT * 16 * B::tr_stride);   // prod[12] cons[12] meta[12] fin
+    int *sync = reinterpret_cast<int *>(ring + W::ring_words);               // prod[12] cons[12] meta[12] fin pha
     int *prod = sync, *cons = sync + NSLOT, *meta = sync + 2 * NSLOT, *fin = sync + 3 * NSLOT, *pha = fin + 1;
-    {
-        unsigned *tb = reinterpret_cast<unsigned *>(smem);
-        for (int i = threadIdx.x; i < n1; i += 1024) tb[i] = t16[B::o_t4 + i];
-        for (int i = threadIdx.x; i < nm; i += 1024) tb[n1 + i] = t16[(LAST ? B::o_tml : B::o_tmn) + i];
-        for (int i = threadIdx.x; i < D; i += 1024) tb[n1 + nm + i] = t16[B::o_b4 + i];
-        for (int i = threadIdx.x; i < (LAST ? 2 : 5) * D; i += 1024)
-            tb[n1 + nm + D + i] = t16[(LAST ? B::o_bml : B::o_bmn) + i];
-        if (threadIdx.x < 3 * NSLOT + 2) sync[threadIdx.x] = 0;
-    }
+    stage_wide_tables<F, D, LAST, EX>(reinterpret_cast<unsigned *>(smem), t16);
+    if (threadIdx.x < W::sync_used) sync[threadIdx.x] = 0;
     __syncthreads();                                   // the only workgroup barrier
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     auto ld = [](const int *w) { return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
@@ -2295,7 +2273,7 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_wx(
             if (sl >= 0) {
 #pragma unroll
                 for (int t = 0; t < B::NT1; ++t) {
-                    const f4v r = *reinterpret_cast<const f4v *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
+                    const f4_t r = *reinterpret_cast<const f4_t *>(tr + hit * B::tr_stride + 16 * t + 4 * g);
                     v[t][0] = r.x; v[t][1] = r.y; v[t][2] = r.z; v[t][3] = r.w;
                 }
                 xb = g < F ? tr[hit * B::tr_stride + D + (g < F ? g : 0)] : 0.0f;
@@ -2308,7 +2286,7 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_wx(
             float h[B::NT1][4];
 #pragma unroll
             for (int T = 0; T < B::NT1; ++T) {
-                f4v c = *reinterpret_cast<const f4v *>(b4 + 16 * T + 4 * g);
+                f4_t c = *reinterpret_cast<const f4_t *>(b4 + 16 * T + 4 * g);
 #pragma unroll
                 for (int st = 0; st < B::KS1; ++st)
                     c = __builtin_amdgcn_mfma_f32_16x16x4f32(T4[(T * B::KS1 + st) * 64 + lane], v[st / 4][st % 4], c, 0, 0, 0);
@@ -2335,30 +2313,9 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_wx(
     constexpr bool SPLIT = EX && D >= 64;
     int rot = 0, seq = team, ngrp = 0;                 // seq: this team's next slot sequence number
     for (int t = t_begin; t < t_end;) {
-        int sg0, sg1;
-        {
-            const int tt = t + lane;
-            const bool in = tt < t_end;
-            const int32_t *d = tiles + (int64_t)(in ? tt : t) * DESC;
-            const int s1 = d[1];
-            int ilo = in && d[3] > 0 ? d[2] : 0x7FFFFFFF, ihi = in && d[3] > 0 ? d[2] + d[3] : -1;
-            int olo = in && d[5] > 0 ? d[4] : 0x7FFFFFFF, ohi = in && d[5] > 0 ? d[4] + d[5] : -1;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int a = __shfl_up(ilo, o, 64), b = __shfl_up(ihi, o, 64);
-                const int c = __shfl_up(olo, o, 64), e = __shfl_up(ohi, o, 64);
-                if (lane >= o) {
-                    ilo = a < ilo ? a : ilo; ihi = b > ihi ? b : ihi;
-                    olo = c < olo ? c : olo; ohi = e > ohi ? e : ohi;
-                }
-            }
-            const bool ok = in && (lane == 0 || ((int64_t)ihi - ilo <= wmax && (int64_t)ohi - olo <= wmax));
-            const unsigned long long m = ~__ballot(ok);
-            const int cnt = m ? __builtin_ctzll(m) : 64;
-            sg1 = __builtin_amdgcn_readfirstlane(__shfl(s1, cnt - 1, 64));
-            sg0 = __builtin_amdgcn_readfirstlane(__shfl(d[0], 0, 64));
-            t += cnt;
-        }
+        const WideGroup g = wide_group(tiles, t, t_end, lane, wmax);
+        const int sg0 = __builtin_amdgcn_readfirstlane(g.s0), sg1 = __builtin_amdgcn_readfirstlane(g.s1);
+        t += g.cnt;
         const int nq = (sg1 - sg0 + NTEAM - 1) / NTEAM;            // "quads" of three slices here
         const int q0 = (((local - rot) % per_xcd) + per_xcd) % per_xcd;
         rot = (rot + nq) % per_xcd;
@@ -2366,16 +2323,7 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_wx(
         for (int q = q0; SPLIT && sg0 + NTEAM * q < sg1; q += per_xcd) {
             const int sl = sg0 + NTEAM * q + team;
             if (sl >= sg1) continue;
-            const int ib = __builtin_amdgcn_readfirstlane(in_off[sl]);
-            const int il = (__builtin_amdgcn_readfirstlane(in_off[sl + 1]) - ib) >> 4;
-            if (il <= 0) continue;
-            const int i16 = 4 * mem + hs;
-            const int64_t n = (int64_t)sl * SLICE + i16;
-            float acc[DL], ownQ[DL];
-            load_vec<DL>(U + n * D + DL * p, acc);
-            load_own_w<D, EX>(QS, n, p, ownQ);
-            sweep_w<D, XP, EX>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
-            store_vec<DL>(U + n * D + DL * p, acc);
+            wide_in_sweep<D, XP, EX, true>(sl, 4 * mem + hs, p, in_off, in_nbr, PR, QS, U, n_pad, w2, b2);
         }
         if constexpr (SPLIT) {
             // the sweep waves of the workgroup change phase TOGETHER (an LDS counter, the matrix-core
@@ -2390,27 +2338,9 @@ __global__ __launch_bounds__(1024, (D == 16 ? 8 : 4)) void k_iter_wx(
             const int sl = sg0 + NTEAM * q + team;
             const bool on = sl < sg1;
             float acc[DL];
-            if (on) {
-                const int ob = __builtin_amdgcn_readfirstlane(out_off[sl]);
-                const int ol = (__builtin_amdgcn_readfirstlane(out_off[sl + 1]) - ob) >> 4;
-                const int i16 = 4 * mem + hs;
-                const int64_t n = (int64_t)sl * SLICE + i16;
-                float ownP[DL];
-                load_vec<DL>(U + n * D + DL * p, acc);
-                if constexpr (!SPLIT) {
-                    const int ib = __builtin_amdgcn_readfirstlane(in_off[sl]);
-                    const int il = (__builtin_amdgcn_readfirstlane(in_off[sl + 1]) - ib) >> 4;
-                    float ownQ[DL];
-                    load_own_w<D, EX>(QS, n, p, ownQ);
-                    load_own_w<D, EX>(PR, n, p, ownP);
-                    sweep_w<D, XP, EX>(in_nbr + ib, i16, il, (int)n_pad, PR, p, ownQ, w2, b2, acc);
-                } else {
-                    load_own_w<D, EX>(PR, n, p, ownP);
-                }
-                sweep_w<D, XP, EX>(out_nbr + ob, i16, ol, (int)n_pad, QS, p, ownP, w2, b2, acc);
-#pragma unroll
-                for (int i = 0; i < DL; ++i) acc[i] = tanh_f(acc[i]);
-            }
+            if (on)
+                wide_hit_sweeps<D, XP, EX, true, SPLIT>(sl, 4 * mem + hs, p, in_off, in_nbr, out_off, out_nbr, PR, QS, U,
+                                                        n_pad, w2, b2, acc);
             // the slot of sequence number seq: free once its previous generation has been taken
             const int slot = seq % NSLOT, gen = seq / NSLOT;
             for (int spins = 0; spins < kSpinLimit && ld(cons + slot) < gen; ++spins) __builtin_amdgcn_s_sleep(2);
@@ -2698,7 +2628,6 @@ __global__ __launch_bounds__(1024) void k_iter2(
             // Lane l supplies input slot l >> 4 of hit l & 15 per k-step and receives positions
             // 4 (l >> 4) .. + 3 of that hit's record - one 16-byte LDS store.  4 MFMAs per 16 hits
             // instead of ~100 vector instructions per lane.
-            typedef float f4v __attribute__((ext_vector_type(4)));
             using MTL = MT<F, D>;
             const float *mb = mt + MTL::o_b;
             const int hit = lane & 15, g = lane >> 4;
@@ -2707,8 +2636,8 @@ __global__ __launch_bounds__(1024) void k_iter2(
             float ar[MTL::NS];
 #pragma unroll
             for (int st = 0; st < MTL::NS; ++st) ar[st] = mt[MTL::o_t + MTL::t_sz * M + 64 * st + lane];
-            const f4v bias0 = *reinterpret_cast<const f4v *>(mb + 4 * g);
-            const f4v biasr = *reinterpret_cast<const f4v *>(mb + 16 + 16 * M + 4 * g);
+            const f4_t bias0 = *reinterpret_cast<const f4_t *>(mb + 4 * g);
+            const f4_t biasr = *reinterpret_cast<const f4_t *>(mb + 16 + 16 * M + 4 * g);
             for (int r = 0; r < rounds; ++r) {
                 const int h = (r * NWV + wv) * 16 + hit;
                 const bool live = h < cnt;
@@ -2719,12 +2648,12 @@ __global__ __launch_bounds__(1024) void k_iter2(
                 float b0 = 0.0f;
 #pragma unroll
                 for (int k = 0; k < F; ++k) b0 = (g == k) ? xs[k] : b0;
-                f4v hq = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, bias0, 0, 0, 0);
+                f4_t hq = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, bias0, 0, 0, 0);
                 const float hh[4] = {tanh_f(hq.x), tanh_f(hq.y), tanh_f(hq.z), tanh_f(hq.w)};
                 // features 3 and 7 (held by lane groups 0 and 1) for lane group 2, see MT::slot_k
                 const float h3a = __int_as_float(__builtin_amdgcn_ds_bpermute(hit << 2, __float_as_int(hh[3])));
                 const float h3b = __int_as_float(__builtin_amdgcn_ds_bpermute((16 + hit) << 2, __float_as_int(hh[3])));
-                f4v c = biasr;
+                f4_t c = biasr;
 #pragma unroll
                 for (int st = 0; st < MTL::NS; ++st) {
                     float b = hh[st];
@@ -2736,7 +2665,7 @@ __global__ __launch_bounds__(1024) void k_iter2(
                     c.x = __builtin_amdgcn_exp2f(c.x);
                     c.y = __builtin_amdgcn_exp2f(c.y);
                 }
-                if (live) *reinterpret_cast<f4v *>(buf + h * 2 * D + 4 * g) = c;
+                if (live) *reinterpret_cast<f4_t *>(buf + h * 2 * D + 4 * g) = c;
             }
             null_fence();
             put_null(buf, cnt, which);
@@ -3005,7 +2934,6 @@ __global__ __launch_bounds__(1024) void k_iter2(
                     // slots of group g) with two ds_bpermute, X with F more; everything after
                     // that, stores included, stays in the product's layout.
                     using MTL = MT<F, D>;
-                    typedef float f4v __attribute__((ext_vector_type(4)));
                     const float *mb = mt + MTL::o_b;
                     const int hit = lane & 15, g = lane >> 4;
                     const int from = ((hit << 2) | g) << 2;          // byte index of the source lane
@@ -3016,7 +2944,7 @@ __global__ __launch_bounds__(1024) void k_iter2(
                     for (int k = 0; k < F; ++k)
                         xm[k] = __int_as_float(__builtin_amdgcn_ds_bpermute(hit << 4, __float_as_int(xv[k])));
                     // H' = tanh(W4 q + b4): slot (s, g) = feature 2 g + s          (model.py:94-98,125)
-                    f4v h = *reinterpret_cast<const f4v *>(mb + 64 + 4 * g);
+                    f4_t h = *reinterpret_cast<const f4_t *>(mb + 64 + 4 * g);
                     h = __builtin_amdgcn_mfma_f32_16x16x4f32(mt[MTL::o_w4 + lane], q0, h, 0, 0, 0);
                     h = __builtin_amdgcn_mfma_f32_16x16x4f32(mt[MTL::o_w4 + 64 + lane], q1, h, 0, 0, 0);
                     const float hh[4] = {tanh_f(h.x), tanh_f(h.y), tanh_f(h.z), tanh_f(h.w)};
@@ -3055,7 +2983,7 @@ __global__ __launch_bounds__(1024) void k_iter2(
                     constexpr int NP = LAST ? 1 : 3;
 #pragma unroll
                     for (int T = 0; T < NP; ++T) {
-                        f4v c = *reinterpret_cast<const f4v *>(mb + 16 * (1 + T) + 4 * g);
+                        f4_t c = *reinterpret_cast<const f4_t *>(mb + 16 * (1 + T) + 4 * g);
 #pragma unroll
                         for (int st = 0; st < MTL::NS; ++st)
                             c = __builtin_amdgcn_mfma_f32_16x16x4f32(mt[MTL::o_t + MTL::t_sz * T + 64 * st + lane],
@@ -3065,15 +2993,15 @@ __global__ __launch_bounds__(1024) void k_iter2(
                                 c.x = __builtin_amdgcn_exp2f(c.x); c.y = __builtin_amdgcn_exp2f(c.y);
                                 c.z = __builtin_amdgcn_exp2f(c.z); c.w = __builtin_amdgcn_exp2f(c.w);
                             }
-                            *reinterpret_cast<f4v *>((g < 2 ? Pc : Qc) + n * D + 4 * (g & 1)) = c;
+                            *reinterpret_cast<f4_t *>((g < 2 ? Pc : Qc) + n * D + 4 * (g & 1)) = c;
                         } else if (T < 2) {            // [P|R] / [Q|S]: this lane's 16-byte chunk g
                             if constexpr (XP) {
                                 c.x = __builtin_amdgcn_exp2f(c.x);
                                 c.y = __builtin_amdgcn_exp2f(c.y);
                             }
-                            *reinterpret_cast<f4v *>((T == 0 ? PRn : QSn) + n * 2 * D + 4 * g) = c;
+                            *reinterpret_cast<f4_t *>((T == 0 ? PRn : QSn) + n * 2 * D + 4 * g) = c;
                         } else if (g < 2) {            // U: rows 0..7
-                            *reinterpret_cast<f4v *>(U + n * D + 4 * g) = c;
+                            *reinterpret_cast<f4_t *>(U + n * D + 4 * g) = c;
                         }
                     }
                 }
@@ -3243,8 +3171,8 @@ __global__ __launch_bounds__(256) void k_edge_w(const int32_t *__restrict__ src,
         for (int i = 0; i < DL; ++i)
             acc = fmaf(w2[i], XP ? __builtin_amdgcn_rcpf(fmaf(P[i], Q[i], 1.0f)) : r_f(P[i] + Q[i]), acc);
         acc = quad_sum(acc);
-        acc += dpp_row<0x124>(acc);
-        acc += dpp_row<0x128>(acc);
+        acc += dpp<0x124>(acc);
+        acc += dpp<0x128>(acc);
         if (p == 0 && j < hi) e[j] = r_f(acc + b2);
     };
     // 16 segments per wave trip (4 passes of 4): all endpoint loads first, then all row loads, then the
@@ -3560,19 +3488,16 @@ int launch_wide(const Run &c, bool last)
     return with_flag(last, [&](auto last_c) {
         constexpr bool LAST = decltype(last_c)::value;
         if (c.r.family == GNN_FAMILY_K_ITER_WX) {
-            const size_t ringw = (size_t)12 * 16 * B::tr_stride + 40;      // 12 slots + the counters (38 words)
             lds_opt_in<&k_iter_wx<F, D, LAST, XP, EX>>(G::lds_bytes);
             GNN_LAUNCH_SH("k_iter_wx", (k_iter_wx<F, D, LAST, XP, EX>), wgs, 1024,
-                          (B::template lds_words<LAST>() + ringw) * 4, c.s, pl->X, w.table, w.t16, pl->tiles, pl->in_off,
-                          pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, tpx,
+                          (size_t)(B::template lds_words<LAST>() + RingLds<B>::words) * 4, c.s, pl->X, w.table, w.t16,
+                          pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, tpx,
                           nt, c.r.wmax);
         } else {
-            // double-buffered q scratch of the 4 teams (+ the hl scratch: exact) + the group word
-            const size_t trw = (size_t)(EX ? 2 * 4 + 4 : 2 * 4) * 16 * B::tr_stride + 4;
             lds_opt_in<&k_iter_w<F, D, LAST, XP, EX>>(G::lds_bytes);
             GNN_LAUNCH_SH("k_iter_w", (k_iter_w<F, D, LAST, XP, EX>), wgs, 1024,
-                          (B::template lds_words<LAST>() + trw) * 4, c.s, pl->X, w.table, w.t16, pl->tiles, pl->in_off,
-                          pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, tpx,
+                          (size_t)(B::template lds_words<LAST>() + WideLds<B, EX>::words) * 4, c.s, pl->X, w.table, w.t16,
+                          pl->tiles, pl->in_off, pl->in_nbr, pl->out_off, pl->out_nbr, PRh, QSh, w.U, c.PRn, c.QSn, w.Pc, w.Qc, pl->n_pad, tpx,
                           nt, c.r.wmax);
         }
         return 0;

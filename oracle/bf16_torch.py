@@ -13,32 +13,34 @@ Per-hit records of H = [h | X] (C = F + D columns; K = kTwoLog2e = 2 log2(e), th
                          e_j = sigmoid(W2 tanh(.) + b2)
     node sum of hit n:   U_n + sum_{d_j = n} e_j R_{s_j} + sum_{s_j = n} e_j S_{d_j};  h' = tanh(W4 tanh(sum) + b4)
 
-What the kernels round (sell_pipeline.hip line numbers), each point emulated below:
+What the kernels round (functions of sell_pipeline.hip), each point emulated below:
 
-  rounding     fp32 -> bf16, round to nearest even: bf16_rne (526, integer form, k_pack16 and the X step) and
-               pack_bf16 (534, v_cvt_pk_bf16_f32, activations and records); here through fp32 first, as the device
-               holds the value, then torch.bfloat16 (RNE; pinned to bf16_rne's formula by the host test)
-  weights      k_pack16 (606-650), once per forward: W4 (632); the record rows of record_weight (570-603): P and Q
-               rows = kTwoLog2e * W1 (598, 600) scaled in fp32 THEN rounded (644); R, S, U = the three C-wide
-               blocks of W3 (599, 601, 602), rounded (644).  Biases stay fp32 (646-652): b4, kTwoLog2e * b1, b3.
+  rounding     fp32 -> bf16, round to nearest even: bf16_rne (integer form, k_pack16 and the X step) and pack_bf16
+               (v_cvt_pk_bf16_f32, activations and records); here through fp32 first, as the device holds the
+               value, then torch.bfloat16 (RNE; pinned to bf16_rne's formula by the host test)
+  weights      k_pack16, once per forward: W4; the record rows of record_weight: P and Q rows = kTwoLog2e * W1
+               scaled in fp32 THEN rounded (k_pack16's bf16_rne); R, S, U = the three C-wide blocks of W3, rounded
+               there too.  Biases stay fp32 (k_pack16's last loops): b4, kTwoLog2e * b1, b3.
                Win / bin, W2 / b2 stay fp32 (k_pack's table: the input network and the score).
-  H0           k_input4_bf (963-1023): tanh(Win X + bin) in fp32 (role_gemv and tanh_f, 990-996), rounded when
-               used by the record product (act_frag 657-663 inside mfma_records 738-740); X rounded in the X step (1014)
-  node hidden  q = tanh(sweep sum) (k_iter_w 2025 / k_iter_wx 2260, fp32, stored to the scratch), rounded
-               as the W4 product's B operand (mfma_tail_scratch 709-711); hl = tanh(W4 q + b4) (712-719) rounded as
-               the record product's B operand (740); X rounded again in the X step (707)
-  products     fp32 accumulation on v_mfma_f32_16x16x32_bf16 (717, 750), bias as the accumulator's start (714, 747)
-  records      mfma_records (727-786): P, R, Q, S stored as bf16 (773-776, pack_bf16 after the exp2 of 767-770 in
-               XP mode: P and Q are 2^x rounded, not 2^(rounded x)); U stays fp32 (778); the LAST iteration's
-               Pc / Qc stay fp32 (757, 778) and k_edge_w (3051-3100) scores them with fp32 W2 / b2
-  sweep        score_w (1780-1843): edge scores from the bf16 P / Q rows (the hit's own value through load_own_w,
-               1876-1890, is a bf16 row as well), fp32 arithmetic; node sums over the bf16 R / S rows (1829-1842)
-               with fp32 e, starting from the fp32 U (2010, 2247)
-  NULL rows    k_pack16 (612-623): P = bf16(kTwoLog2e b1), bf16(2^that) in XP mode; Q = 0, 1 in XP mode; R = S = 0.
-               The sweeps read them only for the SELL padding past a list's end (sweep_w's index_of, 1856-1858),
+  H0           k_input4_bf: tanh(Win X + bin) in fp32 (role_gemv and tanh_f), rounded when used by the record
+               product (act_frag inside mfma_records); X rounded in k_input4_bf's X step
+  node hidden  q = tanh(sweep sum) (wide_hit_sweeps, called by k_iter_w and k_iter_wx; fp32, stored to the scratch),
+               rounded as the W4 product's B operand (mfma_tail_scratch); hl = tanh(W4 q + b4) (mfma_tail_scratch)
+               rounded as the record product's B operand (mfma_records' act_frag); X rounded again in
+               mfma_tail_scratch's X step
+  products     fp32 accumulation on v_mfma_f32_16x16x32_bf16 (mfma_tail_scratch, mfma_records), bias as the
+               accumulator's start
+  records      mfma_records: P, R, Q, S stored as bf16 (pack_bf16 after the exp2 in XP mode: P and Q are 2^x
+               rounded, not 2^(rounded x)); U stays fp32; the LAST iteration's Pc / Qc stay fp32 and k_edge_w
+               scores them with fp32 W2 / b2
+  sweep        score_w: edge scores from the bf16 P / Q rows (the hit's own value through load_own_w is a bf16 row
+               as well), fp32 arithmetic; node sums over the bf16 R / S rows (score_w's second loop) with fp32 e,
+               starting from the fp32 U (wide_in_sweep, wide_hit_sweeps)
+  NULL rows    k_pack16: P = bf16(kTwoLog2e b1), bf16(2^that) in XP mode; Q = 0, 1 in XP mode; R = S = 0.
+               The sweeps read them only for the SELL padding past a list's end (sweep_w's index_of),
                where R = S = 0 makes the step add nothing: the node sums here run over the valid segments only.
                Padded segments (src = dst = -1) are scored by k_edge_w from the fp32 NULL rows of Pc / Qc
-               (write_null_rows 169-174): P = kTwoLog2e b1 (2^that in XP mode), Q = 0 (1).
+               (write_null_rows): P = kTwoLog2e b1 (2^that in XP mode), Q = 0 (1).
   route        choose_route: bf16 only for D in {32, 64}, F <= 8, n_iters > 0 and (Np + 2) D 4 < 2^32;
                n_iters = 0 declines it (the fp32 path runs)
 
@@ -63,7 +65,7 @@ import math
 
 import torch
 
-K32 = torch.tensor(2.8853900817779268, dtype=torch.float32)       # kTwoLog2e (sell_pipeline.hip:89) in fp32
+K32 = torch.tensor(2.8853900817779268, dtype=torch.float32)       # kTwoLog2e (sell_pipeline.hip) in fp32
 K64 = 2.0 / math.log(2.0)
 
 PERTURBATIONS = ("trunc", "x_unrounded", "q_unrounded", "records_fp32", "scale_after_round", "exp2_after_round",
