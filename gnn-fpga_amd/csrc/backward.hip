@@ -2402,9 +2402,13 @@ __global__ __launch_bounds__(kBlock) void k_bce(const float *__restrict__ e, con
     float acc = 0.0f;
     for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (int64_t)gridDim.x * kBlock) {
         const float ej = e[j], yj = y[j];
-        const float l1 = fmaxf(logf(ej), -100.0f), l0 = fmaxf(log1pf(-ej), -100.0f);
+        // the clamps let NaN through (fmaxf would return the bound): a score that is NaN or outside [0, 1] has a
+        // NaN logarithm, hence a NaN term; its e (1 - e) is negative or NaN, and the gradient is made NaN to match
+        const float g1 = logf(ej), g0 = log1pf(-ej), den = ej * (1.0f - ej);
+        const float l1 = g1 < -100.0f ? -100.0f : g1, l0 = g0 < -100.0f ? -100.0f : g0;
         acc -= yj * l1 + (1.0f - yj) * l0;
-        if (grad_e) grad_e[j] = scale * (ej - yj) / fmaxf(ej * (1.0f - ej), 1e-12f);
+        if (grad_e)
+            grad_e[j] = den >= 0.0f ? scale * (ej - yj) / (den < 1e-12f ? 1e-12f : den) : __builtin_nanf("");
     }
     red[threadIdx.x] = acc;
     __syncthreads();

@@ -13,7 +13,7 @@
 //                             column lists (no float atomics), weight gradients are per-graph partial sums
 //   k_gcn_reduce              one fixed-order sum of the partial sums over the graphs
 //
-// Math (ReLU derivative [z > 0], i.e. the mask is h > 0 of the stored post-ReLU h):
+// Math (ReLU derivative [z > 0], i.e. the mask is h > 0 of the stored post-ReLU h - or h NaN: relu_f, relu_open):
 //   h0 = relu(x Wf^T + bf);  per layer hin = h (GCN) or [h | x] (GCRN)
 //   GraphConvSelfInt: z = hin Wn^T + bn + (A hin) Wg^T        GraphConv: z = (A hin) Wl^T + bl
 //   h' = relu(z);  out = h Wc^T + bc
@@ -61,6 +61,12 @@ __device__ __forceinline__ float sum4(int n, Term term)
     if (i + 2 < n) s2 += term(i + 2);
     return (s0 + s1) + (s2 + s3);
 }
+
+// ReLU as torch computes it: relu(NaN) = NaN (fmaxf(NaN, 0) is 0), and its derivative lets the gradient through
+// wherever h <= 0 does not hold - at h > 0 and at a NaN h (threshold_backward).  A NaN weight or feature then reaches
+// the logits and the gradients instead of turning into a plausible zero.
+__device__ __forceinline__ float relu_f(float z) { return z <= 0.0f ? 0.0f : z; }
+__device__ __forceinline__ bool relu_open(float h) { return !(h <= 0.0f); }
 
 // ---- compression ---------------------------------------------------------------------------------------------------
 // info[0] = widest list (atomicMax), info[1] = status (bit 0: a non-finite entry).  Integer atomics only.
@@ -161,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_gcn_fwd(gnn_gcn_adj_t adj, gnn_gcn_n
             const int i = t / d, o = t - i * d;
             float acc = net.bf[o];
             for (int f = 0; f < F; ++f) acc = fmaf(xs[i * F + f], net.Wf[o * F + f], acc);
-            acc = fmaxf(acc, 0.0f);
+            acc = relu_f(acc);
             hA[i * ld + o] = acc;
             if (Hb) Hb[(size_t)i * maxw + o] = acc;
         }
@@ -215,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_gcn_fwd(gnn_gcn_adj_t adj, gnn_gcn_n
                     if (Wn)
                         for (int c = 0; c < cin; ++c) an = fmaf(hi[c], Wn[o * cin + c], an);
                 }
-                z = fmaxf(an + ag, 0.0f);
+                z = relu_f(an + ag);
             }
             __syncthreads();
             if (active) {
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(kBlock) void k_gcn_bwd(gnn_gcn_adj_t adj, gnn_gcn_n
         }
         for (int t = tid; t < N * dL; t += kBlock) {
             const int i = t / dL, o = t - i * dL;
-            G[i * ld + o] = HL[(size_t)i * maxw + o] > 0.0f ? go[i] * net.Wc[o] : 0.0f;
+            G[i * ld + o] = relu_open(HL[(size_t)i * maxw + o]) ? go[i] * net.Wc[o] : 0.0f;
         }
     }
     __syncthreads();
@@ -306,7 +312,7 @@ __global__ __launch_bounds__(kBlock) void k_gcn_bwd(gnn_gcn_adj_t adj, gnn_gcn_n
             const int i = i0 + r;
             const bool active = r < rpp && i < N;
             float g = 0.0f;
-            if (active && Hin[(size_t)i * maxw + c] > 0.0f) {
+            if (active && relu_open(Hin[(size_t)i * maxw + c])) {
                 float an = 0.0f, ag = 0.0f;
                 const float *gi = G + i * ld, *qi = Q + i * ld;
                 for (int o = 0; o < dout; ++o) ag = fmaf(qi[o], Wg[o * cin + c], ag);

@@ -971,6 +971,10 @@ int run_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_p
     return 0;
 }
 
+// max that keeps a NaN (fmaxf drops it): a NaN weight, a NaN feature range or 0 * inf makes the bound NaN, and a NaN
+// bound is not "<= 60" - the caller does not take the exp-product form on a bound that was never computed
+__device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : b != b ? b : b > a ? b : a; }
+
 // bound of |P'|, |Q'| over all hits given |H'| <= 1 and per-feature max |X| (one wavefront)
 __global__ __launch_bounds__(64) void k_exp_bound(const float *__restrict__ W1,
                                                  const float *__restrict__ b1,
@@ -986,9 +990,9 @@ __global__ __launch_bounds__(64) void k_exp_bound(const float *__restrict__ W1,
             const float w = fabsf(W1[row * 2 * C + half * C + k]);
             acc += k < D ? w : w * xmax[k - D];
         }
-        worst = fmaxf(worst, acc);
+        worst = max_nan(worst, acc);
     }
-    for (int o = 32; o > 0; o >>= 1) worst = fmaxf(worst, __shfl_xor(worst, o));
+    for (int o = 32; o > 0; o >>= 1) worst = max_nan(worst, __shfl_xor(worst, o));
     if (threadIdx.x == 0) out[0] = 2.8853900817779268f * worst;
 }
 

@@ -1663,7 +1663,10 @@ __global__ __launch_bounds__(TB) void pb_fill_hits(int64_t n, int F, const float
             if (k < F) {
                 const float v = X[(int64_t)old * F + k];
                 Xp[(int64_t)nw * F + k] = v;
-                mx[k] = fmaxf(mx[k], fabsf(v));
+                // a NaN stays (fmaxf would drop it): its bits are above every number's, so it wins the integer
+                // maxima below too, and x_absmax is NaN as in the host builder (np.abs(X).max)
+                const float av = fabsf(v);
+                if (av > mx[k] || av != av) mx[k] = av;
             }
     }
     __shared__ int red[TB / 64];

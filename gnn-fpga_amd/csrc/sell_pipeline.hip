@@ -483,6 +483,8 @@ typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ unsigned short bf16_rne(float f)
 {
     const unsigned u = __float_as_uint(f);
+    // NaN -> quiet bf16 NaN, sign kept: the carry below would turn 0x7F800001 into +Inf and 0x7FFFFFFF into -0.0
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x0040u);
     return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
 }
 

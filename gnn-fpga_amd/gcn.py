@@ -18,6 +18,14 @@ There is no CPU path: CPU tensors raise RuntimeError, and so does a shape the ke
 names the limit).  No gradient flows to x or a (the notebooks never ask for one): either requiring grad raises.
 Parameter gradients flow in training mode (model.train(), grad enabled), as in the notebooks' training_step; in
 eval mode the per-layer activations are not kept and the logits carry no graph.
+
+Non-finite values ("Non-finite values in the trainable path"; tests/test_gpu_nonfinite.py): they
+propagate, as in torch, by arithmetic alone - no kernel traps and nothing is read back.  The ReLU is torch's:
+relu(NaN) = NaN and its derivative passes the gradient wherever h <= 0 does not hold, so a NaN in one weight makes
+every logit, the loss and the gradients NaN in the forward and the backward.  A NaN in `x` follows the LISTS: the
+nodes reached from the poisoned node within the layers are NaN (forward, and through the column lists backward),
+other graphs of the batch keep their bits.  The adjacency keeps its own contract: a status bit, then ValueError
+(`compress_adjacency`).
 """
 import torch
 import torch.nn as nn
@@ -82,7 +90,12 @@ def compress_adjacency(a):
     Contract for non-finite entries: a NaN or Inf in `a` raises ValueError here.  The dense product of the notebooks
     would spread a NaN to every row (0 * NaN) while a list product would touch only the listed rows, so such an
     adjacency has no faithful compressed form.  The check rides on the ONE host read-back of the compression (the
-    list width and a status word); the model's forward and backward read nothing back."""
+    list width and a status word); the model's forward and backward read nothing back.
+
+    A NaN in `x` is NOT refused, and here the two products differ as well: torch.matmul(a, x) makes every node of the
+    graph NaN, the list product the nodes whose lists reach the poisoned node within the layers.  The kernels keep the
+    list semantics: a node the lists reach is NaN, other nodes may stay finite, other graphs keep their bits (module
+    docstring, "Non-finite values")."""
     if not torch.is_tensor(a) or not a.is_cuda:
         raise _lib.GnnHipError("compress_adjacency needs a tensor on a ROCm device; there is no CPU path")
     if a.dim() != 3 or a.shape[1] != a.shape[2] or a.dtype != torch.float32:

@@ -2,7 +2,14 @@
 used as `self.loss_func(outputs, targets)` in gnn/estimator.py:57), computed by one HIP kernel:
 value and gradient come out of the same pass over the scores, so `loss.backward()` adds no
 second pass (torch's BCELoss is two to three launches each way).  Same clamps as torch
-(log >= -100, denominator >= 1e-12); the sum runs in a fixed order (deterministic)."""
+(log >= -100, denominator >= 1e-12); the sum runs in a fixed order (deterministic).
+
+Non-finite values ("Non-finite values in the trainable path"): torch.nn.BCELoss raises
+for a score outside [0, 1]; this loss is asynchronous - it reads nothing back - and propagates
+instead.  An element whose score is NaN or outside [0, 1] (+-inf included), or whose label is NaN, has
+a NaN loss term and a NaN gradient, so the loss is NaN; every other element's gradient is unchanged, bit
+for bit.  The clamps are written so that a NaN passes (fmaxf(NaN, -100) would be -100: a diverged run
+would go on training on a plausible number).  Scores of exactly 0 and 1 are clamped as before."""
 import torch
 import torch.nn as nn
 

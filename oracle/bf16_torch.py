@@ -63,6 +63,7 @@ Thread count: torch's own (OMP_NUM_THREADS where it is set).
 """
 import math
 
+import numpy as np
 import torch
 
 K32 = torch.tensor(2.8853900817779268, dtype=torch.float32)       # kTwoLog2e (sell_pipeline.hip) in fp32
@@ -70,6 +71,18 @@ K64 = 2.0 / math.log(2.0)
 
 PERTURBATIONS = ("trunc", "x_unrounded", "q_unrounded", "records_fp32", "scale_after_round", "exp2_after_round",
                  "u_rounded", "final_rounded")
+
+
+def bf16_rne_bits(u):
+    """sell_pipeline.hip bf16_rne, integer for integer, on uint32 bit patterns -> uint16: a NaN (exponent all ones,
+    mantissa non-zero) keeps its upper half, sign included, with the quiet bit set; everything else is
+    (u + 0x7FFF + ((u >> 16) & 1)) >> 16.  Without the NaN case the carry turns 0x7F800001 into +Inf (0x7F80),
+    0x7FFFFFFF into -0.0 (0x8000) and 0xFFFFFFFF into +0.0.  torch.bfloat16 keeps a NaN a NaN as well but gives every
+    one the same pattern: the two agree bit for bit on everything that is not a NaN, and on which inputs are."""
+    u = np.asarray(u, np.uint32)
+    rne = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    return np.where(nan, ((u >> np.uint32(16)) | np.uint32(0x0040)).astype(np.uint16), rne)
 
 
 def bf16_round(v, mode="rne"):

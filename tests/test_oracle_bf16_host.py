@@ -13,10 +13,7 @@ from oracle.dense_torch import KEYS
 from test_gpu_parity import TOL_BF16
 
 
-def bf16_rne_bits(u):
-    """sell_pipeline.hip bf16_rne, integer for integer: (u + 0x7FFF + ((u >> 16) & 1)) >> 16 on uint32."""
-    u = np.asarray(u, np.uint32)
-    return ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)
+bf16_rne_bits = bf16_torch.bf16_rne_bits      # sell_pipeline.hip bf16_rne, integer for integer (NaN case included)
 
 
 def _torch_bits(u):
@@ -26,8 +23,9 @@ def _torch_bits(u):
 
 
 def test_rounding_is_the_kernels_bf16_rne():
-    """10^6 random fp32 bit patterns (NaNs excluded: bf16_rne's carry can turn a NaN into an infinity or -0; the
-    kernels never round one) plus constructed ties, +-0, subnormals and the largest finite values."""
+    """10^6 random fp32 bit patterns (NaNs excluded here: torch gives every NaN one bit pattern, bf16_rne keeps the
+    sign - tests/test_nonfinite_host.py pins the NaN case) plus constructed ties, +-0, subnormals and the largest
+    finite values."""
     rng = np.random.default_rng(0)
     u = rng.integers(0, 1 << 32, 1_000_000, dtype=np.uint64).astype(np.uint32)
     u = u[~np.isnan(u.view(np.float32))]
