@@ -74,7 +74,8 @@ def segclf_apply(model, batch):
 # ---- the sub-modules on their own (reference gnn/model.py:69-81, 113-125 are ordinary autograd
 # modules; the notebooks call them directly: gnn/MPNN_Seg_ACTS_maskedlinear.ipynb cells 42, 46) ------
 def _pad_rows(H2, ldh):
-    """[n, C] -> [n, ldh] float32 rows (zero-padded, 16-byte aligned: what the kernels read)."""
+    """[n, C] -> [n, ldh] float32 rows, zero-padded to the stride the kernels read (ldh: a multiple of 4 floats; the
+    rows may start at any multiple of 4 bytes - include/gnn_hip.h, "Alignment")."""
     Hp = torch.zeros((H2.shape[0], ldh), dtype=torch.float32, device=H2.device)
     Hp[:, :H2.shape[1]] = H2
     return Hp

@@ -19,6 +19,26 @@
  *     gnn_edge_bwd, the counters of gnn_segment_metrics_update, the lists of
  *     gnn_gcn_compress_fill) are inputs as well: the caller initialises those;
  *     (tests/test_gpu_uninitialised.py runs every entry point on poisoned, guarded buffers)
+ *   - Alignment.  An array - input, output, weight, gradient, kept training tensor, table column - must
+ *     start at a multiple of its ELEMENT size (4 bytes for float32 / int32, 8 for float64 / int64) and
+ *     nothing more: a window of a larger array (X of graphs j .. j1 of a dataset, a gradient or a
+ *     parameter inside one flat buffer) is as good as an allocation of its own, at every entry point.
+ *     Several kernels move such arrays 16 bytes per lane (hit rows H / H_all / Q_all / grad rows, the
+ *     biases b1, b3, b4 at D >= 32); gfx950 serves a 16-byte global load or store at any 4-byte address and
+ *     the results are bit-identical wherever the array starts; only gnn_segment_metrics_update picks
+ *     between a 16-byte and a 4-byte loop by address.  Rows keep their documented stride (ldh floats).
+ *     A workspace needs no alignment of its own: every entry point rounds the pointer up to 256
+ *     bytes itself and every *_workspace_bytes value includes that slack (gnn_gcn_backward and
+ *     gnn_bce_loss use theirs as floats from the first byte: 4 bytes).  That is read from the code;
+ *     the tests move workspaces in steps of 4 bytes.  The one exception are the arrays of gnn_plan_t
+ *     / gnn_plan_out_t, which the fused kernels stream in pieces of 16 bytes and more: give each an
+ *     allocation of its own (hipMalloc / a torch tensor: 256 bytes and up), as the shipped binding does.
+ *     (tests/test_gpu_offset_arrays.py runs every entry point with its arrays - inputs, and the
+ *     outputs, kept tensors, gradient buffers and workspaces the shipped binding allocates - 4, 8 and
+ *     12 bytes past the 16-byte grid and with a different offset for every array of a call, between
+ *     guard bands; the segment lists of gnn_graph_t, the hit_ptr / seg_ptr of the one-launch entry
+ *     points and seg_ptr / tw_src / tw_dst of gnn_segclf_forward_train_plan - int32 arrays read one
+ *     element at a time - stay where the binding's other modules put them)
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream);
  *     all work is asynchronous on it, no implicit synchronisation;
  *   - return value 0 = success; negative = -(hipError_t) or one of GNN_ERR_*;
