@@ -8,7 +8,8 @@ detector hits, `muon_graph.py` the muon trigger graphs from EMTF hits, `event_gr
 from cluster hits, `select_hits.py` the TrackML barrel hit selection from raw event tables, `metrics.py` confusion
 counts, ROC and AUC, `tracks.py` track candidates from scored segments, their matching to particles and their fit, `gcn.py` the toy notebooks' graph-convolution classifiers and their compressed adjacency,
 `toy_graphs.py` the toy notebooks' segment and hit graphs built straight into that compressed adjacency,
-`cut_study.py` the all-pair histograms and the layer census that choose `build_graphs`' arguments.
+`cut_study.py` the all-pair histograms and the layer census that choose `build_graphs`' arguments,
+`toy_mpnn.py` the toy MPNN notebook's per-iteration segment classifiers and its data cells.
 """
 from .synth import HitGraph  # noqa: F401
 from .hitgraph import HitGraphBatch  # noqa: F401
@@ -25,3 +26,5 @@ from .gcn import (GraphConv, GraphConvSelfInt, GCNBinaryClassifier, GCRNBinaryCl
 from .toy_graphs import (ToyHitGraphs, ToySegmentGraphs, build_toy_hit_graphs,  # noqa: F401,E402
                          build_toy_segment_graphs, sort_toy_tracks)
 from .cut_study import SegmentCutStudy, count_layer_transitions, study_segment_cuts  # noqa: F401,E402
+from .toy_mpnn import (SegmentClassifier as ToySegmentClassifier,  # noqa: F401,E402
+                       SegmentClassifier2 as ToySegmentClassifier2, ToyMpnnGraphs, build_toy_mpnn_graphs)

@@ -235,6 +235,31 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_float), _i32]),
 }
 
+GNN_ITER_MAX = 16           # include/gnn_hip_iter.h
+
+
+class GnnIterSet(ctypes.Structure):
+    _fields_ = [(n, _f) for n in ("Wa", "ba", "Wb", "bb")]
+
+
+class GnnIterParams(ctypes.Structure):
+    _fields_ = [("Win", _f), ("bin", _f), ("edge", GnnIterSet * GNN_ITER_MAX), ("node", GnnIterSet * GNN_ITER_MAX),
+                ("out", GnnIterSet)] + [(n, _i32) for n in ("F", "D", "n_iters", "shared")]
+
+
+# name -> (restype, argtypes); must list every function include/gnn_hip_iter.h declares
+ITER_SIGNATURES = {
+    "gnn_iter_events_supported": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32]),
+    "gnn_iter_forward_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnIterParams), _f, _f, _i64,
+                                               _i32, _i32, _f, _f, _f, _f]),
+    "gnn_iter_grad_floats": (_i64, [_i32, _i32, _i32, _i32]),
+    "gnn_iter_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
+    "gnn_iter_backward_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnIterParams), _f, _f, _i64,
+                                                _i32, _i32, _f, _f, _f, _f, _f, _sz, _f]),
+    "gnn_iter_input_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "gnn_iter_input_bwd": (ctypes.c_int, [_f, _f, _i32, _f, _i32, _i64, _i32, _i32, _f, _f, _sz, _f]),
+}
+
 _lib = None
 
 
@@ -252,9 +277,10 @@ def load():
             "HIP library %s is missing - build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C gnn-fpga_amd/csrc`; there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)           # AttributeError if the symbol is not exported
-        fn.restype, fn.argtypes = res, args
+    for table in (SIGNATURES, ITER_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(lib, name)       # AttributeError if the symbol is not exported
+            fn.restype, fn.argtypes = res, args
     if lib.gnn_abi_version() != GNN_ABI_VERSION:
         raise GnnHipError("libgnn_hip.so ABI %d != binding ABI %d"
                           % (lib.gnn_abi_version(), GNN_ABI_VERSION))
@@ -1530,6 +1556,107 @@ def toy_hit_graphs(hit_x, hit_y, det_r, r_norm, table, L, T, seed_size, norm, ta
                                          cnt[0].data_ptr(), idx[0].data_ptr(), val[0].data_ptr(), cnt[1].data_ptr(),
                                          idx[1].data_ptr(), val[1].data_ptr(), n_iso.data_ptr(), st))
     return X, y0, cnt[0], idx[0], val[0], cnt[1], idx[1], val[1], n_iso
+
+
+# ---- the per-iteration segment classifier (include/gnn_hip_iter.h, csrc/iter_events.hip) ---------------------------------
+@functools.lru_cache(maxsize=None)
+def iter_events_supported(F, D, max_hits, max_segments, backward=False):
+    """True if graphs of at most that size fit the one-launch per-iteration kernels (the backward too, if asked)."""
+    return bool(load().gnn_iter_events_supported(F, D, max_hits, max_segments, int(bool(backward))))
+
+
+def iter_params_struct(win, bin_, edge_sets, node_sets, out_set, F, D, shared=False):
+    """gnn_iter_params_t over float32 device tensors: edge_sets / node_sets are n_iters lists of the four tensors of
+    one network (layer 0 weight, bias, layer 2 weight, bias), out_set the output network's four.  The struct keeps
+    the tensors alive (`_keep`)."""
+    C, T = F + D, len(edge_sets)
+    if T > GNN_ITER_MAX or len(node_sets) != T:
+        raise GnnHipError("expected at most %d edge sets and as many node sets, got %d and %d"
+                          % (GNN_ITER_MAX, T, len(node_sets)))
+    p = GnnIterParams()
+    keep = []
+
+    def put(dst, name, t, shape):
+        n = 1
+        for d in shape:
+            n *= d
+        if not torch.is_tensor(t) or t.numel() != n:
+            # the kernels index the tensors as rows of (F, D): a mismatch is an out-of-bounds read
+            raise GnnHipError("%s has %s elements, but input_dim=%d hidden_dim=%d needs shape %s"
+                              % (name, t.numel() if torch.is_tensor(t) else "no", F, D, shape))
+        setattr(dst, name.split(".")[-1], _dev(t, torch.float32, name))
+        keep.append(t)
+
+    put(p, "Win", win, (D, F))
+    put(p, "bin", bin_, (D,))
+    e_shapes, n_shapes = ((D, 2 * C), (D,), (1, D), (1,)), ((D, 3 * C), (D,), (D, D), (D,))
+    for i in range(T):
+        for name, t, shp in zip(("Wa", "ba", "Wb", "bb"), edge_sets[i], e_shapes):
+            put(p.edge[i], "edge[%d].%s" % (i, name), t, shp)
+        for name, t, shp in zip(("Wa", "ba", "Wb", "bb"), node_sets[i], n_shapes):
+            put(p.node[i], "node[%d].%s" % (i, name), t, shp)
+    for name, t, shp in zip(("Wa", "ba", "Wb", "bb"), out_set, e_shapes):
+        put(p.out, "out.%s" % name, t, shp)
+    p.F, p.D, p.n_iters, p.shared = F, D, T, int(bool(shared))
+    devs = {t.device for t in keep}
+    if len(devs) != 1:
+        raise GnnHipError("the weight tensors must live on one device, got %s" % sorted(map(str, devs)))
+    p._device, p._keep = devs.pop(), keep
+    return p
+
+
+def _iter_ptrs(batch, layout):
+    return _dev(layout.hit_ptr, torch.int32, "hit_ptr"), _dev(layout.seg_ptr, torch.int32, "seg_ptr")
+
+
+def iter_forward_events(batch, layout, ip, train=False):
+    """The per-iteration forward in one launch (`layout` = batch.event_layout(), `ip` = iter_params_struct(...)):
+    scores [n_segments], or with train=True (e_all [(T+1), E], H_all [(T+1), N, ldh]) - scores = e_all[-1]."""
+    dev = batch.X.device
+    E, N, T = batch.n_segments, batch.n_hits, ip.n_iters
+    out = e_all = H_all = None
+    if train:
+        e_all = torch.empty((T + 1, E), dtype=torch.float32, device=dev)
+        H_all = torch.empty((T + 1, N, h_stride(ip.F, ip.D)), dtype=torch.float32, device=dev)
+    else:
+        out = torch.empty(E, dtype=torch.float32, device=dev)
+    g = cached_graph_struct(batch)
+    with _on(batch.X, g, ip) as st:
+        hp, sp = _iter_ptrs(batch, layout)
+        _check(load().gnn_iter_forward_events(
+            ctypes.byref(g), ctypes.byref(ip), hp, sp, batch.n_graphs, layout.max_hits, layout.max_segments,
+            out.data_ptr() if out is not None else None, e_all.data_ptr() if train else None,
+            H_all.data_ptr() if train else None, st))
+    return (e_all, H_all) if train else out
+
+
+def iter_backward_events(batch, layout, ip, e_all, H_all, grad_out):
+    """The flat gradient (state_dict order; gnn_iter_grad_floats) of the per-iteration model in one launch and a fold."""
+    dev = batch.X.device
+    lib = load()
+    flat = torch.empty(int(lib.gnn_iter_grad_floats(ip.F, ip.D, ip.n_iters, ip.shared)), dtype=torch.float32, device=dev)
+    ws = _workspace(dev, lib.gnn_iter_backward_workspace_bytes(batch.n_graphs, ip.F, ip.D, ip.n_iters))
+    g = cached_graph_struct(batch)
+    with _on(batch.X, g, ip) as st:
+        hp, sp = _iter_ptrs(batch, layout)
+        _check(lib.gnn_iter_backward_events(
+            ctypes.byref(g), ctypes.byref(ip), hp, sp, batch.n_graphs, layout.max_hits, layout.max_segments,
+            _dev(e_all, torch.float32, "e_all"), _dev(H_all, torch.float32, "H_all"),
+            _dev(grad_out, torch.float32, "grad_out"), flat.data_ptr(), ws.data_ptr(), ws.numel(), st))
+    return flat
+
+
+def iter_input_bwd(X, H0, gH0, F, D):
+    """Gradients of the input network from dLoss/dH0: flat [D*F + D] = gWin [D, F] then gbin [D] (gnn_iter_input_bwd)."""
+    n = X.shape[0]
+    lib = load()
+    flat = torch.empty(D * F + D, dtype=torch.float32, device=X.device)
+    ws = _workspace(X.device, lib.gnn_iter_input_bwd_workspace_bytes(n, F, D))
+    with _on(X) as st:
+        _check(lib.gnn_iter_input_bwd(_dev(X, torch.float32, "X"), _dev(H0, torch.float32, "H0"), H0.shape[1],
+                                      _dev(gH0, torch.float32, "grad_H0"), gH0.shape[1], n, F, D, flat.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), st))
+    return flat
 
 
 class profile:

@@ -11,6 +11,9 @@ a `Route`; its kind stays on the model as `_route.kind` (tests, diagnostics).
              "twin"        the batch's level-ordered twin: fused training forward (k_edge_tw), per-pass backward
              "twin_pp"     the twin: per-module training forward, per-pass backward
              "pass"        the caller's batch: per-module training forward, per-pass backward
+
+The per-iteration classifiers of toy_mpnn.py have a rule of their own, `choose_iter` / `iter_route` at the end of this file
+("iter_events" or "per_module", inference and training alike).
 """
 import collections
 import functools
@@ -26,7 +29,7 @@ _EVENTS, _PER_MODULE, _PLAN, _PASS = (Choice(k, False) for k in ("events", "per_
 Route = collections.namedtuple("Route", "kind layout plan batch")
 # what a model keeps of its last call: the kind alone - the batch, its plan and its twin must not live as long as the
 # model does (and the plan's exp-product cache points back at the model: a cycle would hold their memory until a collection)
-_KEPT = {k: Route(k, None, None, None) for k in ("events", "plan", "per_module", "twin", "twin_pp", "pass")}
+_KEPT = {k: Route(k, None, None, None) for k in ("events", "plan", "per_module", "twin", "twin_pp", "pass", "iter_events")}
 
 
 def refuse_unsupported(who, X, F, D, training=False):
@@ -124,3 +127,26 @@ def training_route(model, batch):
         batch.remember("host", "train_uses", uses + 1)
     model.__dict__["_route"] = _KEPT[c.kind]
     return Route(c.kind, lay if c.kind == "events" else None, None, run)
+
+
+# ---- the per-iteration classifiers of toy_mpnn.py (gnn/MPNN_Seg_Toy2D.ipynb cell 14) ------------------------------------
+def choose_iter(use_events, n_graphs, layout, n_iters, fits):
+    """The route of one toy_mpnn call, inference and training alike: "iter_events" - the whole forward (and backward)
+    in one launch, one workgroup per graph, a weight set per pass (csrc/iter_events.hip) - or "per_module", the
+    notebook's forward module by module on the per-module kernels, which takes every shape and size.
+    layout: batch.event_layout() (None: not block-diagonal, or a graph beyond _lib.EVENTS_MAX_SEGMENTS); fits:
+    gnn_iter_events_supported for the largest graph (with the backward when the call trains)."""
+    if use_events and 0 < n_graphs <= EVENTS_MAX_GRAPHS and layout is not None and n_iters <= _lib.GNN_ITER_MAX and fits:
+        return "iter_events"
+    return "per_module"
+
+
+def iter_route(model, batch, training):
+    """The Route of one call of a toy_mpnn model on `batch`; its kind stays on the model as `_route.kind`."""
+    use_events = model.use_events
+    lay = batch.event_layout() if use_events and 0 < batch.n_graphs <= EVENTS_MAX_GRAPHS else None
+    fits = lay is not None and _lib.iter_events_supported(model.input_dim, model.hidden_dim, lay.max_hits,
+                                                          lay.max_segments, training)
+    kind = choose_iter(use_events, batch.n_graphs, lay, model.n_iters, fits)
+    model.__dict__["_route"] = _KEPT[kind]
+    return Route(kind, lay if kind == "iter_events" else None, None, batch)

@@ -578,3 +578,26 @@ def toy_tracks(n_events, n_tracks, seed=0, det_r=TOY_DET_R):
     """Seeded [n_events, n_tracks, n_layers] float32 positions of straight tracks (gen_tracks of both notebooks' cell
     3 / 4, with numpy's Generator): what toy_graphs.sort_toy_tracks starts from."""
     return _toy_tracks(np.random.default_rng(seed), n_events, n_tracks, np.asarray(det_r, dtype=np.float32))
+
+
+# ---- the toy MPNN notebook's inputs (gnn/MPNN_Seg_Toy2D.ipynb cells 8, 11, 12), for toy_mpnn.py -------------------------
+def toy_mpnn_segments(n_layers, n_tracks):
+    """(src, dst) int64 [T^2 (L - 1)] of ONE event, hits layer-major: every hit of a layer to every hit of the next,
+    in the order cell 11's np.where(d == 1) gives - segment (l T + a) T + b joins hit l T + a to hit (l + 1) T + b."""
+    lay, a, b = np.meshgrid(np.arange(n_layers - 1), np.arange(n_tracks), np.arange(n_tracks), indexing="ij")
+    return (lay * n_tracks + a).ravel().astype(np.int64), ((lay + 1) * n_tracks + b).ravel().astype(np.int64)
+
+
+def toy_mpnn_graphs_from_hits(hit_x, hit_y, det_r=TOY_DET_R):
+    """The numpy specification of toy_mpnn.build_toy_mpnn_graphs: hit_x, hit_y [E, L * T] (layer-major, sorted within
+    each layer) -> X [E, L T, 2] = (x, r) float32 (cell 12), src, dst [S] of one event (cell 11; every event has the
+    same), y [E, S] float32 = the segment's two hits carry the same label (cell 12's ey)."""
+    det = np.asarray(det_r, dtype=np.float64)
+    L = det.shape[0]
+    hit_x = np.asarray(hit_x)
+    T = hit_x.shape[1] // L
+    src, dst = toy_mpnn_segments(L, T)
+    r = np.broadcast_to(np.repeat(det, T)[None], hit_x.shape)
+    X = np.stack([hit_x.astype(np.float64), r], axis=-1).astype(np.float32)
+    hit_y = np.asarray(hit_y)
+    return X, src, dst, (hit_y[:, src] == hit_y[:, dst]).astype(np.float32)
