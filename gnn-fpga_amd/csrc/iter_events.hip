@@ -768,8 +768,10 @@ int gnn_iter_forward_events(const gnn_graph_t *g, const gnn_iter_params_t *p, co
     const char *who = "gnn_iter_forward_events";
     if (int rc = check_params(who, p)) return rc;
     if (int rc = check_batch(who, g, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments)) return rc;
-    if (!e_all != !H_all) return fail(GNN_ERR_BADARG, "%s: e_all and H_all come together or not at all", who);
-    if (!e_out && !e_all) return fail(GNN_ERR_BADARG, "%s: no output asked for", who);
+    // (an array of no elements may be NULL: a batch without segments has no e_all, one without hits no H_all)
+    if ((e_all && !H_all && g->n_hits > 0) || (H_all && !e_all && g->n_segments > 0))
+        return fail(GNN_ERR_BADARG, "%s: e_all and H_all come together or not at all", who);
+    if (!e_out && !e_all && g->n_segments > 0) return fail(GNN_ERR_BADARG, "%s: no output asked for", who);
     if (!gnn_iter_events_supported(p->F, p->D, max_hits, max_segments, 0))
         return fail(GNN_ERR_UNSUPPORTED, "%s: graphs of up to %d hits / %d segments do not fit one workgroup's LDS at "
                     "input_dim=%d hidden_dim=%d", who, max_hits, max_segments, p->F, p->D);

@@ -54,7 +54,8 @@ int gnn_iter_events_supported(int32_t F, int32_t D, int64_t max_hits, int64_t ma
 /* SegmentClassifier.forward (cell 14) for a batch of small graphs in one launch.  hit_ptr / seg_ptr [n_graphs+1]
  * and the six lists of `g` as gnn_segclf_forward_train_events takes them (all required).  e_out [n_segments]: the
  * output network's scores, or NULL; e_all [(n_iters+1), n_segments] and H_all [(n_iters+1), n_hits, ldh]: every
- * pass's scores and hit rows for the backward, or both NULL (inference).  Sums run in list order; the arithmetic per
+ * pass's scores and hit rows for the backward, or both NULL (inference); an array of no elements (no segments, no
+ * hits) may be NULL.  Sums run in list order; the arithmetic per
  * row is that of gnn_input_fwd / gnn_edge_fwd / gnn_node_fwd. */
 int gnn_iter_forward_events(const gnn_graph_t *g, const gnn_iter_params_t *p, const int32_t *hit_ptr,
                             const int32_t *seg_ptr, int64_t n_graphs, int32_t max_hits, int32_t max_segments,

@@ -12,9 +12,11 @@ import torch
 import torch.nn as nn
 
 import toy_mpnn_fp64 as ref
-from gnn_fpga_amd import HitGraphBatch, ToySegmentClassifier, ToySegmentClassifier2, build_toy_mpnn_graphs, synth
+from gnn_fpga_amd import HitGraphBatch, ToySegmentClassifier, build_toy_mpnn_graphs, synth
 from gnn_fpga_amd import sort_toy_tracks
 from gnn_fpga_amd.call_route import EVENTS_MAX_GRAPHS
+from toy_mpnn_cases import (check_abs, check_graphs, check_rel, model_of, random_graph, random_params,  # noqa: F401
+                            reference_error, train_step)
 
 pytestmark = pytest.mark.gpu
 _FIX = {}
@@ -24,13 +26,6 @@ def fixture(case):
     if case not in _FIX:
         _FIX[case] = ref.Fixture(case)
     return _FIX[case]
-
-
-def model_of(params, F, D, T, shared, events=True):
-    m = (ToySegmentClassifier2 if shared else ToySegmentClassifier)(F, D, T)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in params.items()})
-    m.use_events = events
-    return m.cuda()
 
 
 def index_batch(X, src, dst, y, hit_ptr, seg_ptr, dense_shape=None):
@@ -43,29 +38,6 @@ def fixture_inputs(fx, form):
         return [torch.from_numpy(fx[k]).cuda() for k in ("X", "Ri", "Ro")]
     return index_batch(fx["X"], fx["src"], fx["dst"], fx["y"], np.arange(fx.B + 1) * fx.N, np.arange(fx.B + 1) * fx.E,
                        (fx.B, fx.N, fx.E))
-
-
-def train_step(m, inp, y):
-    """What the notebook's Estimator does per batch: (scores, loss, {name: grad})."""
-    m.train()
-    m.zero_grad()
-    out = m(inp)
-    loss = nn.BCELoss()(out.reshape(-1), y.reshape(-1))
-    loss.backward()
-    return out.detach().reshape(-1), float(loss.item()), {n: p.grad.detach().cpu().numpy().copy()
-                                                           for n, p in m.named_parameters()}
-
-
-def check_abs(what, got, want):
-    err = float(np.abs(np.asarray(got, np.float64) - np.asarray(want, np.float64)).max()) if np.size(want) else 0.0
-    print("  %-52s |err| %.3e  bound %.1e" % (what, err, ref.SCORE_BOUND))
-    return [] if err <= ref.SCORE_BOUND else ["%s: %.3e > %.1e" % (what, err, ref.SCORE_BOUND)]
-
-
-def check_rel(what, got, want, ref_err):
-    err, b = ref.rel_err(got, want), ref.grad_bound(ref_err)
-    print("  %-52s err %.3e  bound %.3e  (reference's own %.3e)" % (what, err, b, float(ref_err)))
-    return [] if err <= b else ["%s: %.3e > %.3e" % (what, err, b)]
 
 
 # ---- the reference's fixtures: both routes, both input forms -----------------------------------------------------------
@@ -133,67 +105,6 @@ def test_adam_step_changes_every_tensor(hip):
 
 
 # ---- size edges, against the restatement -------------------------------------------------------------------------------
-def random_graph(rng, nh, ns, F, lone=True):
-    """nh hits, ns segments between distinct hits (a lower id to a higher one); with `lone` the last hit has none."""
-    X = rng.uniform(-1.0, 1.0, size=(nh, F)).astype(np.float32)
-    top = nh - 1 if (lone and nh >= 3) else nh
-    if top < 2:
-        ns = 0
-    a = rng.integers(0, max(top - 1, 1), size=ns)
-    b = a + 1 + rng.integers(0, np.maximum(top - 1 - a, 1), size=ns) if ns else a
-    y = (rng.random(ns) < 0.3).astype(np.float32)
-    return synth.HitGraph(X, a.astype(np.int32), np.minimum(b, top - 1).astype(np.int32), y)
-
-
-def random_params(F, D, T, shared, seed):
-    torch.manual_seed(seed)
-    m = (ToySegmentClassifier2 if shared else ToySegmentClassifier)(F, D, T)
-    return {k: v.detach().numpy().copy() for k, v in m.state_dict().items()}
-
-
-def reference_error(params, X, src, dst, y, T, r64, orders=8):
-    """The reference's own fp32 error on synthetic inputs, per tensor: the restatement run in fp32 on the CPU with the
-    segments in `orders` orders (as given, then seeded permutations), the largest distance from the fp64 run.  One
-    run is ONE sample of a rounding error, and where a gradient is a cancelling sum the samples spread: the bias of
-    edge_networks[0]'s output layer in test_segment_count_edges[32] is a sum of 3 800 terms whose absolute values add
-    up to 86 times the sum, and the fp32 restatement's error on it is anywhere from 0.9e-6 to 5.3e-6 over eight
-    orders (measured on the CPU alone).  A fixture's ref_err_* is the one sample the reference gave: this stand-in, a
-    largest of eight, is WIDER than that one-sample figure, so the synthetic cases are held to a looser bound than the
-    fixtures are (never below the project's 5e-6 either way)."""
-    own = {}
-    for i in range(orders):
-        o = np.arange(len(src)) if i == 0 else np.random.default_rng(i).permutation(len(src))
-        r32 = ref.run(params, X, src[o], dst[o], y[o], T, dtype=torch.float32)
-        own["loss"] = max(own.get("loss", 0.0), ref.rel_err(r32["loss"], r64["loss"]))
-        for k in params:
-            own[k] = max(own.get(k, 0.0), ref.rel_err(r32["grads"][k], r64["grads"][k]))
-    return own
-
-
-def check_graphs(hip, graphs, F, D, T, want_infer, want_train, shared=False, seed=0):
-    """Inference and one training step on `graphs` by the default route, against the fp64 restatement."""
-    params = random_params(F, D, T, shared, seed)
-    batch = HitGraphBatch.from_graphs(graphs).to("cuda")
-    X, src, dst, y = (batch.X.cpu().numpy(), batch.src.cpu().numpy(), batch.dst.cpu().numpy(), batch.y.cpu().numpy())
-    r64 = ref.run(params, X, src, dst, y, T)
-    own = reference_error(params, X, src, dst, y, T, r64)
-    m = model_of(params, F, D, T, shared)
-    bad = []
-    with torch.no_grad():
-        e = m.eval()(batch)
-    print("  inference route %s" % m._route.kind)
-    assert m._route.kind == want_infer
-    bad += check_abs("scores", e.cpu().numpy(), r64["e"][T])
-    out, loss, grads = train_step(m, batch, batch.y)
-    print("  training route %s" % m._route.kind)
-    assert m._route.kind == want_train
-    bad += check_abs("training scores", out.cpu().numpy(), r64["e"][T])
-    bad += check_rel("loss", loss, r64["loss"], own["loss"])
-    for k in params:
-        bad += check_rel("grad " + k, grads[k], r64["grads"][k], own[k])
-    assert not bad, "\n".join(bad)
-
-
 def _nt_forward(D):
     return 64 * (16 if D >= 32 else 8 if D >= 8 else 4)         # csrc/iter_events.hip ItFwd::NT; the backward runs 256
 
