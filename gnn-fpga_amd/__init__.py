@@ -9,7 +9,8 @@ from cluster hits, `select_hits.py` the TrackML barrel hit selection from raw ev
 counts, ROC and AUC, `tracks.py` track candidates from scored segments, their matching to particles and their fit, `gcn.py` the toy notebooks' graph-convolution classifiers and their compressed adjacency,
 `toy_graphs.py` the toy notebooks' segment and hit graphs built straight into that compressed adjacency,
 `cut_study.py` the all-pair histograms and the layer census that choose `build_graphs`' arguments,
-`toy_mpnn.py` the toy MPNN notebook's per-iteration segment classifiers and its data cells.
+`toy_mpnn.py` the toy MPNN notebook's per-iteration segment classifiers and its data cells,
+`fixed_point.py` the bit-accurate fixed-point forward of SegmentClassifier and the precision scan over word formats.
 """
 from .synth import HitGraph  # noqa: F401
 from .hitgraph import HitGraphBatch  # noqa: F401
@@ -28,3 +29,5 @@ from .toy_graphs import (ToyHitGraphs, ToySegmentGraphs, build_toy_hit_graphs,  
 from .cut_study import SegmentCutStudy, count_layer_transitions, study_segment_cuts  # noqa: F401,E402
 from .toy_mpnn import (SegmentClassifier as ToySegmentClassifier,  # noqa: F401,E402
                        SegmentClassifier2 as ToySegmentClassifier2, ToyMpnnGraphs, build_toy_mpnn_graphs)
+from .fixed_point import (FixedPointFormat, FixedPointScores, FixedPointSegmentClassifier,  # noqa: F401,E402
+                          fixed_forward_numpy, quantize_model, scan_precision)

@@ -260,6 +260,33 @@ ITER_SIGNATURES = {
     "gnn_iter_input_bwd": (ctypes.c_int, [_f, _f, _i32, _f, _i32, _i64, _i32, _i32, _f, _f, _sz, _f]),
 }
 
+GNN_FX_ROUNDING = {"trn": 0, "rnd": 1}        # include/gnn_hip_fixed.h GNN_FX_TRN / GNN_FX_RND
+GNN_FX_OVERFLOW = {"wrap": 0, "sat": 1}       # GNN_FX_WRAP / GNN_FX_SAT
+GNN_FX_STAGES = 6
+
+
+class GnnFxFormat(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("total_bits", "int_bits", "rounding", "overflow", "table_bits")]
+
+
+class GnnFxParams(ctypes.Structure):
+    _fields_ = [(n, _f) for n in ("Win", "bin", "W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4")] + \
+               [("F", _i32), ("D", _i32)]
+
+
+class GnnFxTables(ctypes.Structure):
+    _fields_ = [("tanh_table", _f), ("sigmoid_table", _f)]
+
+
+# name -> (restype, argtypes); must list every function include/gnn_hip_fixed.h declares
+FX_SIGNATURES = {
+    "gnn_fx_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
+    "gnn_fx_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "gnn_fx_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnFxParams),
+                                      ctypes.POINTER(GnnFxFormat), ctypes.POINTER(GnnFxTables), _i32, _f, _f, _f, _f, _f,
+                                      _f, _sz, _f]),
+}
+
 _lib = None
 
 
@@ -277,7 +304,7 @@ def load():
             "HIP library %s is missing - build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C gnn-fpga_amd/csrc`; there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, ITER_SIGNATURES):
+    for table in (SIGNATURES, ITER_SIGNATURES, FX_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
@@ -1657,6 +1684,85 @@ def iter_input_bwd(X, H0, gH0, F, D):
                                       _dev(gH0, torch.float32, "grad_H0"), gH0.shape[1], n, F, D, flat.data_ptr(),
                                       ws.data_ptr(), ws.numel(), st))
     return flat
+
+
+# ---- the fixed-point forward (include/gnn_hip_fixed.h, csrc/fixed_point.hip) -------------------------------------------
+@functools.lru_cache(maxsize=None)
+def fx_supported(F, D, total_bits, int_bits, table_bits):
+    return bool(load().gnn_fx_supported(F, D, total_bits, int_bits, table_bits))
+
+
+def fx_workspace_bytes(n_hits, n_segments, F, D):
+    return int(load().gnn_fx_workspace_bytes(n_hits, n_segments, F, D))
+
+
+def fx_format_struct(total_bits, int_bits, rounding, overflow, table_bits):
+    return GnnFxFormat(total_bits, int_bits, GNN_FX_ROUNDING[rounding], GNN_FX_OVERFLOW[overflow], table_bits)
+
+
+def fx_params_struct(weights, F, D):
+    """gnn_fx_params_t over the ten quantised weight tensors (int32, state_dict order); keeps them alive (`_keep`)."""
+    p = GnnFxParams()
+    C = F + D
+    shapes = ((D, F), (D,), (D, 2 * C), (D,), (1, D), (1,), (D, 3 * C), (D,), (D, D), (D,))
+    if len(weights) != 10:
+        raise GnnHipError("expected the ten weight tensors in state_dict order, got %d" % len(weights))
+    for name, w, shp in zip(("Win", "bin", "W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4"), weights, shapes):
+        n = 1
+        for d in shp:
+            n *= d
+        if not torch.is_tensor(w) or w.numel() != n:
+            # the kernels index the tensors as [D, ...] rows of (F, D): a mismatch is an out-of-bounds read
+            raise GnnHipError("%s has %s elements, but input_dim=%d hidden_dim=%d needs shape %s"
+                              % (name, w.numel() if torch.is_tensor(w) else "no", F, D, shp))
+        setattr(p, name, _dev(w, torch.int32, name))
+    p.F, p.D = F, D
+    devs = {w.device for w in weights}
+    if len(devs) != 1:
+        raise GnnHipError("the weight tensors must live on one device, got %s" % sorted(map(str, devs)))
+    p._device, p._keep = devs.pop(), list(weights)
+    return p
+
+
+def fx_tables_struct(tanh_table, sigmoid_table, table_bits):
+    """gnn_fx_tables_t over the two int32 device tables of 2^table_bits entries; keeps them alive (`_keep`)."""
+    t = GnnFxTables()
+    for name, tab in (("tanh_table", tanh_table), ("sigmoid_table", sigmoid_table)):
+        if not torch.is_tensor(tab) or tab.numel() != 1 << table_bits:
+            raise GnnHipError("%s must hold 2^%d entries" % (name, table_bits))       # (the kernels copy that many)
+        setattr(t, name, _dev(tab, torch.int32, name))
+    if tanh_table.device != sigmoid_table.device:
+        raise GnnHipError("the two tables must live on one device")
+    t._device, t._keep = tanh_table.device, (tanh_table, sigmoid_table)
+    return t
+
+
+def fx_forward(batch, params, fmt, tables, n_iters, trace=False, workspace=None):
+    """gnn_fx_forward on an index-form batch (`params` = fx_params_struct(...), `fmt` = fx_format_struct(...), `tables`
+    = fx_tables_struct(...)): (raw int32 [E], scores float32 [E], counts int64 [T+1, 6], e_trace int32 [T+1, E] or
+    None, H_trace int32 [T+1, N, C] or None)."""
+    dev = batch.X.device
+    E, N, F, D = batch.n_segments, batch.n_hits, params.F, params.D
+    if not fx_supported(F, D, fmt.total_bits, fmt.int_bits, fmt.table_bits):
+        raise GnnHipError("no fixed-point kernel for input_dim=%d hidden_dim=%d at total_bits=%d int_bits=%d "
+                          "table_bits=%d" % (F, D, fmt.total_bits, fmt.int_bits, fmt.table_bits))
+    need = fx_workspace_bytes(N, E, F, D)
+    if workspace is None or workspace.numel() < need:
+        workspace = _workspace(dev, need)
+    raw = torch.empty(E, dtype=torch.int32, device=dev)
+    scores = torch.empty(E, dtype=torch.float32, device=dev)
+    counts = torch.empty((n_iters + 1, GNN_FX_STAGES), dtype=torch.int64, device=dev)     # (the call zeroes them)
+    et = Ht = None
+    if trace:
+        et = torch.empty((n_iters + 1, E), dtype=torch.int32, device=dev)
+        Ht = torch.empty((n_iters + 1, N, F + D), dtype=torch.int32, device=dev)
+    g = graph_struct(batch)
+    with _on(batch.X, g, params, tables) as st:
+        _check(load().gnn_fx_forward(ctypes.byref(g), ctypes.byref(params), ctypes.byref(fmt), ctypes.byref(tables),
+                                     n_iters, raw.data_ptr(), scores.data_ptr(), counts.data_ptr(),
+                                     et.data_ptr() if trace else None, Ht.data_ptr() if trace else None,
+                                     _dev(workspace, torch.uint8, "workspace"), workspace.numel(), st))
+    return raw, scores, counts, et, Ht
 
 
 class profile:
