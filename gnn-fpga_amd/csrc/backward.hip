@@ -32,6 +32,7 @@
 // in a fixed order, and two runs give bit-identical gradients (deterministic by default).
 #include "common.h"
 #include "lane_ops.h"
+#include "event_passes.h"
 
 namespace {
 using namespace gnn;
@@ -1993,22 +1994,8 @@ int node_bwd_t(const float *H, const float *e, const float *Hn, const gnn_graph_
 // in the same order per item, a barrier separates them.  Weight gradients: every thread owns a few
 // elements of each gradient tensor, sums its graph's contributions in registers over all
 // iterations and issues one atomic per element at the end (to the workgroup's gradient replica).
-template <int F, int D>
-struct EvBwd {
-    static constexpr int C = F + D, LDH = (C + 3) & ~3;
-    // weights in LDS: W1, b1, W2, W3, b3, W4; the rows of W1 / W3 are laid out like the feature rows
-    // they multiply (blocks of C columns padded to LDH, zeros) so that products run on 4-float pieces
-    static constexpr int oW1 = 0, ob1 = oW1 + D * 2 * LDH, oW2 = ob1 + D, oW3 = oW2 + D,
-                         ob3 = oW3 + D * 3 * LDH, oW4 = ob3 + D, w_total = oW4 + D * D;
-    static constexpr int per_hit = 9 * LDH + 5 * D;     // Hc Hp gH gHp (4) + gmio (2) + M (3) | PQ fa (2D each) qb
-    static size_t lds_bytes(int64_t cap_h, int64_t cap_s)
-    {
-        const int64_t s4 = (cap_s + 3) & ~3;
-        return (size_t)(cap_h * per_hit + 2 * s4 + w_total + 2 * (cap_h + 1) + 6 * cap_s + 8) * sizeof(float);
-    }
-    static constexpr int n1 = D * 2 * C + D, n3 = D * 3 * C + D, n4 = D * D + D, nin = D * F + D;
-};
-
+// The LDS layout and byte count: EvBwd (event_passes.h).
+//
 // Weight gradients inside k_event_bwd: sum over the graph's hits of L (x) R, R taken in 4-float
 // pieces.  Role r of a thread (r = tid + u * 256): r < NL * NR4 -> the 4 products of L row r / NR4
 // with piece r % NR4 of R; the next NB roles -> the plain sums of L rows 0 .. NB-1 (the bias).
@@ -2105,27 +2092,9 @@ __global__ __launch_bounds__(kBlock) void k_event_bwd(
     }
     const float *W1 = wl + B::oW1, *b1 = wl + B::ob1, *W2 = wl + B::oW2, *W3 = wl + B::oW3,
                 *b3 = wl + B::ob3, *W4 = wl + B::oW4;
-    if (nh > 0) {       // the graph's index arrays as LOCAL ids (see k_event)
-        const int ib = g.in_ptr[h0], ob = g.out_ptr[h0];
-        for (int n = tid; n <= nh; n += NT) {
-            ip[n] = g.in_ptr[h0 + n] - ib;
-            op[n] = g.out_ptr[h0 + n] - ob;
-        }
-        const int ni = g.in_ptr[h0 + nh] - ib, no = g.out_ptr[h0 + nh] - ob;
-        for (int k = tid; k < ni; k += NT) {
-            ie[k] = g.in_eid[ib + k] - s0;
-            inb[k] = g.in_nbr[ib + k] - h0;
-        }
-        for (int k = tid; k < no; k += NT) {
-            oe[k] = g.out_eid[ob + k] - s0;
-            onb[k] = g.out_nbr[ob + k] - h0;
-        }
-    }
-    for (int j = tid; j < ns; j += NT) {
-        const int sg = g.src[s0 + j];
-        sl[j] = sg < 0 ? -1 : sg - h0;
-        dl[j] = sg < 0 ? -1 : g.dst[s0 + j] - h0;
-    }
+    const EvIds ids = {ip, op, ie, inb, oe, onb, sl, dl};       // the graph's index arrays as LOCAL ids
+    if (nh > 0) ev_local_lists<NT>(g, h0, nh, s0, ids);
+    ev_local_ends<NT>(g, h0, s0, ns, ids);
     for (int i = tid; i < nh * LDH; i += NT) {
         gH[i] = gHp[i] = 0.0f;                  // (padding columns stay zero: nothing writes them)
         gmio[2 * i] = gmio[2 * i + 1] = 0.0f;

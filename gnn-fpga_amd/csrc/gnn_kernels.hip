@@ -28,6 +28,7 @@
 //   gnn_input_fwd / gnn_edge_fwd (k_pq, k_edge) / gnn_node_fwd: one lane per item at every size
 #include "common.h"
 #include "lane_ops.h"
+#include "event_passes.h"
 
 #include <type_traits>
 
@@ -656,13 +657,6 @@ struct EvW {
         *__restrict__ b4;
 };
 
-template <int D>
-struct EvCfg {
-    // wavefronts per graph: the output rows of every layer are dealt to them
-    static constexpr int NWV = D >= 32 ? 16 : D >= 8 ? 8 : 4;
-    static constexpr int NT = 64 * NWV;
-};
-
 template <int F, int D>
 __global__ __launch_bounds__((EvCfg<D>::NT)) void k_event(
     gnn_graph_t g, const float *__restrict__ Win, const float *__restrict__ bin,
@@ -711,27 +705,9 @@ __global__ __launch_bounds__((EvCfg<D>::NT)) void k_event(
             *ie = op + cap_hits + 1, *inb = ie + cap_segments, *oe = inb + cap_segments,
             *onb = oe + cap_segments, *sl = onb + cap_segments, *dl = sl + cap_segments;
     const bool raw = g.in_ptr == nullptr;            // no segment lists from the caller: built below, in LDS
-    if (nh > 0 && !raw) {
-        const int ib = g.in_ptr[h0], ob = g.out_ptr[h0];
-        for (int n = threadIdx.x; n <= nh; n += NT) {
-            ip[n] = g.in_ptr[h0 + n] - ib;
-            op[n] = g.out_ptr[h0 + n] - ob;
-        }
-        const int ni = g.in_ptr[h0 + nh] - ib, no = g.out_ptr[h0 + nh] - ob;
-        for (int k = threadIdx.x; k < ni; k += NT) {
-            ie[k] = g.in_eid[ib + k] - s0;
-            inb[k] = g.in_nbr[ib + k] - h0;
-        }
-        for (int k = threadIdx.x; k < no; k += NT) {
-            oe[k] = g.out_eid[ob + k] - s0;
-            onb[k] = g.out_nbr[ob + k] - h0;
-        }
-    }
-    for (int j = threadIdx.x; j < ns; j += NT) {
-        const int sg = g.src[s0 + j];
-        sl[j] = sg < 0 ? -1 : sg - h0;
-        dl[j] = sg < 0 ? -1 : g.dst[s0 + j] - h0;
-    }
+    const EvIds ids = {ip, op, ie, inb, oe, onb, sl, dl};       // the graph's index arrays as LOCAL ids
+    if (nh > 0 && !raw) ev_local_lists<NT>(g, h0, nh, s0, ids);
+    ev_local_ends<NT>(g, h0, s0, ns, ids);
     if (raw) {
         // The two lists of a graph nobody has seen before (trigger-style use, gnn/Inference.ipynb cell 3: one event
         // in, scores out), from its (src, dst) alone - what gnn_csr_build does with four launches, here inside the
@@ -946,11 +922,10 @@ constexpr size_t kEventLdsMax = 128 * 1024;     // of the CU's 160 KB
 
 inline size_t event_lds_bytes(int F, int D, int64_t cap_hits, int64_t cap_segments)
 {
-    const int ldh = (F + D + 3) & ~3, C = F + D;
+    const int C = F + D;
     auto a4 = [](int x) { return (x + 3) & ~3; };
     const int wfl = a4(D * F) + a4(D * 2 * C) + a4(1) + a4(D * 3 * C) + a4(D * D) + 5 * a4(D);   // EvWeights::total
-    return (size_t)(cap_hits * (4 * ldh + 3 * D) + ((cap_segments + 3) & ~3) + wfl +
-                    2 * (cap_hits + 1) + 6 * cap_segments) * sizeof(float);
+    return ev_fwd_lds_bytes(F, D, cap_hits, cap_segments, wfl);
 }
 
 template <int F, int D>

@@ -1,14 +1,17 @@
 // iter_events.hip - the per-iteration segment classifier of gnn/MPNN_Seg_Toy2D.ipynb cell 14 (include/gnn_hip_iter.h):
 // the whole forward and the whole backward of one small graph in one workgroup, a different weight set per pass.
 //
-// Counterparts of k_event (gnn_kernels.hip) and k_event_bwd (backward.hip), whose statements per hit, per segment and
-// per list entry these kernels repeat in the same order.  What differs:
+// Counterparts of k_event (gnn_kernels.hip) and k_event_bwd (backward.hip).  The wavefronts per graph, the LDS byte
+// counts, the backward's LDS layout and the local-id copy are theirs too (event_passes.h); the stages per hit, per
+// segment and per list entry are written out here, the same statements in the same order: shared functions compile to
+// other register counts (profiles/event_passes_ab.txt), so a fix in a stage is made in both files.  What differs:
 //   - the weights of ONE pass live in LDS (an edge set and a node set: 6 593 floats at F = 2, D = 32); the next
 //     pass's set is copied in as soon as the last reader of the current one is past a barrier;
 //   - the backward keeps no gradient in registers across passes: after every pass each element of that pass's
 //     gradient tensors is summed over the graph's hits by ONE thread and stored to the pass's slot of the graph's row
 //     of partial gradients; k_iter_fold then adds the rows in graph order.  No atomics anywhere.
 #include "common.h"
+#include "event_passes.h"
 #include "gnn_hip_iter.h"
 
 namespace {
@@ -46,17 +49,11 @@ struct IterLayout {
 template <int F, int D>
 struct ItFwd {
     static constexpr int C = F + D, LDH = a4(C);
-    static constexpr int NWV = D >= 32 ? 16 : D >= 8 ? 8 : 4;      // wavefronts per graph, as EvCfg
-    static constexpr int NT = 64 * NWV;
+    static constexpr int NWV = EvCfg<D>::NWV, NT = EvCfg<D>::NT;
     // LDS offsets (floats, 16-byte aligned) of the input network and of one pass's edge and node sets
     static constexpr int oWin = 0, obin = oWin + a4(D * F), oW1 = obin + D, ob1 = oW1 + a4(D * 2 * C), oW2 = ob1 + D,
                          ob2 = oW2 + D, oW3 = ob2 + 4, ob3 = oW3 + a4(D * 3 * C), oW4 = ob3 + D, ob4 = oW4 + D * D,
                          w_total = ob4 + D;
-    static size_t lds_bytes(int64_t cap_h, int64_t cap_s)
-    {
-        return (size_t)(cap_h * (4 * LDH + 3 * D) + ((cap_s + 3) & ~(int64_t)3) + w_total + 2 * (cap_h + 1) + 6 * cap_s) *
-               sizeof(float);
-    }
 };
 
 template <int F, int D>
@@ -105,7 +102,8 @@ __global__ __launch_bounds__((ItFwd<F, D>::NT)) void k_iter_event(
     copy_in(wl + L::obin, p.bin, D);
     stage_edge(0);
     if (T > 0) stage_node(0);
-    // the graph's index arrays as LOCAL ids (see k_event)
+    // the graph's index arrays as LOCAL ids: the text of ev_local_lists / ev_local_ends (event_passes.h), kept here -
+    // through the shared functions this kernel alone compiles to 13 more SGPR spills at hidden_dim 32
     if (nh > 0) {
         const int ib = g.in_ptr[h0], ob = g.out_ptr[h0];
         for (int n = threadIdx.x; n <= nh; n += NT) {
@@ -279,21 +277,6 @@ __global__ __launch_bounds__((ItFwd<F, D>::NT)) void k_iter_event(
 // ---------------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------------
-template <int F, int D>
-struct ItBwd {
-    static constexpr int C = F + D, LDH = a4(C);
-    // one pass's weights in LDS: W1, b1, W2, W3, b3, W4; the rows of W1 / W3 laid out like the feature rows they
-    // multiply (blocks of C columns padded to LDH with zeros), as EvBwd
-    static constexpr int oW1 = 0, ob1 = oW1 + D * 2 * LDH, oW2 = ob1 + D, oW3 = oW2 + D, ob3 = oW3 + D * 3 * LDH,
-                         oW4 = ob3 + D, w_total = oW4 + D * D;
-    static constexpr int per_hit = 9 * LDH + 5 * D;     // Hc Hp gH gHp (4) + gmio (2) + M (3) | PQ fa (2D each) qb
-    static size_t lds_bytes(int64_t cap_h, int64_t cap_s)
-    {
-        const int64_t s4 = (cap_s + 3) & ~(int64_t)3;
-        return (size_t)(cap_h * per_hit + 2 * s4 + w_total + 2 * (cap_h + 1) + 6 * cap_s + 8) * sizeof(float);
-    }
-};
-
 // One pass's weight gradient: out[index(l, k)] = sum over the graph's hits of L[n][l] * R[n][k], R taken in 4-float
 // pieces (index < 0: a padding column), then the NB plain sums of L's first columns (the bias, + bias_add[l] if
 // given).  One thread per element group, hits ascending: the same sums as Outer4 of k_event_bwd, stored, not added.
@@ -332,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void k_iter_event_bwd(
     const float *__restrict__ e_all, const float *__restrict__ H_all, const float *__restrict__ grad_out,
     float *__restrict__ rep, int cap_h, int cap_s)
 {
-    using B = ItBwd<F, D>;
+    using B = EvBwd<F, D>;
     constexpr int C = B::C, LDH = B::LDH, NT = kBlock, NW = NT / 64, NS = D + 2;
     extern __shared__ __attribute__((aligned(16))) float ib_lds[];
     __shared__ float red[NW * NS];      // the wavefronts' per-segment sums of one edge pass
@@ -376,27 +359,9 @@ __global__ __launch_bounds__(kBlock) void k_iter_event_bwd(
     const float *W1 = wl + B::oW1, *b1 = wl + B::ob1, *W2 = wl + B::oW2, *W3 = wl + B::oW3, *b3 = wl + B::ob3,
                 *W4 = wl + B::oW4;
     stage_edge(T);                                      // the last pass is output_network's
-    if (nh > 0) {       // the graph's index arrays as LOCAL ids (see k_event)
-        const int ib = g.in_ptr[h0], ob = g.out_ptr[h0];
-        for (int n = tid; n <= nh; n += NT) {
-            ip[n] = g.in_ptr[h0 + n] - ib;
-            op[n] = g.out_ptr[h0 + n] - ob;
-        }
-        const int ni = g.in_ptr[h0 + nh] - ib, no = g.out_ptr[h0 + nh] - ob;
-        for (int k = tid; k < ni; k += NT) {
-            ie[k] = g.in_eid[ib + k] - s0;
-            inb[k] = g.in_nbr[ib + k] - h0;
-        }
-        for (int k = tid; k < no; k += NT) {
-            oe[k] = g.out_eid[ob + k] - s0;
-            onb[k] = g.out_nbr[ob + k] - h0;
-        }
-    }
-    for (int j = tid; j < ns; j += NT) {
-        const int sg = g.src[s0 + j];
-        sl[j] = sg < 0 ? -1 : sg - h0;
-        dl[j] = sg < 0 ? -1 : g.dst[s0 + j] - h0;
-    }
+    const EvIds ids = {ip, op, ie, inb, oe, onb, sl, dl};       // the graph's index arrays as LOCAL ids
+    if (nh > 0) ev_local_lists<NT>(g, h0, nh, s0, ids);
+    ev_local_ends<NT>(g, h0, s0, ns, ids);
     for (int i = tid; i < nh * LDH; i += NT) {
         gH[i] = gHp[i] = 0.0f;                  // (padding columns stay zero: nothing writes them)
         gmio[2 * i] = gmio[2 * i + 1] = 0.0f;
@@ -649,8 +614,9 @@ int run_iter_forward(const gnn_graph_t *g, const gnn_iter_params_t *p, const int
     if (attr_done.need())
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_event<F, D>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIterLdsMax);
-    GNN_LAUNCH_SH("k_iter_event", (k_iter_event<F, D>), (unsigned)n_graphs, L::NT, L::lds_bytes(cap_h, cap_s), s, *g, *p,
-                  hit_ptr, seg_ptr, e_out, cap_h, cap_s, e_all, H_all);
+    const size_t lds = ev_fwd_lds_bytes(F, D, cap_h, cap_s, L::w_total);
+    GNN_LAUNCH_SH("k_iter_event", (k_iter_event<F, D>), (unsigned)n_graphs, L::NT, lds, s, *g, *p, hit_ptr, seg_ptr, e_out,
+                  cap_h, cap_s, e_all, H_all);
     return 0;
 }
 
@@ -673,7 +639,7 @@ int run_iter_backward(const gnn_graph_t *g, const gnn_iter_params_t *p, const in
         if (attr_done.need())
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_iter_event_bwd<F, D>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kIterLdsMax);
-        const size_t lds = ItBwd<F, D>::lds_bytes(cap_h, cap_s);
+        const size_t lds = EvBwd<F, D>::lds_bytes(cap_h, cap_s);
         GNN_LAUNCH_SH("k_iter_event_bwd", (k_iter_event_bwd<F, D>), (unsigned)n_graphs, kBlock, lds, s, *g, *p, hit_ptr,
                       seg_ptr, e_all, H_all, grad_out, rep, cap_h, cap_s);
     }
@@ -754,8 +720,8 @@ int gnn_iter_events_supported(int32_t F, int32_t D, int64_t max_hits, int64_t ma
     if (max_hits < 0 || max_segments < 0 || max_hits >= (1 << 20) || max_segments >= (1 << 24)) return 0;
 #define X_(F_, D_)                                                                                   \
     if (F == F_ && D == D_)                                                                          \
-        return ItFwd<F_, D_>::lds_bytes(max_hits, max_segments) <= kIterLdsMax &&                    \
-               (!backward || ItBwd<F_, D_>::lds_bytes(max_hits, max_segments) <= kIterLdsMax);
+        return ev_fwd_lds_bytes(F_, D_, max_hits, max_segments, ItFwd<F_, D_>::w_total) <= kIterLdsMax && \
+               (!backward || EvBwd<F_, D_>::lds_bytes(max_hits, max_segments) <= kIterLdsMax);
     ITER_SHAPES(X_)
 #undef X_
     return 0;

@@ -319,3 +319,22 @@ def test_a_dropped_segment_moves_the_checked_tensors(case):
     d_e = np.abs(got["e"][fx.T] - fx["e64_%d" % fx.T].reshape(-1))[others].max()
     print("  %s: H_1 moves by %.1e, the other segments' scores by %.1e" % (case[0], d_h1, d_e))
     assert d_h1 >= 1e4 * FLOOR and d_e >= 10 * ref.SCORE_BOUND
+
+
+def test_the_shared_passes_header_rebuilds_its_three_units():
+    """csrc/event_passes.h holds what k_event, k_event_bwd and the two per-iteration kernels share: it is in the Makefile's
+    HDR, which every object depends on, and the three units include it."""
+    csrc = os.path.join(REPO, "gnn-fpga_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    assert "$(CSRC)/event_passes.h" in re.search(r"^HDR\s*:=\s*(.*)$", mk, re.M).group(1).split()
+    assert re.search(r"^\$\(ROOT\)/build/%\.o: \$\(CSRC\)/%\.hip \$\(HDR\)$", mk, re.M)
+    assert os.path.exists(os.path.join(csrc, "event_passes.h"))
+    for unit in ("gnn_kernels", "backward", "iter_events"):
+        assert re.search(r'^#include "event_passes\.h"$', open(os.path.join(csrc, unit + ".hip")).read(), re.M), unit
+
+
+def test_the_shared_byte_counts_stay_wide():
+    """The LDS byte counts are 64-bit sums: a segment count whose id words (6 per segment) pass 2^31 is refused, not
+    wrapped into a few KB that fit."""
+    assert _lib.events_supported(11, 8, 60, 300) and not _lib.events_supported(11, 8, 10, 613566757)
+    assert not _lib.events_supported(3, 16, 10, 1 << 40) and not _lib.events_supported(3, 16, 1 << 40, 10)
