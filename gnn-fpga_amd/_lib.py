@@ -287,6 +287,15 @@ FX_SIGNATURES = {
                                       _f, _sz, _f]),
 }
 
+# name -> (restype, argtypes); must list every function include/gnn_hip_fixed_events.h declares
+FXEV_SIGNATURES = {
+    "gnn_fxev_lds_bytes": (_sz, [_i32, _i32, _i32, _i64, _i64]),
+    "gnn_fxev_supported": (ctypes.c_int, [_i32, _i32, _i32, _i64, _i64]),
+    "gnn_fxev_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnFxParams),
+                                        ctypes.POINTER(GnnFxFormat), ctypes.POINTER(GnnFxTables), _f, _f, _i64, _i32, _i32,
+                                        _i32, _f, _f, _f, _f, _f, _f, _f]),
+}
+
 _lib = None
 
 
@@ -304,7 +313,7 @@ def load():
             "HIP library %s is missing - build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` or `make -C gnn-fpga_amd/csrc`; there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for table in (SIGNATURES, ITER_SIGNATURES, FX_SIGNATURES):
+    for table in (SIGNATURES, ITER_SIGNATURES, FX_SIGNATURES, FXEV_SIGNATURES):
         for name, (res, args) in table.items():
             fn = getattr(lib, name)       # AttributeError if the symbol is not exported
             fn.restype, fn.argtypes = res, args
@@ -1763,6 +1772,43 @@ def fx_forward(batch, params, fmt, tables, n_iters, trace=False, workspace=None)
                                      et.data_ptr() if trace else None, Ht.data_ptr() if trace else None,
                                      _dev(workspace, torch.uint8, "workspace"), workspace.numel(), st))
     return raw, scores, counts, et, Ht
+
+
+# ---- its one-launch form for small graphs (include/gnn_hip_fixed_events.h, csrc/fixed_events.hip) -----------------------
+@functools.lru_cache(maxsize=None)
+def fxev_lds_bytes(F, D, table_bits, max_hits, max_segments):
+    """Bytes of LDS a workgroup of gnn_fxev_forward needs for graphs of at most that size (0: arguments it refuses)."""
+    return int(load().gnn_fxev_lds_bytes(F, D, table_bits, max_hits, max_segments))
+
+
+@functools.lru_cache(maxsize=None)
+def fxev_supported(F, D, table_bits, max_hits, max_segments):
+    """True if graphs of at most that size fit the one-launch fixed-point kernel."""
+    return bool(load().gnn_fxev_supported(F, D, table_bits, max_hits, max_segments))
+
+
+def fxev_forward(batch, layout, params, fmt, tables, n_iters, trace=False):
+    """gnn_fxev_forward on a block-diagonal batch of small graphs (`layout` = batch.event_layout(); `params`, `fmt`,
+    `tables` as fx_forward takes them): (raw int32 [E], scores float32 [E], counts int64 [T+1, 6], graph_overflows int64
+    [n_graphs], e_trace int32 [T+1, E] or None, H_trace int32 [T+1, N, C] or None)."""
+    dev = batch.X.device
+    E, N, F, D = batch.n_segments, batch.n_hits, params.F, params.D
+    raw = torch.empty(E, dtype=torch.int32, device=dev)
+    scores = torch.empty(E, dtype=torch.float32, device=dev)
+    counts = torch.empty((n_iters + 1, GNN_FX_STAGES), dtype=torch.int64, device=dev)     # (the call zeroes them)
+    per_graph = torch.empty(batch.n_graphs, dtype=torch.int64, device=dev)
+    et = Ht = None
+    if trace:
+        et = torch.empty((n_iters + 1, E), dtype=torch.int32, device=dev)
+        Ht = torch.empty((n_iters + 1, N, F + D), dtype=torch.int32, device=dev)
+    g = cached_graph_struct(batch)
+    with _on(batch.X, g, params, tables) as st:
+        hp, sp = _iter_ptrs(batch, layout)
+        _check(load().gnn_fxev_forward(ctypes.byref(g), ctypes.byref(params), ctypes.byref(fmt), ctypes.byref(tables),
+                                       hp, sp, batch.n_graphs, layout.max_hits, layout.max_segments, n_iters,
+                                       raw.data_ptr(), scores.data_ptr(), counts.data_ptr(), per_graph.data_ptr(),
+                                       et.data_ptr() if trace else None, Ht.data_ptr() if trace else None, st))
+    return raw, scores, counts, per_graph, et, Ht
 
 
 class profile:

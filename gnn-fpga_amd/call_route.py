@@ -13,7 +13,8 @@ a `Route`; its kind stays on the model as `_route.kind` (tests, diagnostics).
              "pass"        the caller's batch: per-module training forward, per-pass backward
 
 The per-iteration classifiers of toy_mpnn.py have a rule of their own, `choose_iter` / `iter_route` at the end of this file
-("iter_events" or "per_module", inference and training alike).
+("iter_events" or "per_module", inference and training alike), and so has the fixed-point forward of fixed_point.py,
+`choose_fixed` ("events" or "per_module").
 """
 import collections
 import functools
@@ -150,3 +151,14 @@ def iter_route(model, batch, training):
     kind = choose_iter(use_events, batch.n_graphs, lay, model.n_iters, fits)
     model.__dict__["_route"] = _KEPT[kind]
     return Route(kind, lay if kind == "iter_events" else None, None, batch)
+
+
+# ---- the fixed-point forward of fixed_point.py (include/gnn_hip_fixed.h, include/gnn_hip_fixed_events.h) ------------------
+def choose_fixed(use_events, trace, n_graphs, layout, fits):
+    """The route of one FixedPointSegmentClassifier call: "events" - the whole forward in one launch, one workgroup per
+    graph (csrc/fixed_events.hip), which also counts the overflows of every graph - or "per_module", one kernel per
+    reference module (csrc/fixed_point.hip), which takes every size and keeps the traces.  Both give the same bits.
+    layout: batch.event_layout(); fits: gnn_fxev_supported for the largest graph at the format's table_bits."""
+    if use_events and not trace and 0 < n_graphs <= EVENTS_MAX_GRAPHS and layout is not None and fits:
+        return "events"
+    return "per_module"

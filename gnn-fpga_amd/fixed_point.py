@@ -1,11 +1,13 @@
-"""Fixed-point inference: SegmentClassifier as an FPGA would run it (include/gnn_hip_fixed.h, csrc/fixed_point.hip).
+"""Fixed-point inference: SegmentClassifier as an FPGA would run it (include/gnn_hip_fixed.h, csrc/fixed_point.hip; for
+batches of small graphs include/gnn_hip_fixed_events.h, csrc/fixed_events.hip: one launch, overflows per graph).
 
 The reference's goal is a segment classifier small enough for an FPGA.  Pruning is `MaskedLinear`; this module is the
 other lever, word length: a bit-accurate forward in two's-complement words of a chosen width with table-lookup
 activations, on the GPU at detector scale, so that a scan over formats feeds `SegmentMetrics` directly.
 
     qm = quantize_model(model, FixedPointFormat(16, 6))
-    out = qm(batch)                       # FixedPointScores: raw, scores, counts (overflows per pass and stage), fmt
+    out = qm(batch)                       # FixedPointScores: raw, scores, counts (overflows per pass and stage), fmt,
+                                          # event_overflows (per graph, for batches of small graphs)
     rows = scan_precision(model, [(batch, y), ...], [FixedPointFormat(w, 6) for w in (8, 12, 16, 24)])
 
 The arithmetic ("Fixed point") is all integers, so `fixed_forward_numpy` - the specification, vectorised
@@ -15,7 +17,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, call_route
 from .hitgraph import HitGraphBatch
 
 ROUNDINGS = ("trn", "rnd")
@@ -73,12 +75,14 @@ class FixedPointFormat:
 class FixedPointScores:
     """What a fixed-point forward returns: `raw` int32 [E] stored integers, `scores` float32 [E] = raw * 2^-Fb (exact),
     `counts` int64 [T + 1, 6] overflows per pass and stage (STAGES), `e_trace` [T + 1, E] / `H_trace` [T + 1, N, C]
-    int32 or None, `fmt`."""
+    int32 or None, `fmt`; `event_overflows` int64 [n_graphs], the overflows of every graph over all passes and stages
+    (they add up to `counts.sum()`), from the one-launch route for small graphs, else None."""
 
-    __slots__ = ("raw", "scores", "counts", "e_trace", "H_trace", "fmt")
+    __slots__ = ("raw", "scores", "counts", "e_trace", "H_trace", "fmt", "event_overflows")
 
-    def __init__(self, raw, scores, counts, e_trace, H_trace, fmt):
+    def __init__(self, raw, scores, counts, e_trace, H_trace, fmt, event_overflows=None):
         self.raw, self.scores, self.counts, self.e_trace, self.H_trace, self.fmt = raw, scores, counts, e_trace, H_trace, fmt
+        self.event_overflows = event_overflows
 
 
 # ---- the specification ------------------------------------------------------------------------------------------------
@@ -209,7 +213,12 @@ class FixedPointSegmentClassifier:
     """`quantize_model`'s result: the model's ten effective weight tensors as int32 stored integers and the two
     activation tables, on the model's device; rebuilt when a parameter changes (the model's `_param_key`; after an
     in-place edit through `.data` call the model's `invalidate()` and this object's).  Calling it runs
-    gnn_fx_forward."""
+    gnn_fxev_forward - one launch, one workgroup per graph - on a batch of small graphs and gnn_fx_forward, one kernel
+    per reference module, on everything else (`call_route.choose_fixed`; the same bits either way).  `use_events =
+    False` forces the per-module kernels; `last_route` is the kind of the last call."""
+
+    use_events = True
+    last_route = None
 
     def __init__(self, model, fmt):
         if not isinstance(fmt, FixedPointFormat):
@@ -267,8 +276,18 @@ class FixedPointSegmentClassifier:
                              % (batch.X.shape[1], self.model.input_dim))
         params, tables, fmt = self._ensure()
         self._check_lists(batch)
+        f, n_graphs = self.fmt, batch.n_graphs
+        # (the layout is asked for only where it can matter: a batch's first answer costs a pass over its endpoints)
+        lay = (batch.event_layout() if self.use_events and not trace and 0 < n_graphs <= call_route.EVENTS_MAX_GRAPHS
+               else None)
+        fits = lay is not None and _lib.fxev_supported(self.model.input_dim, self.model.hidden_dim, f.table_bits,
+                                                       lay.max_hits, lay.max_segments)
+        self.last_route = call_route.choose_fixed(self.use_events, trace, n_graphs, lay, fits)
+        if self.last_route == "events":
+            raw, scores, counts, per_graph, _, _ = _lib.fxev_forward(batch, lay, params, fmt, tables, self.model.n_iters)
+            return FixedPointScores(raw, scores, counts, None, None, f, per_graph)
         raw, scores, counts, et, Ht = _lib.fx_forward(batch, params, fmt, tables, self.model.n_iters, trace=trace)
-        return FixedPointScores(raw, scores, counts, et, Ht, self.fmt)
+        return FixedPointScores(raw, scores, counts, et, Ht, f)
 
 
 def quantize_model(model, fmt):
@@ -277,12 +296,14 @@ def quantize_model(model, fmt):
     return FixedPointSegmentClassifier(model, fmt)
 
 
-def scan_precision(model, batches_with_labels, formats, thresholds=(0.5,)):
+def scan_precision(model, batches_with_labels, formats, thresholds=(0.5,), use_events=True):
     """One row (a dict) per format over `batches_with_labels`, a list of (HitGraphBatch, y) on the model's device:
     `format`; `n`, `tp`, `fp`, `tn`, `fn`, `accuracy`, `precision`, `recall` from SegmentMetrics.compute() (arrays, one
     entry per threshold; padded segments left out); `auc`; `overflows` int64 [6], the overflow counts of every stage
     summed over passes and batches (STAGES); `max_abs_diff`, the largest |score - float32 score| against the model's
-    own forward."""
+    own forward; `events_overflowed`, the number of graphs with at least one overflow, summed over batches - what a
+    trigger picks `int_bits` by - or None if a batch ran per module (FixedPointScores.event_overflows).  `use_events`
+    = False forces the per-module kernels."""
     from .metrics import SegmentMetrics
     items = list(batches_with_labels)
     with torch.no_grad():
@@ -295,8 +316,10 @@ def scan_precision(model, batches_with_labels, formats, thresholds=(0.5,)):
     rows = []
     for fmt in formats:
         qm = quantize_model(model, fmt)
+        qm.use_events = use_events
         metrics = None
         over, worst = None, None
+        spoiled, per_event = None, True         # graphs with an overflow; False once a batch ran per module
         for (b, y), ref in zip(items, floats):
             out = qm(b)
             if metrics is None:
@@ -304,6 +327,11 @@ def scan_precision(model, batches_with_labels, formats, thresholds=(0.5,)):
             metrics.update(out.scores, y, batch=b)
             total = out.counts.sum(dim=0)
             over = total if over is None else over + total
+            if out.event_overflows is None:
+                per_event = False
+            elif per_event:
+                n = (out.event_overflows > 0).sum()
+                spoiled = n if spoiled is None else spoiled + n
             if out.scores.numel():
                 d = (out.scores - ref).abs().max()
                 worst = d if worst is None else torch.maximum(worst, d)
@@ -314,5 +342,6 @@ def scan_precision(model, batches_with_labels, formats, thresholds=(0.5,)):
             row["auc"] = metrics.auc()[0]
         row["overflows"] = (over.cpu().numpy() if over is not None else np.zeros(len(STAGES), dtype=np.int64))
         row["max_abs_diff"] = float(worst.item()) if worst is not None else 0.0
+        row["events_overflowed"] = (int(spoiled.item()) if spoiled is not None else 0) if per_event else None
         rows.append(row)
     return rows
