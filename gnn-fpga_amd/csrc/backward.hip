@@ -30,9 +30,17 @@
 // element, so the adds of successive launches land in launch order).  k_grad_fold1 / 2 then sum the
 // rows in row order, 32 rows per chunk, chunks in order: every float addition of a backward happens
 // in a fixed order, and two runs give bit-identical gradients (deterministic by default).
+//
+// Host side (below the kernels): choose_bwd_route, BwdRun, backward_t / edge_bwd_t / node_bwd_t / backward_events_t.  The
+// unit owns its C ABI, at the end of the file: gnn_backward_workspace_bytes, gnn_segclf_backward, gnn_nodeclf_backward,
+// gnn_edge_bwd, gnn_node_bwd, gnn_events_backward_supported, gnn_backward_events_workspace_bytes,
+// gnn_segclf_backward_events and gnn_bce_loss - each checks its arguments there and goes through with_bwd_shape
+// (workspace, shape list, alignment) straight into the launchers.
 #include "common.h"
 #include "lane_ops.h"
 #include "event_passes.h"
+
+#include <type_traits>
 
 namespace {
 using namespace gnn;
@@ -1788,6 +1796,14 @@ BwdRoute choose_bwd_route(int T, bool have_Q, bool have_head, bool have_grad_out
     return {start, iter, iter == BwdIter::quad && !sw.no_fin_hit};
 }
 
+// NodeClassifier's output network y = sigmoid(Wo [H'_T | X] + bo) (gnn/MPNN_HitClassifier.ipynb cell 21): with
+// `head` the backward starts from the hit scores' gradient gy instead of the final edge pass (grad_out unused,
+// e_all holds the n_iters edge passes of the trunk) and adds the head's own gradients into gWo [C], gbo [1]
+struct HeadBwd {
+    const float *Wo, *y, *gy;
+    float *gWo, *gbo;
+};
+
 #define BWD_LISTS g->in_ptr, g->in_eid, g->in_nbr, g->out_ptr, g->out_eid, g->out_nbr
 // One backward in flight: what its launchers share.  A launcher takes what differs between its calls - the H / e / Q
 // rows of the step, gH (the gradient row it reads) and gHprev (the one it writes) - and skips an empty batch.
@@ -2355,7 +2371,8 @@ int backward_events_t(const gnn_graph_t *g, const gnn_params_t *p, const int32_t
 }
 
 // shapes of the one-launch backward: the register-held gradient elements must stay few
-#define BWD_EVENT_SHAPES(X_) X_(2, 4) X_(2, 8) X_(2, 16) X_(3, 4) X_(3, 8) X_(3, 16) X_(11, 4) X_(11, 8) X_(11, 16)
+using BwdEventShapes = ShapeList<Shape<2, 4>, Shape<2, 8>, Shape<2, 16>, Shape<3, 4>, Shape<3, 8>, Shape<3, 16>,
+                                 Shape<11, 4>, Shape<11, 8>, Shape<11, 16>>;
 
 // ---- fused BCE loss (value + gradient in one pass over the scores) ----------------------------
 // torch.nn.BCELoss semantics (the loss of gnn/estimator.py:57): logs clamped at -100,
@@ -2404,84 +2421,151 @@ __global__ __launch_bounds__(64) void k_bce_final(const float *__restrict__ part
     if (threadIdx.x == 0) loss[0] = s * scale;
 }
 
-// What the public entry points share: the workspace check, the 256-byte alignment and the shape dispatch -
-// fn(Shape<F, D>, base) for the caller's shape (GNN_FOR_EACH_SHAPE, common.h), over the one-launch backward's shapes with EVENTS.
+// What the entry points share once their arguments are checked: the workspace holds `need` bytes, the shape has a
+// kernel in the list (the one-launch backward's with EVENTS, else ModelShapes of common.h), the 256-byte alignment;
+// then fn(Shape<F, D>, base).  Inside fn nothing is null that the kernels read, and base holds `need` bytes.
 template <bool EVENTS, typename Fn>
 int with_bwd_shape(const gnn_params_t *p, void *ws, size_t ws_bytes, size_t need, Fn fn)
 {
+    using Shapes = std::conditional_t<EVENTS, BwdEventShapes, ModelShapes>;
     if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
+    if (!Shapes::has(p->F, p->D))
+        return fail(GNN_ERR_UNSUPPORTED, "no %sbackward kernel for input_dim=%d hidden_dim=%d", EVENTS ? "one-launch " : "",
+                    p->F, p->D);
     char *base = align_ws(ws);
-#define X_(F_, D_) if (p->F == F_ && p->D == D_) return fn(Shape<F_, D_>{}, base);
-    if constexpr (EVENTS) { BWD_EVENT_SHAPES(X_) } else { GNN_FOR_EACH_SHAPE(X_) }
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no %sbackward kernel for input_dim=%d hidden_dim=%d", EVENTS ? "one-launch " : "",
-                p->F, p->D);
+    return Shapes::template find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) { return fn(sh, base); });
+}
+
+// the backward of both classifiers (head null: SegmentClassifier), arguments checked
+int backward(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all, const float *H_all,
+             const float *Q_all, const float *grad_out, const gnn_grads_t *gr, void *ws, size_t ws_bytes, void *stream,
+             const HeadBwd *head)
+{
+    const size_t need = carve_bwd(nullptr, g->n_hits, g->n_segments, p->F, p->D).bytes;
+    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
+        return backward_t<sh.F, sh.D>(g, p, T, e_all, H_all, Q_all, grad_out, gr, base, static_cast<hipStream_t>(stream),
+                                      head); });
 }
 
 }  // namespace
 
-namespace gnn {
+using namespace gnn;
 
-int bce_loss(const float *e, const float *y, int64_t n, float scale, float *loss, float *grad_e,
-             float *partial, hipStream_t s)
+// ---------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+size_t gnn_backward_workspace_bytes(int64_t n_hits, int64_t n_segments, int32_t F, int32_t D)
 {
-    const int64_t need = (n + kBlock - 1) / kBlock;
-    const int blocks = (int)(need < 1 ? 1 : need < kBceBlocks ? need : kBceBlocks);
-    GNN_LAUNCH("k_bce", k_bce, blocks, kBlock, s, e, y, n, scale, grad_e, partial);
-    GNN_LAUNCH("k_bce_final", k_bce_final, 1, 64, s, partial, blocks, scale, loss);
-    return 0;
+    if (n_hits < 0 || n_segments < 0 || F <= 0 || D <= 0) return 0;
+    return carve_bwd(nullptr, n_hits, n_segments, F, D).bytes;
 }
 
-int backward_events_supported(int F, int D, int64_t max_hits, int64_t max_segments)
+int gnn_segclf_backward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_iters,
+                        const float *e_all, const float *H_all, const float *Q_all,
+                        const float *grad_out, const gnn_grads_t *gr, void *workspace,
+                        size_t workspace_bytes, void *stream)
 {
-#define X_(F_, D_) if (F == F_ && D == D_) return EvBwd<F_, D_>::lds_bytes(max_hits, max_segments) <= kEventBwdLdsMax;
-    BWD_EVENT_SHAPES(X_)
-#undef X_
-    return 0;
+    gnn::ProfChain chain_;
+    if (!g || !p || !gr || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0 || !workspace)
+        return fail(GNN_ERR_BADARG, "gnn_segclf_backward: bad argument");
+    if ((g->n_segments > 0 && (!e_all || !grad_out)) || (g->n_hits > 0 && !H_all))
+        return fail(GNN_ERR_BADARG, "gnn_segclf_backward: saved tensors missing");
+    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward: gradient pointer missing");
+    return backward(g, p, n_iters, e_all, H_all, Q_all, grad_out, gr, workspace, workspace_bytes, stream, nullptr);
 }
 
-size_t backward_events_workspace_bytes(int64_t n_graphs, int F, int D)
+// NodeClassifier (gnn/MPNN_HitClassifier.ipynb cells 20-21): the trunk's backward behind the output network's
+int gnn_nodeclf_backward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo, int32_t n_iters,
+                         const float *e_all, const float *H_all, const float *Q_all, const float *y, const float *grad_y,
+                         const gnn_grads_t *gr, float *gWo, float *gbo, void *workspace, size_t workspace_bytes,
+                         void *stream)
+{
+    gnn::ProfChain chain_;
+    if (!g || !p || !gr || !Wo || !bo || !gWo || !gbo || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0 || !workspace)
+        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: bad argument");
+    if ((n_iters > 0 && g->n_segments > 0 && !e_all) || (g->n_hits > 0 && (!H_all || !y || !grad_y)))
+        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: saved tensors missing");
+    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: gradient pointer missing");
+    if (!ModelShapes::has(p->F, p->D))
+        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const HeadBwd head = {Wo, y, grad_y, gWo, gbo};
+    return backward(g, p, n_iters, e_all, H_all, Q_all, nullptr, gr, workspace, workspace_bytes, stream, &head);
+}
+
+int gnn_edge_bwd(const float *H, int32_t ldh, const gnn_graph_t *g, const gnn_params_t *p, const float *e,
+                 const float *grad_e, float *grad_H, const gnn_grads_t *gr, void *workspace,
+                 size_t workspace_bytes, void *stream)
+{
+    if (!g || !p || !workspace || g->n_hits < 0 || g->n_segments < 0 || !grads_complete(gr))
+        return fail(GNN_ERR_BADARG, "gnn_edge_bwd: bad argument");
+    if (ldh != gnn_h_stride(p->F, p->D)) return fail(GNN_ERR_BADARG, "gnn_edge_bwd: ldh must be gnn_h_stride(F, D)");
+    if ((g->n_hits > 0 && (!H || !grad_H)) || (g->n_segments > 0 && (!e || !grad_e)))
+        return fail(GNN_ERR_BADARG, "gnn_edge_bwd: tensor missing");
+    const size_t need = carve_bwd(nullptr, g->n_hits, g->n_segments, p->F, p->D).bytes;
+    return with_bwd_shape<false>(p, workspace, workspace_bytes, need, [&](auto sh, char *base) {
+        return edge_bwd_t<sh.F, sh.D>(H, g, p, e, grad_e, grad_H, gr, base, static_cast<hipStream_t>(stream)); });
+}
+
+int gnn_node_bwd(const float *H, int32_t ldh, const float *e, const float *Hnext, const gnn_graph_t *g,
+                 const gnn_params_t *p, const float *grad_Hnext, float *grad_H, float *grad_e,
+                 const gnn_grads_t *gr, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!g || !p || !workspace || g->n_hits < 0 || g->n_segments < 0 || !grads_complete(gr))
+        return fail(GNN_ERR_BADARG, "gnn_node_bwd: bad argument");
+    if (ldh != gnn_h_stride(p->F, p->D)) return fail(GNN_ERR_BADARG, "gnn_node_bwd: ldh must be gnn_h_stride(F, D)");
+    if ((g->n_hits > 0 && (!H || !Hnext || !grad_Hnext || !grad_H)) || (g->n_segments > 0 && (!e || !grad_e)))
+        return fail(GNN_ERR_BADARG, "gnn_node_bwd: tensor missing");
+    const size_t need = carve_bwd(nullptr, g->n_hits, g->n_segments, p->F, p->D).bytes;
+    return with_bwd_shape<false>(p, workspace, workspace_bytes, need, [&](auto sh, char *base) {
+        return node_bwd_t<sh.F, sh.D>(H, e, Hnext, g, p, grad_Hnext, grad_H, grad_e, gr, base,
+                                      static_cast<hipStream_t>(stream)); });
+}
+
+int gnn_events_backward_supported(int32_t F, int32_t D, int64_t max_hits, int64_t max_segments)
+{
+    if (max_hits < 0 || max_segments < 0) return 0;
+    return BwdEventShapes::find<int>(F, D, 0, [&](auto sh) {
+        return EvBwd<sh.F, sh.D>::lds_bytes(max_hits, max_segments) <= kEventBwdLdsMax; });
+}
+
+size_t gnn_backward_events_workspace_bytes(int64_t n_graphs, int32_t F, int32_t D)
 {
     const int64_t rows = n_graphs > 0 ? n_graphs : 1;
     return (size_t)(rows + fold_chunks(rows)) * replica_stride(F, D) * sizeof(float) + 256;
 }
 
-int backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
-                    const int32_t *seg_ptr, int64_t n_graphs, int cap_h, int cap_s, int T,
-                    const float *e_all, const float *H_all, const float *grad_out,
-                    const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s)
+int gnn_segclf_backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
+                               const int32_t *seg_ptr, int64_t n_graphs, int32_t max_hits,
+                               int32_t max_segments, int32_t n_iters, const float *e_all,
+                               const float *H_all, const float *grad_out, const gnn_grads_t *gr,
+                               void *workspace, size_t workspace_bytes, void *stream)
 {
-    const size_t need = backward_events_workspace_bytes(n_graphs, p->F, p->D);
-    return with_bwd_shape<true>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
-        return backward_events_t<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, cap_h, cap_s, T, e_all, H_all, grad_out, gr,
-                                             base, s); });
+    if (!g || !p || !gr || n_iters < 0 || n_graphs < 0 || max_hits < 0 || max_segments < 0 || !workspace)
+        return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: bad argument");
+    if (n_graphs > 0 && (!hit_ptr || !seg_ptr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: graph offsets missing");
+    if ((g->n_segments > 0 && (!e_all || !grad_out || !g->src || !g->dst)) || (g->n_hits > 0 && (!H_all || !g->in_ptr || !g->out_ptr)))
+        return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: saved tensors or graph arrays missing");
+    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: gradient pointer missing");
+    const size_t need = gnn_backward_events_workspace_bytes(n_graphs, p->F, p->D);
+    return with_bwd_shape<true>(p, workspace, workspace_bytes, need, [&](auto sh, char *base) {
+        return backward_events_t<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_all,
+                                             H_all, grad_out, gr, base, static_cast<hipStream_t>(stream)); });
 }
 
-size_t backward_workspace_bytes(int64_t N, int64_t E, int F, int D) { return carve_bwd(nullptr, N, E, F, D).bytes; }
-
-int backward(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
-             const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
-             void *ws, size_t ws_bytes, hipStream_t s, const HeadBwd *head)
+int gnn_bce_loss(const float *e, const float *y, int64_t n, float scale, float *loss_out,
+                 float *grad_e, void *workspace, void *stream)
 {
-    const size_t need = backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D);
-    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
-        return backward_t<sh.F, sh.D>(g, p, T, e_all, H_all, Q_all, grad_out, gr, base, s, head); });
+    if (n < 0 || !loss_out || !workspace || (n > 0 && (!e || !y)))
+        return fail(GNN_ERR_BADARG, "gnn_bce_loss: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    float *partial = static_cast<float *>(workspace);
+    const int64_t need = (n + kBlock - 1) / kBlock;
+    const int blocks = (int)(need < 1 ? 1 : need < kBceBlocks ? need : kBceBlocks);
+    GNN_LAUNCH("k_bce", k_bce, blocks, kBlock, s, e, y, n, scale, grad_e, partial);
+    GNN_LAUNCH("k_bce_final", k_bce_final, 1, 64, s, partial, blocks, scale, loss_out);
+    return 0;
 }
 
-int edge_bwd(const float *H, const gnn_graph_t *g, const gnn_params_t *p, const float *e, const float *ge, float *gH,
-             const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s)
-{
-    const size_t need = backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D);
-    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
-        return edge_bwd_t<sh.F, sh.D>(H, g, p, e, ge, gH, gr, base, s); });
-}
-
-int node_bwd(const float *H, const float *e, const float *Hn, const gnn_graph_t *g, const gnn_params_t *p,
-             const float *gHn, float *gH, float *ge, const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s)
-{
-    const size_t need = backward_workspace_bytes(g->n_hits, g->n_segments, p->F, p->D);
-    return with_bwd_shape<false>(p, ws, ws_bytes, need, [&](auto sh, char *base) {
-        return node_bwd_t<sh.F, sh.D>(H, e, Hn, g, p, gHn, gH, ge, gr, base, s); });
-}
-
-}  // namespace gnn
+}  // extern "C"

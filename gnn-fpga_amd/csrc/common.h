@@ -1,4 +1,6 @@
-// common.h - error reporting, HIP-event profiler and launch macro shared by the kernel files.
+// common.h - what the units share: the error and profiler hooks (defined in core.hip), the launch macro, the shape
+// lists and their dispatch (ShapeList), workspace carving and a few device helpers.  It declares nothing that
+// gnn_kernels.hip, sell_pipeline.hip or backward.hip define: each of them owns its entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,20 +49,44 @@ struct ProfChain {
 
 constexpr int kBlock = 256;   // 4 waves of 64
 
-// The (input_dim, hidden_dim) pairs the per-pass forward (gnn_kernels.hip) and the backward (backward.hip) have kernels
-// for: one list, so that a shape cannot be trained without a forward or the other way round.
-// (input_dim 4: the hit classifier of gnn/MPNN_HitClassifier.ipynb - r, phi, z and the seed label - and the first
-// shapes whose hit rows [H' | X] have no zero pad column, C == LDH)
-#define GNN_FOR_EACH_SHAPE(X_) \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) X_(4, 8) X_(4, 16) \
-    X_(4, 32) X_(4, 64) X_(11, 4) X_(11, 8) X_(11, 16)
-
 // a shape as a type: hit rows [H'(D) | X(F) | 0-pad] of C floats, stored LDH = gnn_h_stride(F, D) apart
 template <int F_, int D_>
 struct Shape {
     static constexpr int F = F_, D = D_, C = F + D;
     static constexpr int LDH = (C + 3) & ~3;
 };
+
+// The one shape dispatch: a list of Shape<F, D> types, written once per kernel family, that answers "is (F, D)
+// listed" and runs a generic lambda at the caller's (F, D) - `fn(sh)` may use sh.F / sh.D as template arguments.
+template <typename... S>
+struct ShapeList {
+    static constexpr bool has(int F, int D) { return ((F == S::F && D == S::D) || ...); }
+    // fn(Shape<F, D>{}) for the listed shape (F, D); `miss` where there is none
+    template <typename R, typename Fn>
+    static R find(int F, int D, R miss, Fn fn)
+    {
+        (void)((F == S::F && D == S::D && (miss = fn(S{}), true)) || ...);
+        return miss;
+    }
+};
+
+// The (input_dim, hidden_dim) pairs the per-pass forward (gnn_kernels.hip) and the backward (backward.hip) have kernels
+// for: one list, so that a shape cannot be trained without a forward or the other way round.
+// (input_dim 4: the hit classifier of gnn/MPNN_HitClassifier.ipynb - r, phi, z and the seed label - and the first
+// shapes whose hit rows [H' | X] have no zero pad column, C == LDH)
+using ModelShapes = ShapeList<Shape<2, 4>, Shape<2, 8>, Shape<2, 16>, Shape<2, 32>, Shape<3, 4>, Shape<3, 8>, Shape<3, 16>,
+                              Shape<3, 32>, Shape<3, 64>, Shape<4, 8>, Shape<4, 16>, Shape<4, 32>, Shape<4, 64>,
+                              Shape<11, 4>, Shape<11, 8>, Shape<11, 16>>;
+
+// every weight (gradient) pointer of a whole-model call is there
+inline bool params_complete(const gnn_params_t *p)
+{
+    return p && p->Win && p->bin && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3 && p->W4 && p->b4;
+}
+inline bool grads_complete(const gnn_grads_t *gr)
+{
+    return gr && gr->Win && gr->bin && gr->W1 && gr->b1 && gr->W2 && gr->b2 && gr->W3 && gr->b3 && gr->W4 && gr->b4;
+}
 
 // csr_build.hip's device-wide scan, shared: exclusive scans of n_arrays (1 or 2) int32 count arrays stored `stride`
 // apart into ptr_a / ptr_b [n + 1] (entry n = the total); `sums` = scan_sums_words(n) int32 of scratch
@@ -196,42 +222,5 @@ __device__ __forceinline__ void csr_walk(int k0, int k1, RowOf row_of, WOf w_of,
         use(w, r);
     }
 }
-
-// forward of the plan-based pipeline (sell_pipeline.hip)
-int sell_forward(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, float *e_out, void *ws,
-                 size_t ws_bytes, hipStream_t s);
-int sell_forward_train(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const int32_t *seg_ptr,
-                       const int32_t *tw_src, const int32_t *tw_dst, float *e_all, float *H_all, float *Q_all, int ldh,
-                       float *e_out, void *ws, size_t ws_bytes, hipStream_t s);
-size_t sell_workspace_bytes(int64_t n_hits, int64_t n_segments, int F, int D);
-int sell_shape_supported(int F, int D);
-int sell_limits(int F, int D, int32_t *out4);
-int sell_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, int training, int32_t *out);
-
-// backward.hip
-int bce_loss(const float *e, const float *y, int64_t n, float scale, float *loss, float *grad_e,
-             float *partial, hipStream_t s);
-size_t backward_workspace_bytes(int64_t n_hits, int64_t n_segments, int F, int D);
-int backward_events_supported(int F, int D, int64_t max_hits, int64_t max_segments);
-size_t backward_events_workspace_bytes(int64_t n_graphs, int F, int D);
-int backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
-                    const int32_t *seg_ptr, int64_t n_graphs, int cap_h, int cap_s, int T,
-                    const float *e_all, const float *H_all, const float *grad_out,
-                    const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s);
-// NodeClassifier's output network y = sigmoid(Wo [H'_T | X] + bo) (gnn/MPNN_HitClassifier.ipynb cell 21): with
-// `head` the backward starts from the hit scores' gradient gy instead of the final edge pass (grad_out unused,
-// e_all holds the n_iters edge passes of the trunk) and adds the head's own gradients into gWo [C], gbo [1]
-struct HeadBwd {
-    const float *Wo, *y, *gy;
-    float *gWo, *gbo;
-};
-int backward(const gnn_graph_t *g, const gnn_params_t *p, int T, const float *e_all,
-             const float *H_all, const float *Q_all, const float *grad_out, const gnn_grads_t *gr,
-             void *ws, size_t ws_bytes, hipStream_t s, const HeadBwd *head = nullptr);
-
-int edge_bwd(const float *H, const gnn_graph_t *g, const gnn_params_t *p, const float *e, const float *ge, float *gH,
-             const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s);
-int node_bwd(const float *H, const float *e, const float *Hn, const gnn_graph_t *g, const gnn_params_t *p,
-             const float *gHn, float *gH, float *ge, const gnn_grads_t *gr, void *ws, size_t ws_bytes, hipStream_t s);
 
 }  // namespace gnn

@@ -359,14 +359,10 @@ int gnn_fxev_forward(const gnn_graph_t *g, const gnn_fx_params_t *p, const gnn_f
     if (E > 0 && N > 0 && (!g->in_eid || !g->in_nbr || !g->out_eid || !g->out_nbr))
         return fail(GNN_ERR_BADARG, "gnn_fxev_forward: a segment list is null");
     const Fx f = fx_of(*fmt);
-#define X_(F_, D_)                                                                                                  \
-    if (p->F == F_ && p->D == D_)                                                                                   \
-        return run_fx_events<F_, D_>(g, p, f, tables, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters,  \
-                                     e_raw, e_float, counts, graph_overflows, e_trace, H_trace,                     \
-                                     static_cast<hipStream_t>(stream));
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "gnn_fxev_forward: no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    return ModelShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {      // (gnn_fx_supported: the shape is listed)
+        return run_fx_events<sh.F, sh.D>(g, p, f, tables, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters,
+                                         e_raw, e_float, counts, graph_overflows, e_trace, H_trace,
+                                         static_cast<hipStream_t>(stream)); });
 }
 
 }  // extern "C"

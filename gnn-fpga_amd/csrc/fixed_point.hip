@@ -290,15 +290,6 @@ unsigned fx_grid(int64_t items, int per_cu)
 
 constexpr size_t kFxLdsMax = 160 * 1024;
 
-template <typename Fn>
-int with_fx_shape(int F, int D, Fn fn)
-{
-#define X_(F_, D_) if (F == F_ && D == D_) return fn(Shape<F_, D_>{});
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no fixed-point kernel for input_dim=%d hidden_dim=%d", F, D);
-}
-
 template <int F, int D>
 int fx_forward_impl(const gnn_graph_t *g, const gnn_fx_params_t *p, const Fx &f, const gnn_fx_tables_t *tb, int T,
                     int32_t *e_raw, float *e_float, int64_t *counts, int32_t *e_trace, int32_t *H_trace, char *ws,
@@ -401,7 +392,7 @@ int gnn_fx_forward(const gnn_graph_t *g, const gnn_fx_params_t *p, const gnn_fx_
         return fail(GNN_ERR_BADARG, "gnn_fx_forward: a segment list is null");
     if (int rc = check_workspace(workspace, workspace_bytes, carve_fx(nullptr, N, E, p->F, p->D).bytes)) return rc;
     const Fx f = fx_of(*fmt);
-    return with_fx_shape(p->F, p->D, [&](auto sh) {
+    return ModelShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {      // (gnn_fx_supported: the shape is listed)
         return fx_forward_impl<sh.F, sh.D>(g, p, f, tables, n_iters, e_raw, e_float, counts, e_trace, H_trace,
                                            align_ws(workspace), static_cast<hipStream_t>(stream));
     });

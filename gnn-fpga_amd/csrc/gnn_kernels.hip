@@ -26,87 +26,16 @@
 //   edge pass   k_edge
 //   node pass   k_node;  wide at >= 2048 hits, and with a NodeClassifier's head at every size: k_node_walkW, k_node_mlpW
 //   gnn_input_fwd / gnn_edge_fwd (k_pq, k_edge) / gnn_node_fwd: one lane per item at every size
+// k_event / run_events: the same forward for batches of small graphs, one launch, one workgroup per graph.
+// The C ABI at the end of the file is that of these kernels only: gnn_input_fwd, gnn_edge_fwd, gnn_node_fwd,
+// gnn_forward_workspace_bytes, gnn_segclf_forward(_train), gnn_nodeclf_forward(_train), gnn_events_supported,
+// gnn_segclf_forward_events, gnn_segclf_forward_train_events.  (The library's core - last error, profiler, ABI version,
+// shape queries - is core.hip; the fused pipeline, the backward and the dense-to-index adapter own their entry points.)
 #include "common.h"
 #include "lane_ops.h"
 #include "event_passes.h"
 
 #include <type_traits>
-
-namespace gnn {
-
-thread_local char g_err[320] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-struct Profiler {
-    bool on = false;
-    int cap = 0;
-    std::vector<hipEvent_t> ev;     // 2 per record
-    std::vector<const char *> name;
-    std::vector<int> start;         // index of the event a record starts at
-    int n = 0;
-    // Inside one library call that launches several kernels back to back (ProfChain), a kernel's
-    // interval starts at the event recorded behind the previous kernel: ONE event per kernel
-    // boundary, so the intervals of a call tile its time exactly - each is the kernel plus the
-    // boundary to the next launch, as in an unprofiled run - instead of two event packets per
-    // kernel, whose processing time (~10 us per pair) ended up inside every interval.
-    bool chain = false, have_prev = false;
-};
-Profiler g_prof;
-
-// GNN_DEBUG_SYNC=1: every launch is named on stderr and waited for - the last name printed before a GPU fault is
-// the kernel that raised it (a debugging switch; never set in measurements)
-static const char *g_dbg_name = nullptr;
-static bool debug_sync()
-{
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("GNN_DEBUG_SYNC"); on = (e && e[0] == '1') ? 1 : 0; }
-    return on == 1;
-}
-
-void prof_pre(const char *name, hipStream_t s)
-{
-    if (debug_sync()) g_dbg_name = name;
-    if (g_prof.on && g_prof.n < g_prof.cap) {
-        g_prof.name[g_prof.n] = name;
-        if (g_prof.chain && g_prof.have_prev && g_prof.n > 0) {
-            g_prof.start[g_prof.n] = 2 * (g_prof.n - 1) + 1;
-        } else {
-            g_prof.start[g_prof.n] = 2 * g_prof.n;
-            (void)hipEventRecord(g_prof.ev[2 * g_prof.n], s);
-        }
-    }
-}
-void prof_post(hipStream_t s)
-{
-    if (debug_sync()) {
-        fprintf(stderr, "[gnn] %s\n", g_dbg_name ? g_dbg_name : "?");
-        fflush(stderr);
-        (void)hipStreamSynchronize(s);
-    }
-    if (g_prof.on && g_prof.n < g_prof.cap) {
-        (void)hipEventRecord(g_prof.ev[2 * g_prof.n + 1], s);
-        g_prof.n++;
-        g_prof.have_prev = true;
-    }
-}
-ProfChain::ProfChain() : prev(g_prof.chain)
-{
-    if (!prev) { g_prof.chain = true; g_prof.have_prev = false; }
-}
-ProfChain::~ProfChain()
-{
-    if (!prev) g_prof.chain = g_prof.have_prev = false;
-}
-
-}  // namespace gnn
 
 namespace {
 using namespace gnn;
@@ -946,31 +875,6 @@ int run_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_p
     return 0;
 }
 
-// max that keeps a NaN (fmaxf drops it): a NaN weight, a NaN feature range or 0 * inf makes the bound NaN, and a NaN
-// bound is not "<= 60" - the caller does not take the exp-product form on a bound that was never computed
-__device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : b != b ? b : b > a ? b : a; }
-
-// bound of |P'|, |Q'| over all hits given |H'| <= 1 and per-feature max |X| (one wavefront)
-__global__ __launch_bounds__(64) void k_exp_bound(const float *__restrict__ W1,
-                                                 const float *__restrict__ b1,
-                                                 const float *__restrict__ xmax, int F, int D,
-                                                 float *__restrict__ out)
-{
-    const int C = F + D;
-    float worst = 0.0f;
-    for (int i = threadIdx.x; i < 2 * D; i += 64) {       // rows of the P block, then the Q block
-        const int row = i % D, half = i / D;
-        float acc = half == 0 ? fabsf(b1[row]) : 0.0f;
-        for (int k = 0; k < C; ++k) {
-            const float w = fabsf(W1[row * 2 * C + half * C + k]);
-            acc += k < D ? w : w * xmax[k - D];
-        }
-        worst = max_nan(worst, acc);
-    }
-    for (int o = 32; o > 0; o >>= 1) worst = max_nan(worst, __shfl_xor(worst, o));
-    if (threadIdx.x == 0) out[0] = 2.8853900817779268f * worst;
-}
-
 // H (padded rows) -> unpadded [n_hits, C] trace rows (parity tests only).
 __global__ __launch_bounds__(kBlock) void k_unpad(const float *__restrict__ H, int ldh, int C,
                                                   float *__restrict__ out, int64_t total)
@@ -983,24 +887,8 @@ __global__ __launch_bounds__(kBlock) void k_unpad(const float *__restrict__ H, i
 // ---------------------------------------------------------------------------------------------
 // host side of the per-pass forward
 // ---------------------------------------------------------------------------------------------
-// fn(Shape<F, D>) for the caller's shape (GNN_FOR_EACH_SHAPE, common.h)
-template <typename Fn>
-int with_fwd_shape(int F, int D, Fn fn)
-{
-#define X_(F_, D_) if (F == F_ && D == D_) return fn(Shape<F_, D_>{});
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", F, D);
-}
-
-bool params_complete(const gnn_params_t *p)
-{
-    return p && p->Win && p->bin && p->W1 && p->b1 && p->W2 && p->b2 && p->W3 && p->b3 && p->W4 && p->b4;
-}
-bool grads_complete(const gnn_grads_t *gr)
-{
-    return gr && gr->Win && gr->bin && gr->W1 && gr->b1 && gr->W2 && gr->b2 && gr->W3 && gr->b3 && gr->W4 && gr->b4;
-}
+// the miss of this unit's shape dispatch (ModelShapes, common.h)
+int no_kernel(int F, int D) { return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", F, D); }
 
 // The environment switch of the per-pass forward (A / B runs, tests): this is its one reader, called once per library
 // call and not cached, like read_bwd_switches - tests flip it inside one process.
@@ -1166,13 +1054,12 @@ int forward_impl(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, const
 // holds gnn_forward_workspace_bytes; then the 256-byte alignment and the shape dispatch.
 int check_forward(const gnn_graph_t *g, const gnn_params_t *p, const void *ws, size_t ws_bytes)
 {
-    if (!gnn_shape_supported(p->F, p->D))
-        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    if (!ModelShapes::has(p->F, p->D)) return no_kernel(p->F, p->D);
     return check_workspace(ws, ws_bytes, carve_fwd(nullptr, g->n_hits, g->n_segments, p->F, p->D).bytes);
 }
 int forward(const gnn_graph_t *g, const gnn_params_t *p, int n_iters, const FwdOut &o, void *ws, void *stream)
 {
-    return with_fwd_shape(p->F, p->D, [&](auto sh) {
+    return ModelShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
         return forward_impl<sh.F, sh.D>(g, p, n_iters, o, align_ws(ws), static_cast<hipStream_t>(stream)); });
 }
 
@@ -1185,27 +1072,24 @@ using namespace gnn;
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
-int gnn_abi_version(void) { return GNN_ABI_VERSION; }
-
-const char *gnn_last_error(void) { return g_err; }
-
-int gnn_shape_supported(int32_t F, int32_t D)
-{
-#define X_(F_, D_) if (F == F_ && D == D_) return 1;
-    GNN_FOR_EACH_SHAPE(X_)
-#undef X_
-    return 0;
-}
-
-int32_t gnn_h_stride(int32_t F, int32_t D)
-{
-    return gnn_shape_supported(F, D) ? ((F + D + 3) & ~3) : 0;
-}
-
 int gnn_events_supported(int32_t F, int32_t D, int64_t max_hits, int64_t max_segments)
 {
     if (!gnn_shape_supported(F, D) || max_hits < 0 || max_segments < 0) return 0;
     return event_lds_bytes(F, D, max_hits, max_segments) <= kEventLdsMax;
+}
+
+// what the two one-launch forwards end with: the last of their checks - the largest graph fits one workgroup's LDS at a
+// shape with kernels - and the launch
+static int events_forward(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr, const int32_t *seg_ptr,
+                          int64_t n_graphs, int32_t max_hits, int32_t max_segments, int32_t n_iters, float *e_out,
+                          float *e_all, float *H_all, void *stream)
+{
+    if (!gnn_events_supported(p->F, p->D, max_hits, max_segments))
+        return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit one workgroup's LDS at input_dim=%d hidden_dim=%d",
+                    max_hits, max_segments, p->F, p->D);
+    return ModelShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
+        return run_events<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_out,
+                                      static_cast<hipStream_t>(stream), e_all, H_all); });
 }
 
 int gnn_segclf_forward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
@@ -1222,12 +1106,7 @@ int gnn_segclf_forward_events(const gnn_graph_t *g, const gnn_params_t *p, const
     if (g->in_ptr ? (!g->out_ptr || (g->n_segments > 0 && (!g->in_eid || !g->in_nbr || !g->out_eid || !g->out_nbr)))
                   : (g->out_ptr || g->in_eid || g->in_nbr || g->out_eid || g->out_nbr) != 0)
         return fail(GNN_ERR_BADARG, "gnn_segclf_forward_events: segment lists incomplete (all six arrays, or none)");
-    if (!gnn_events_supported(p->F, p->D, max_hits, max_segments))
-        return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit one workgroup's LDS at input_dim=%d hidden_dim=%d",
-                    max_hits, max_segments, p->F, p->D);
-    return with_fwd_shape(p->F, p->D, [&](auto sh) {
-        return run_events<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_out,
-                                      static_cast<hipStream_t>(stream)); });
+    return events_forward(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_out, nullptr, nullptr, stream);
 }
 
 int gnn_input_fwd(const float *X, const float *Win, const float *bin, float *H, int64_t n_hits,
@@ -1239,7 +1118,8 @@ int gnn_input_fwd(const float *X, const float *Win, const float *bin, float *H, 
     gnn_params_t p = {};
     g.X = X, g.n_hits = n_hits;
     p.Win = Win, p.bin = bin;
-    return with_fwd_shape(F, D, [&](auto sh) {
+    if (!ModelShapes::has(F, D)) return no_kernel(F, D);
+    return ModelShapes::find<int>(F, D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
         return FwdRun<sh.F, sh.D>(&g, &p, nullptr, static_cast<hipStream_t>(stream), kOneLane).input(H, ldh, nullptr, nullptr); });
 }
 
@@ -1255,7 +1135,8 @@ int gnn_edge_fwd(const float *H, int32_t ldh, const int32_t *src, const int32_t 
     gnn_params_t p = {};
     g.src = src, g.dst = dst, g.n_hits = n_hits, g.n_segments = n_segments;
     p.W1 = W1, p.b1 = b1, p.W2 = W2, p.b2 = b2;
-    return with_fwd_shape(F, D, [&](auto sh) {
+    if (!ModelShapes::has(F, D)) return no_kernel(F, D);
+    return ModelShapes::find<int>(F, D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
         const FwdRun<sh.F, sh.D> c(&g, &p, nullptr, static_cast<hipStream_t>(stream), kOneLane);
         if (int rc = c.pq(H, ldh, pq_ws)) return rc;
         return c.edge(pq_ws, e); });
@@ -1272,7 +1153,8 @@ int gnn_node_fwd(const float *H, int32_t ldh, const float *e, const gnn_graph_t 
     if (Hnext == H) return fail(GNN_ERR_BADARG, "gnn_node_fwd: Hnext must not alias H");
     gnn_params_t p = {};
     p.W3 = W3, p.b3 = b3, p.W4 = W4, p.b4 = b4;
-    return with_fwd_shape(F, D, [&](auto sh) {
+    if (!ModelShapes::has(F, D)) return no_kernel(F, D);
+    return ModelShapes::find<int>(F, D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
         return FwdRun<sh.F, sh.D>(g, &p, nullptr, static_cast<hipStream_t>(stream), kOneLane)
             .node(H, ldh, e, Hnext, nullptr, nullptr, nullptr); });
 }
@@ -1315,27 +1197,6 @@ int gnn_segclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, int32_
     return forward(g, p, n_iters, {last, e_all, nullptr, H_all, Q_all, nullptr}, workspace, stream);
 }
 
-size_t gnn_backward_workspace_bytes(int64_t n_hits, int64_t n_segments, int32_t F, int32_t D)
-{
-    if (n_hits < 0 || n_segments < 0 || F <= 0 || D <= 0) return 0;
-    return backward_workspace_bytes(n_hits, n_segments, F, D);
-}
-
-int gnn_segclf_backward(const gnn_graph_t *g, const gnn_params_t *p, int32_t n_iters,
-                        const float *e_all, const float *H_all, const float *Q_all,
-                        const float *grad_out, const gnn_grads_t *gr, void *workspace,
-                        size_t workspace_bytes, void *stream)
-{
-    gnn::ProfChain chain_;
-    if (!g || !p || !gr || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0 || !workspace)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_backward: bad argument");
-    if ((g->n_segments > 0 && (!e_all || !grad_out)) || (g->n_hits > 0 && !H_all))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_backward: saved tensors missing");
-    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward: gradient pointer missing");
-    return backward(g, p, n_iters, e_all, H_all, Q_all, grad_out, gr, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream));
-}
-
 // ---- NodeClassifier (gnn/MPNN_HitClassifier.ipynb cells 20-21): the trunk above, the output network in place
 // of the final edge pass ------------------------------------------------------------------------------------
 static int nodeclf_check(const char *who, const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo,
@@ -1372,97 +1233,6 @@ int gnn_nodeclf_forward_train(const gnn_graph_t *g, const gnn_params_t *p, const
     return forward(g, p, n_iters, {nullptr, e_all, nullptr, H_all, Q_all, &head}, workspace, stream);
 }
 
-int gnn_nodeclf_backward(const gnn_graph_t *g, const gnn_params_t *p, const float *Wo, const float *bo, int32_t n_iters,
-                         const float *e_all, const float *H_all, const float *Q_all, const float *y, const float *grad_y,
-                         const gnn_grads_t *gr, float *gWo, float *gbo, void *workspace, size_t workspace_bytes,
-                         void *stream)
-{
-    gnn::ProfChain chain_;
-    if (!g || !p || !gr || !Wo || !bo || !gWo || !gbo || n_iters < 0 || g->n_hits < 0 || g->n_segments < 0 || !workspace)
-        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: bad argument");
-    if ((n_iters > 0 && g->n_segments > 0 && !e_all) || (g->n_hits > 0 && (!H_all || !y || !grad_y)))
-        return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: saved tensors missing");
-    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_nodeclf_backward: gradient pointer missing");
-    if (!gnn_shape_supported(p->F, p->D))
-        return fail(GNN_ERR_UNSUPPORTED, "no kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    const HeadBwd head = {Wo, y, grad_y, gWo, gbo};
-    return backward(g, p, n_iters, e_all, H_all, Q_all, nullptr, gr, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream), &head);
-}
-
-// dense one-hot incidence matrices -> index form, where the matrices live (the reference's input
-// contract: [B, N, E] float32 with one 1 per real column, all-zero padded columns;
-// gnn/graph.py:28-35, gnn/trainSegmentClassifier.py:66-95).  One lane per (batch, column): the N
-// rows of a column are read with the column index fastest across lanes (coalesced).  O(B N E)
-// reads - the price of the dense contract, paid once per batch on the device instead of a PCIe
-// round trip.  flags[0] |= 1: a column with more than one non-zero, |= 2: a column set in only one
-// of Ri / Ro.
-__global__ __launch_bounds__(256) void k_dense_to_index(const float *__restrict__ Ri, const float *__restrict__ Ro,
-                                                        int64_t B, int64_t N, int64_t E, int32_t *__restrict__ src,
-                                                        int32_t *__restrict__ dst, int32_t *flags)
-{
-    int bad = 0;
-    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < B * E; c += (int64_t)gridDim.x * 256) {
-        const int64_t b = c / E, j = c % E;
-        const float *ri = Ri + b * N * E + j, *ro = Ro + b * N * E + j;
-        int ci = 0, co = 0;
-        int64_t di = -1, so = -1;
-        for (int64_t n = 0; n < N; ++n) {
-            if (ri[n * E] != 0.0f) { if (!ci) di = n; ++ci; }
-            if (ro[n * E] != 0.0f) { if (!co) so = n; ++co; }
-        }
-        if (ci > 1 || co > 1) bad |= 1;
-        if ((ci == 0) != (co == 0)) bad |= 2;
-        const bool real = ci == 1 && co == 1;
-        src[c] = real ? (int32_t)(b * N + so) : -1;
-        dst[c] = real ? (int32_t)(b * N + di) : -1;
-    }
-    if (bad) atomicOr(flags, bad);
-}
-
-int gnn_dense_to_index(const float *Ri, const float *Ro, int64_t B, int64_t N, int64_t E, int32_t *src, int32_t *dst,
-                       int32_t *flags, void *stream)
-{
-    if (B < 0 || N < 0 || E < 0 || !flags || (B * E > 0 && (!Ri || !Ro || !src || !dst)))
-        return fail(GNN_ERR_BADARG, "gnn_dense_to_index: bad argument");
-    if (B * N >= (1ll << 31) || B * E >= (1ll << 31))
-        return fail(GNN_ERR_UNSUPPORTED, "gnn_dense_to_index: batch too large for 32-bit ids");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t err = hipMemsetAsync(flags, 0, sizeof(int32_t), s);
-    if (err != hipSuccess) return fail(-(int)err, "memset of the flag failed");
-    if (B * E > 0) {
-        const int64_t g = (B * E + 255) / 256;
-        GNN_LAUNCH("k_dense_to_index", k_dense_to_index, (unsigned)(g < 65536 ? g : 65536), 256, s, Ri, Ro, B, N, E, src,
-                   dst, flags);
-    }
-    return 0;
-}
-
-int gnn_edge_bwd(const float *H, int32_t ldh, const gnn_graph_t *g, const gnn_params_t *p, const float *e,
-                 const float *grad_e, float *grad_H, const gnn_grads_t *gr, void *workspace,
-                 size_t workspace_bytes, void *stream)
-{
-    if (!g || !p || !workspace || g->n_hits < 0 || g->n_segments < 0 || !grads_complete(gr))
-        return fail(GNN_ERR_BADARG, "gnn_edge_bwd: bad argument");
-    if (ldh != gnn_h_stride(p->F, p->D)) return fail(GNN_ERR_BADARG, "gnn_edge_bwd: ldh must be gnn_h_stride(F, D)");
-    if ((g->n_hits > 0 && (!H || !grad_H)) || (g->n_segments > 0 && (!e || !grad_e)))
-        return fail(GNN_ERR_BADARG, "gnn_edge_bwd: tensor missing");
-    return edge_bwd(H, g, p, e, grad_e, grad_H, gr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gnn_node_bwd(const float *H, int32_t ldh, const float *e, const float *Hnext, const gnn_graph_t *g,
-                 const gnn_params_t *p, const float *grad_Hnext, float *grad_H, float *grad_e,
-                 const gnn_grads_t *gr, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!g || !p || !workspace || g->n_hits < 0 || g->n_segments < 0 || !grads_complete(gr))
-        return fail(GNN_ERR_BADARG, "gnn_node_bwd: bad argument");
-    if (ldh != gnn_h_stride(p->F, p->D)) return fail(GNN_ERR_BADARG, "gnn_node_bwd: ldh must be gnn_h_stride(F, D)");
-    if ((g->n_hits > 0 && (!H || !Hnext || !grad_Hnext || !grad_H)) || (g->n_segments > 0 && (!e || !grad_e)))
-        return fail(GNN_ERR_BADARG, "gnn_node_bwd: tensor missing");
-    return node_bwd(H, e, Hnext, g, p, grad_Hnext, grad_H, grad_e, gr, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream));
-}
-
 int gnn_segclf_forward_train_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
                                     const int32_t *seg_ptr, int64_t n_graphs, int32_t max_hits,
                                     int32_t max_segments, int32_t n_iters, float *e_all, float *H_all,
@@ -1473,156 +1243,7 @@ int gnn_segclf_forward_train_events(const gnn_graph_t *g, const gnn_params_t *p,
     if (n_graphs > 0 && (!hit_ptr || !seg_ptr)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_events: graph offsets missing");
     if (g->n_segments > 0 && (!e_all || !g->src || !g->dst)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_events: segment arrays missing");
     if (g->n_hits > 0 && (!H_all || !g->X || !g->in_ptr || !g->out_ptr)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_events: hit arrays missing");
-    if (!gnn_events_supported(p->F, p->D, max_hits, max_segments))
-        return fail(GNN_ERR_UNSUPPORTED, "events of up to %d hits / %d segments do not fit one workgroup's LDS at input_dim=%d hidden_dim=%d",
-                    max_hits, max_segments, p->F, p->D);
-    return with_fwd_shape(p->F, p->D, [&](auto sh) {
-        return run_events<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, nullptr,
-                                      static_cast<hipStream_t>(stream), e_all, H_all); });
-}
-
-int gnn_events_backward_supported(int32_t F, int32_t D, int64_t max_hits, int64_t max_segments)
-{
-    if (max_hits < 0 || max_segments < 0) return 0;
-    return backward_events_supported(F, D, max_hits, max_segments);
-}
-
-size_t gnn_backward_events_workspace_bytes(int64_t n_graphs, int32_t F, int32_t D)
-{
-    return backward_events_workspace_bytes(n_graphs, F, D);
-}
-
-int gnn_segclf_backward_events(const gnn_graph_t *g, const gnn_params_t *p, const int32_t *hit_ptr,
-                               const int32_t *seg_ptr, int64_t n_graphs, int32_t max_hits,
-                               int32_t max_segments, int32_t n_iters, const float *e_all,
-                               const float *H_all, const float *grad_out, const gnn_grads_t *gr,
-                               void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!g || !p || !gr || n_iters < 0 || n_graphs < 0 || max_hits < 0 || max_segments < 0 || !workspace)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: bad argument");
-    if (n_graphs > 0 && (!hit_ptr || !seg_ptr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: graph offsets missing");
-    if ((g->n_segments > 0 && (!e_all || !grad_out || !g->src || !g->dst)) || (g->n_hits > 0 && (!H_all || !g->in_ptr || !g->out_ptr)))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: saved tensors or graph arrays missing");
-    if (!grads_complete(gr)) return fail(GNN_ERR_BADARG, "gnn_segclf_backward_events: gradient pointer missing");
-    return backward_events(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, e_all, H_all,
-                           grad_out, gr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gnn_bce_loss(const float *e, const float *y, int64_t n, float scale, float *loss_out,
-                 float *grad_e, void *workspace, void *stream)
-{
-    if (n < 0 || !loss_out || !workspace || (n > 0 && (!e || !y)))
-        return fail(GNN_ERR_BADARG, "gnn_bce_loss: bad argument");
-    return bce_loss(e, y, n, scale, loss_out, grad_e, static_cast<float *>(workspace),
-                    static_cast<hipStream_t>(stream));
-}
-
-size_t gnn_plan_workspace_bytes(int64_t n_pad, int64_t n_segments, int32_t F, int32_t D)
-{
-    if (n_pad < 0 || n_segments < 0) return 0;
-    return sell_workspace_bytes(n_pad, n_segments, F, D);
-}
-
-int gnn_plan_shape_supported(int32_t F, int32_t D) { return sell_shape_supported(F, D); }
-
-int gnn_plan_limits(int32_t F, int32_t D, int32_t *out4)
-{
-    if (!out4) return fail(GNN_ERR_BADARG, "gnn_plan_limits: null output");
-    return sell_limits(F, D, out4);
-}
-
-int gnn_plan_route(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters, int32_t training, int32_t *out)
-{
-    if (!pl || !p || !out || n_iters < 0 || pl->n_pad < 0 || pl->n_tiles < 0 || pl->iter_lds_records < 0 ||
-        pl->edge_lds_rows < 0 || pl->iter_lds_in < 0 || pl->iter_lds_out < 0)
-        return fail(GNN_ERR_BADARG, "gnn_plan_route: bad argument");
-    return sell_route(pl, p, n_iters, training, out);
-}
-
-int gnn_segclf_forward_plan(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters,
-                            float *e_out, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!pl || !p || n_iters < 0 || pl->n_pad < 0 || pl->n_segments < 0 || pl->n_tiles < 0 ||
-        pl->n_chunks < 0 || (pl->n_pad & 15))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: bad argument");
-    if (pl->iter_lds_records < 0 || pl->edge_lds_rows < 0)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: negative LDS size");
-    if (!pl->X || !pl->in_off || !pl->out_off || (pl->n_tiles > 0 && !pl->tiles) ||
-        (pl->n_segments > 0 && (!pl->src || !pl->dst || !pl->sd16 || !pl->chunks || !e_out)))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: plan array missing");
-    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: weight pointer missing");
-    return sell_forward(pl, p, n_iters, e_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gnn_segclf_forward_train_plan(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters,
-                                  const int32_t *seg_ptr, const int32_t *tw_src, const int32_t *tw_dst, float *e_all,
-                                  float *H_all, float *Q_all, float *e_out, void *workspace, size_t workspace_bytes,
-                                  void *stream)
-{
-    if (!pl || !p || n_iters < 0 || pl->n_pad < 0 || pl->n_segments < 0 || pl->n_tiles < 0 ||
-        pl->n_chunks < 0 || (pl->n_pad & 15) || pl->iter_lds_records < 0 || pl->edge_lds_rows < 0)
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: bad argument");
-    if (!pl->X || !pl->in_off || !pl->out_off || !pl->in_nbr || !pl->out_nbr || (pl->n_tiles > 0 && !pl->tiles) ||
-        (pl->n_segments > 0 && (!pl->src || !pl->dst || !pl->sd16 || !pl->chunks || !e_all)))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: plan array missing");
-    if (pl->n_segments > 0 && ((!tw_src != !tw_dst) || (!e_out && !tw_src)))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: e_out or the (tw_src, tw_dst) pair is needed");
-    if (pl->n_pad > 0 && (!seg_ptr || !H_all || (n_iters > 0 && !Q_all)))
-        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: output array missing");
-    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: weight pointer missing");
-    const int ldh = gnn_h_stride(p->F, p->D);
-    if (ldh <= 0) return fail(GNN_ERR_UNSUPPORTED, "no HIP kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
-    return sell_forward_train(pl, p, n_iters, seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh, e_out, workspace,
-                              workspace_bytes, static_cast<hipStream_t>(stream));
-}
-
-int gnn_exp_product_bound(const gnn_params_t *p, const float *x_absmax, float *bound_out,
-                          void *stream)
-{
-    if (!p || !p->W1 || !p->b1 || !x_absmax || !bound_out || p->F <= 0 || p->D <= 0)
-        return fail(GNN_ERR_BADARG, "gnn_exp_product_bound: bad argument");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    GNN_LAUNCH("k_exp_bound", k_exp_bound, 1, 64, s, p->W1, p->b1, x_absmax, p->F, p->D, bound_out);
-    return 0;
-}
-
-int gnn_profile_begin(int32_t capacity)
-{
-    if (capacity <= 0) return fail(GNN_ERR_BADARG, "gnn_profile_begin: capacity must be positive");
-    for (hipEvent_t ev : g_prof.ev) (void)hipEventDestroy(ev);
-    g_prof.ev.assign(2 * (size_t)capacity, nullptr);
-    g_prof.name.assign((size_t)capacity, nullptr);
-    g_prof.start.assign((size_t)capacity, 0);
-    g_prof.chain = g_prof.have_prev = false;
-    for (auto &ev : g_prof.ev) {
-        hipError_t err = hipEventCreate(&ev);
-        if (err != hipSuccess) return fail(-(int)err, "hipEventCreate failed");
-    }
-    g_prof.cap = capacity;
-    g_prof.n = 0;
-    g_prof.on = true;
-    return 0;
-}
-
-int gnn_profile_end(const char **names, float *ms, int32_t capacity_out)
-{
-    g_prof.on = false;
-    const int n = g_prof.n;
-    for (int i = 0; i < n; ++i) {
-        hipError_t err = hipEventSynchronize(g_prof.ev[2 * i + 1]);
-        if (err != hipSuccess) return fail(-(int)err, "hipEventSynchronize failed");
-        if (i < capacity_out) {
-            float t = 0.0f;
-            (void)hipEventElapsedTime(&t, g_prof.ev[g_prof.start[i]], g_prof.ev[2 * i + 1]);
-            if (ms) ms[i] = t;
-            if (names) names[i] = g_prof.name[i];
-        }
-    }
-    for (hipEvent_t ev : g_prof.ev) (void)hipEventDestroy(ev);
-    g_prof.ev.clear();
-    g_prof.n = 0;
-    g_prof.cap = 0;
-    return n;
+    return events_forward(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, n_iters, nullptr, e_all, H_all, stream);
 }
 
 }  // extern "C"

@@ -17,10 +17,10 @@
 namespace {
 using namespace gnn;
 
-// the shapes of GNN_FOR_EACH_SHAPE up to hidden_dim 32 (at 64 one pass's weights alone take 103 KB of LDS)
-#define ITER_SHAPES(X_) \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(4, 8) X_(4, 16) X_(4, 32) \
-    X_(11, 4) X_(11, 8) X_(11, 16)
+// the shapes of ModelShapes (common.h) up to hidden_dim 32 (at 64 one pass's weights alone take 103 KB of LDS)
+using IterShapes = ShapeList<Shape<2, 4>, Shape<2, 8>, Shape<2, 16>, Shape<2, 32>, Shape<3, 4>, Shape<3, 8>, Shape<3, 16>,
+                             Shape<3, 32>, Shape<4, 8>, Shape<4, 16>, Shape<4, 32>, Shape<11, 4>, Shape<11, 8>,
+                             Shape<11, 16>>;
 
 constexpr size_t kIterLdsMax = 128 * 1024;      // of the CU's 160 KB, as k_event
 
@@ -668,20 +668,12 @@ __global__ __launch_bounds__(kBlock) void k_iter_input_bwd(const float *__restri
     }
 }
 
-int shape_known(int F, int D)
-{
-#define X_(F_, D_) if (F == F_ && D == D_) return 1;
-    ITER_SHAPES(X_)
-#undef X_
-    return 0;
-}
-
 int check_params(const char *who, const gnn_iter_params_t *p)
 {
     if (!p) return fail(GNN_ERR_BADARG, "%s: params missing", who);
     if (p->n_iters < 0 || p->n_iters > GNN_ITER_MAX)
         return fail(GNN_ERR_BADARG, "%s: n_iters must be in [0, %d], got %d", who, GNN_ITER_MAX, p->n_iters);
-    if (!shape_known(p->F, p->D))
+    if (!IterShapes::has(p->F, p->D))
         return fail(GNN_ERR_UNSUPPORTED, "%s: no per-iteration kernel for input_dim=%d hidden_dim=%d", who, p->F, p->D);
     auto whole = [](const gnn_iter_set_t &s) { return s.Wa && s.ba && s.Wb && s.bb; };
     auto same = [](const gnn_iter_set_t &a, const gnn_iter_set_t &b) {
@@ -718,13 +710,9 @@ extern "C" {
 int gnn_iter_events_supported(int32_t F, int32_t D, int64_t max_hits, int64_t max_segments, int32_t backward)
 {
     if (max_hits < 0 || max_segments < 0 || max_hits >= (1 << 20) || max_segments >= (1 << 24)) return 0;
-#define X_(F_, D_)                                                                                   \
-    if (F == F_ && D == D_)                                                                          \
-        return ev_fwd_lds_bytes(F_, D_, max_hits, max_segments, ItFwd<F_, D_>::w_total) <= kIterLdsMax && \
-               (!backward || EvBwd<F_, D_>::lds_bytes(max_hits, max_segments) <= kIterLdsMax);
-    ITER_SHAPES(X_)
-#undef X_
-    return 0;
+    return IterShapes::find<int>(F, D, 0, [&](auto sh) {
+        return ev_fwd_lds_bytes(sh.F, sh.D, max_hits, max_segments, ItFwd<sh.F, sh.D>::w_total) <= kIterLdsMax &&
+               (!backward || EvBwd<sh.F, sh.D>::lds_bytes(max_hits, max_segments) <= kIterLdsMax); });
 }
 
 int gnn_iter_forward_events(const gnn_graph_t *g, const gnn_iter_params_t *p, const int32_t *hit_ptr,
@@ -741,25 +729,21 @@ int gnn_iter_forward_events(const gnn_graph_t *g, const gnn_iter_params_t *p, co
     if (!gnn_iter_events_supported(p->F, p->D, max_hits, max_segments, 0))
         return fail(GNN_ERR_UNSUPPORTED, "%s: graphs of up to %d hits / %d segments do not fit one workgroup's LDS at "
                     "input_dim=%d hidden_dim=%d", who, max_hits, max_segments, p->F, p->D);
-#define X_(F_, D_)                                                                                              \
-    if (p->F == F_ && p->D == D_)                                                                               \
-        return run_iter_forward<F_, D_>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, e_out, e_all, \
-                                        H_all, static_cast<hipStream_t>(stream));
-    ITER_SHAPES(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "%s: no kernel", who);
+    return IterShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {      // (check_params: the shape is listed)
+        return run_iter_forward<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, e_out, e_all, H_all,
+                                            static_cast<hipStream_t>(stream)); });
 }
 
 int64_t gnn_iter_grad_floats(int32_t F, int32_t D, int32_t n_iters, int32_t shared)
 {
-    if (!shape_known(F, D) || n_iters < 0 || n_iters > GNN_ITER_MAX) return 0;
+    if (!IterShapes::has(F, D) || n_iters < 0 || n_iters > GNN_ITER_MAX) return 0;
     const IterLayout lay(F, D, n_iters);
     return shared ? lay.shared_floats() : lay.stride();
 }
 
 size_t gnn_iter_backward_workspace_bytes(int64_t n_graphs, int32_t F, int32_t D, int32_t n_iters)
 {
-    if (!shape_known(F, D) || n_iters < 0 || n_iters > GNN_ITER_MAX || n_graphs < 0) {
+    if (!IterShapes::has(F, D) || n_iters < 0 || n_iters > GNN_ITER_MAX || n_graphs < 0) {
         fail(GNN_ERR_BADARG, "gnn_iter_backward_workspace_bytes: bad argument");
         return 0;
     }
@@ -782,13 +766,9 @@ int gnn_iter_backward_events(const gnn_graph_t *g, const gnn_iter_params_t *p, c
                     "input_dim=%d hidden_dim=%d", who, max_hits, max_segments, p->F, p->D);
     if (int rc = check_workspace(workspace, workspace_bytes, gnn_iter_backward_workspace_bytes(n_graphs, p->F, p->D, p->n_iters)))
         return rc;
-#define X_(F_, D_)                                                                                                   \
-    if (p->F == F_ && p->D == D_)                                                                                    \
-        return run_iter_backward<F_, D_>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, e_all, H_all,     \
-                                         grad_out, grads_flat, align_ws(workspace), static_cast<hipStream_t>(stream));
-    ITER_SHAPES(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "%s: no kernel", who);
+    return IterShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {      // (check_params: the shape is listed)
+        return run_iter_backward<sh.F, sh.D>(g, p, hit_ptr, seg_ptr, n_graphs, max_hits, max_segments, e_all, H_all,
+                                             grad_out, grads_flat, align_ws(workspace), static_cast<hipStream_t>(stream)); });
 }
 
 size_t gnn_iter_input_bwd_workspace_bytes(int64_t n_hits, int32_t F, int32_t D)

@@ -47,6 +47,12 @@
 // wasted) and bound the kernel.  Tiles whose windows exceed the LDS budget (irregular graphs)
 // gather from global memory instead, with workgroups renumbered so that each XCD walks a
 // contiguous range of tiles (whole graphs stay in one XCD's L2).
+//
+// Host side (below the kernels): choose_route, one launcher per kernel family, forward_t.  The unit owns its C ABI, at
+// the end of the file: gnn_plan_workspace_bytes, gnn_plan_shape_supported, gnn_plan_limits, gnn_plan_route,
+// gnn_segclf_forward_plan and gnn_segclf_forward_train_plan (plan checks: check_plan), which dispatch over PlanShapes
+// straight into forward_any / choose_route / carve / Cfg; and gnn_exp_product_bound with its kernel k_exp_bound, the
+// bound that lets a caller set GNN_FLAG_EXP_PRODUCT.
 #include "common.h"
 #include "lane_ops.h"
 
@@ -3599,6 +3605,7 @@ int forward_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const Sw
     }
 }
 
+// the shapes the pipeline has kernels for: ModelShapes (common.h) without input_dim 4
 #ifdef GNN_QUICK      // compile-time experiments: one shape only
 #ifndef GNN_QUICK_F
 #define GNN_QUICK_F 3
@@ -3606,81 +3613,121 @@ int forward_t(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const Sw
 #ifndef GNN_QUICK_D
 #define GNN_QUICK_D 8
 #endif
-#define SELL_FOR_EACH_SHAPE(X_) X_(GNN_QUICK_F, GNN_QUICK_D)
+using PlanShapes = ShapeList<Shape<GNN_QUICK_F, GNN_QUICK_D>>;
 #else
-#define SELL_FOR_EACH_SHAPE(X_)                                                          \
-    X_(2, 4) X_(2, 8) X_(2, 16) X_(2, 32) X_(3, 4) X_(3, 8) X_(3, 16) X_(3, 32) X_(3, 64) \
-    X_(11, 4) X_(11, 8) X_(11, 16)
+using PlanShapes = ShapeList<Shape<2, 4>, Shape<2, 8>, Shape<2, 16>, Shape<2, 32>, Shape<3, 4>, Shape<3, 8>, Shape<3, 16>,
+                             Shape<3, 32>, Shape<3, 64>, Shape<11, 4>, Shape<11, 8>, Shape<11, 16>>;
 #endif
 
-// what sell_forward and sell_forward_train share: the workspace check, the switches, the shape dispatch
+int no_fused_kernel(int F, int D)
+{
+    return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", F, D);
+}
+
+// gnn_plan_workspace_bytes; 0: no kernels for the shape
+size_t plan_workspace_bytes(int64_t n_pad, int F, int D)
+{
+    return PlanShapes::find<size_t>(F, D, 0, [&](auto sh) { return carve<sh.F, sh.D>(nullptr, n_pad).bytes; });
+}
+
+// What the two forwards share once check_plan has passed: the workspace check, the switches, the shape dispatch.
+// Inside forward_t the plan's sizes are non-negative, n_pad is a multiple of 16, every array the route reads is
+// there, and ws holds gnn_plan_workspace_bytes.
 template <bool TR>
 int forward_any(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const TrainArgs &tr, float *e_out, void *ws,
                 size_t ws_bytes, hipStream_t s)
 {
     ProfChain chain_;      // (profiling runs: one event per kernel boundary of this call)
-    const size_t need = sell_workspace_bytes(pl->n_pad, pl->n_segments, p->F, p->D);
-    if (need == 0) return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const size_t need = plan_workspace_bytes(pl->n_pad, p->F, p->D);
+    if (need == 0) return no_fused_kernel(p->F, p->D);
     if (int rc = check_workspace(ws, ws_bytes, need)) return rc;
     const Switches sw = read_switches();
-#define X_(F_, D_)                                                                                            \
-    if (p->F == F_ && p->D == D_)                                                                            \
-        return (p->flags & GNN_FLAG_EXP_PRODUCT) ? forward_t<F_, D_, true, TR>(pl, p, n_iters, sw, tr, e_out, align_ws(ws), s) \
-                                                 : forward_t<F_, D_, false, TR>(pl, p, n_iters, sw, tr, e_out, align_ws(ws), s);
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "unreachable");
+    return PlanShapes::find<int>(p->F, p->D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
+        return with_flag(p->flags & GNN_FLAG_EXP_PRODUCT, [&](auto xp) {
+            return forward_t<sh.F, sh.D, decltype(xp)::value, TR>(pl, p, n_iters, sw, tr, e_out, align_ws(ws), s); }); });
+}
+
+// The plan checks of gnn_segclf_forward_plan and gnn_segclf_forward_train_plan.  `scores` is where every segment's
+// score goes (e_out; e_all of a training forward, which also walks both neighbour lists and has no message of its own
+// for a negative LDS size).
+int check_plan(const char *who, const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, bool training, const float *scores)
+{
+    if (!pl || !p || n_iters < 0 || pl->n_pad < 0 || pl->n_segments < 0 || pl->n_tiles < 0 || pl->n_chunks < 0 ||
+        (pl->n_pad & 15))
+        return fail(GNN_ERR_BADARG, "%s: bad argument", who);
+    if (pl->iter_lds_records < 0 || pl->edge_lds_rows < 0)
+        return training ? fail(GNN_ERR_BADARG, "%s: bad argument", who) : fail(GNN_ERR_BADARG, "%s: negative LDS size", who);
+    if (!pl->X || !pl->in_off || !pl->out_off || (training && (!pl->in_nbr || !pl->out_nbr)) ||
+        (pl->n_tiles > 0 && !pl->tiles) ||
+        (pl->n_segments > 0 && (!pl->src || !pl->dst || !pl->sd16 || !pl->chunks || !scores)))
+        return fail(GNN_ERR_BADARG, "%s: plan array missing", who);
+    return 0;
+}
+
+// max that keeps a NaN (fmaxf drops it): a NaN weight, a NaN feature range or 0 * inf makes the bound NaN, and a NaN
+// bound is not "<= 60" - the caller does not take the exp-product form on a bound that was never computed
+__device__ __forceinline__ float max_nan(float a, float b) { return a != a ? a : b != b ? b : b > a ? b : a; }
+
+// What justifies GNN_FLAG_EXP_PRODUCT:
+// bound of |P'|, |Q'| over all hits given |H'| <= 1 and per-feature max |X| (one wavefront)
+__global__ __launch_bounds__(64) void k_exp_bound(const float *__restrict__ W1,
+                                                 const float *__restrict__ b1,
+                                                 const float *__restrict__ xmax, int F, int D,
+                                                 float *__restrict__ out)
+{
+    const int C = F + D;
+    float worst = 0.0f;
+    for (int i = threadIdx.x; i < 2 * D; i += 64) {       // rows of the P block, then the Q block
+        const int row = i % D, half = i / D;
+        float acc = half == 0 ? fabsf(b1[row]) : 0.0f;
+        for (int k = 0; k < C; ++k) {
+            const float w = fabsf(W1[row * 2 * C + half * C + k]);
+            acc += k < D ? w : w * xmax[k - D];
+        }
+        worst = max_nan(worst, acc);
+    }
+    for (int o = 32; o > 0; o >>= 1) worst = max_nan(worst, __shfl_xor(worst, o));
+    if (threadIdx.x == 0) out[0] = 2.8853900817779268f * worst;
 }
 
 }  // namespace
 
-namespace gnn {
+using namespace gnn;
 
-int sell_shape_supported(int F, int D)
+// ---------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+size_t gnn_plan_workspace_bytes(int64_t n_pad, int64_t n_segments, int32_t F, int32_t D)
 {
-#define X_(F_, D_) if (F == F_ && D == D_) return 1;
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    return 0;
+    if (n_pad < 0 || n_segments < 0) return 0;
+    return plan_workspace_bytes(n_pad, F, D);
 }
 
-int sell_limits(int F, int D, int32_t *out4)
+int gnn_plan_shape_supported(int32_t F, int32_t D) { return PlanShapes::has(F, D); }
+
+int gnn_plan_limits(int32_t F, int32_t D, int32_t *out4)
 {
-#define X_(F_, D_)                                               \
-    if (F == F_ && D == D_) {                                    \
-        out4[0] = Cfg<F_, D_>::tile_hits;                        \
-        out4[1] = Cfg<F_, D_>::it_rec;                           \
-        out4[2] = Cfg<F_, D_>::chunk_segments;                   \
-        out4[3] = Cfg<F_, D_>::ed_rec;                           \
-        return 0;                                                \
-    }
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", F, D);
+    if (!out4) return fail(GNN_ERR_BADARG, "gnn_plan_limits: null output");
+    if (!PlanShapes::has(F, D)) return no_fused_kernel(F, D);
+    return PlanShapes::find<int>(F, D, GNN_ERR_UNSUPPORTED, [&](auto sh) {
+        using G = Cfg<sh.F, sh.D>;
+        out4[0] = G::tile_hits, out4[1] = G::it_rec, out4[2] = G::chunk_segments, out4[3] = G::ed_rec;
+        return 0; });
 }
 
-size_t sell_workspace_bytes(int64_t n_pad, int64_t n_segments, int F, int D)
+// choose_route's answer as GNN_ROUTE_FIELDS small integers
+int gnn_plan_route(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters, int32_t training, int32_t *out)
 {
-    (void)n_segments;
-#define X_(F_, D_) if (F == F_ && D == D_) return carve<F_, D_>(nullptr, n_pad).bytes;
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    return 0;
-}
-
-// gnn_plan_route: choose_route's answer as GNN_ROUTE_FIELDS small integers
-int sell_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, int training, int32_t *out)
-{
+    if (!pl || !p || !out || n_iters < 0 || pl->n_pad < 0 || pl->n_tiles < 0 || pl->iter_lds_records < 0 ||
+        pl->edge_lds_rows < 0 || pl->iter_lds_in < 0 || pl->iter_lds_out < 0)
+        return fail(GNN_ERR_BADARG, "gnn_plan_route: bad argument");
+    if (!PlanShapes::has(p->F, p->D)) return no_fused_kernel(p->F, p->D);
     const Switches sw = read_switches();
-    Route r{};
-#define X_(F_, D_)                                                                                       \
-    if (p->F == F_ && p->D == D_)                                                                       \
-        r = (p->flags & GNN_FLAG_EXP_PRODUCT) ? choose_route<F_, D_, true>(pl, p, n_iters, sw, training != 0) \
-                                              : choose_route<F_, D_, false>(pl, p, n_iters, sw, training != 0);
-    SELL_FOR_EACH_SHAPE(X_)
-#undef X_
-    if (!sell_shape_supported(p->F, p->D))
-        return fail(GNN_ERR_UNSUPPORTED, "no fused kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    const Route r = PlanShapes::find<Route>(p->F, p->D, Route{}, [&](auto sh) {
+        return (p->flags & GNN_FLAG_EXP_PRODUCT) ? choose_route<sh.F, sh.D, true>(pl, p, n_iters, sw, training != 0)
+                                                 : choose_route<sh.F, sh.D, false>(pl, p, n_iters, sw, training != 0); });
     if (!r.supported)
         return fail(GNN_ERR_UNSUPPORTED, "no fused training forward for input_dim=%d hidden_dim=%d", p->F, p->D);
     const int64_t f[GNN_ROUTE_FIELDS] = {r.rec, r.input, r.family, r.fuse_first, r.edge, r.pack, r.it_lds, r.it2_lds,
@@ -3689,18 +3736,40 @@ int sell_route(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, int tra
     return 0;
 }
 
-int sell_forward_train(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, const int32_t *seg_ptr,
-                       const int32_t *tw_src, const int32_t *tw_dst, float *e_all, float *H_all, float *Q_all, int ldh,
-                       float *e_out, void *ws, size_t ws_bytes, hipStream_t s)
+int gnn_segclf_forward_plan(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters,
+                            float *e_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return forward_any<true>(pl, p, n_iters, TrainArgs{seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh}, e_out, ws,
-                             ws_bytes, s);
+    if (int rc = check_plan("gnn_segclf_forward_plan", pl, p, n_iters, false, e_out)) return rc;
+    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_plan: weight pointer missing");
+    return forward_any<false>(pl, p, n_iters, TrainArgs{}, e_out, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
 }
 
-int sell_forward(const gnn_plan_t *pl, const gnn_params_t *p, int n_iters, float *e_out, void *ws,
-                 size_t ws_bytes, hipStream_t s)
+int gnn_segclf_forward_train_plan(const gnn_plan_t *pl, const gnn_params_t *p, int32_t n_iters,
+                                  const int32_t *seg_ptr, const int32_t *tw_src, const int32_t *tw_dst, float *e_all,
+                                  float *H_all, float *Q_all, float *e_out, void *workspace, size_t workspace_bytes,
+                                  void *stream)
 {
-    return forward_any<false>(pl, p, n_iters, TrainArgs{}, e_out, ws, ws_bytes, s);
+    if (int rc = check_plan("gnn_segclf_forward_train_plan", pl, p, n_iters, true, e_all)) return rc;
+    if (pl->n_segments > 0 && ((!tw_src != !tw_dst) || (!e_out && !tw_src)))
+        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: e_out or the (tw_src, tw_dst) pair is needed");
+    if (pl->n_pad > 0 && (!seg_ptr || !H_all || (n_iters > 0 && !Q_all)))
+        return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: output array missing");
+    if (!params_complete(p)) return fail(GNN_ERR_BADARG, "gnn_segclf_forward_train_plan: weight pointer missing");
+    const int ldh = gnn_h_stride(p->F, p->D);
+    if (ldh <= 0) return fail(GNN_ERR_UNSUPPORTED, "no HIP kernel for input_dim=%d hidden_dim=%d", p->F, p->D);
+    return forward_any<true>(pl, p, n_iters, TrainArgs{seg_ptr, tw_src, tw_dst, e_all, H_all, Q_all, ldh}, e_out, workspace,
+                             workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
-}  // namespace gnn
+int gnn_exp_product_bound(const gnn_params_t *p, const float *x_absmax, float *bound_out,
+                          void *stream)
+{
+    if (!p || !p->W1 || !p->b1 || !x_absmax || !bound_out || p->F <= 0 || p->D <= 0)
+        return fail(GNN_ERR_BADARG, "gnn_exp_product_bound: bad argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    GNN_LAUNCH("k_exp_bound", k_exp_bound, 1, 64, s, p->W1, p->b1, x_absmax, p->F, p->D, bound_out);
+    return 0;
+}
+
+}  // extern "C"

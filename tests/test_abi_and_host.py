@@ -332,7 +332,7 @@ def test_plan_route_is_pinned(monkeypatch):
     bf16 = ("bf16", "k_input4_bf", "k_iter_w", False, "k_edge_w", True)
     bf16_wx = ("bf16", "k_input4_bf", "k_iter_wx", False, "k_edge_w", True)
     general_wide = ("fp32", "k_input4", "k_iter", False, "k_edge_w", True)     # big table: k_pack; wide rows: k_edge_w
-    # every shape of SELL_FOR_EACH_SHAPE: 3 iterations, exp-product on, every tile in LDS mode, 1024 padded hits
+    # every shape of PlanShapes: 3 iterations, exp-product on, every tile in LDS mode, 1024 padded hits
     default = {(2, 4): fused, (2, 8): iter2, (2, 16): exact16, (2, 32): exact, (3, 4): fused, (3, 8): fused,
                (3, 16): exact16, (3, 32): exact, (3, 64): exact, (11, 4): iter2, (11, 8): iter2, (11, 16): general}
     trains = {(2, 4), (2, 8), (3, 4), (3, 8), (11, 4), (11, 8), (11, 16)}     # D <= 16 without the wide route
@@ -464,8 +464,8 @@ def test_backward_workspace_bytes_are_pinned():
         (11, 16): ([97024, 98816, 1399040, 61194496], [21760, 21760, 11354368]),
     }
     with open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "common.h")) as f:         # the list the backward dispatches over
-        listed = re.search(r"#define GNN_FOR_EACH_SHAPE\(X_\)((?:.*\\\n)*.*)\n", f.read()).group(1)
-    assert sorted(recorded) == sorted((int(a), int(b)) for a, b in re.findall(r"X_\((\d+), (\d+)\)", listed))
+        listed = re.search(r"using ModelShapes = ShapeList<(.*?)>;", f.read(), flags=re.S).group(1)
+    assert sorted(recorded) == sorted((int(a), int(b)) for a, b in re.findall(r"Shape<(\d+), (\d+)>", listed))
     lib = _lib.load()
     for (F, D), (want, want_events) in recorded.items():
         got = [lib.gnn_backward_workspace_bytes(n, e, F, D) for n, e in ((0, 0), (1, 0), (909, 6011), (40000, 300000))]

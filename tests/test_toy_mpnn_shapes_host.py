@@ -19,14 +19,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_matrix_is_every_shape_the_library_builds():
-    """A shape added to ITER_SHAPES and not to MATRIX (or the reverse) fails here: no built shape goes unrun."""
+    """A shape added to IterShapes and not to MATRIX (or the reverse) fails here: no built shape goes unrun."""
     built = {(F, D) for F in range(1, 17) for D in range(1, 65) if _lib.iter_events_supported(F, D, 1, 1, False)}
     assert len(MATRIX) == len(set(MATRIX)) == 14
     assert built == set(MATRIX), "built and not in MATRIX: %s; in MATRIX and not built: %s" % (
         sorted(built - set(MATRIX)), sorted(set(MATRIX) - built))
     src = open(os.path.join(REPO, "gnn-fpga_amd", "csrc", "iter_events.hip")).read()
-    macro = re.search(r"#define ITER_SHAPES\(X_\)(.*?)\n\n", src, flags=re.S).group(1)
-    assert [(int(a), int(b)) for a, b in re.findall(r"X_\((\d+), (\d+)\)", macro)] == MATRIX
+    listed = re.search(r"using IterShapes = ShapeList<(.*?)>;", src, flags=re.S).group(1)
+    assert [(int(a), int(b)) for a, b in re.findall(r"Shape<(\d+), (\d+)>", listed)] == MATRIX
     # both matrix batches take the one-launch route, forward and backward, at every shape
     assert MATRIX_CAPS == (40, 144)
     for F, D in MATRIX:

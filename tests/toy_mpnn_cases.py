@@ -108,7 +108,7 @@ def check_graphs(hip, graphs, F, D, T, want_infer, want_train, shared=False, see
 
 
 # ---- the shape matrix --------------------------------------------------------------------------------------------------
-# Every (input_dim, hidden_dim) of ITER_SHAPES in csrc/iter_events.hip; test_toy_mpnn_shapes_host.py derives the same set
+# Every (input_dim, hidden_dim) of IterShapes in csrc/iter_events.hip; test_toy_mpnn_shapes_host.py derives the same set
 # from the library and fails when the two differ.
 MATRIX = [(2, 4), (2, 8), (2, 16), (2, 32), (3, 4), (3, 8), (3, 16), (3, 32), (4, 8), (4, 16), (4, 32), (11, 4), (11, 8),
           (11, 16)]
