@@ -1,4 +1,5 @@
-"""ctypes binding of libgnn_hip.so (C ABI in include/gnn_hip.h).
+"""ctypes binding of libgnn_hip.so (C ABI in include/*.h; _abi.py reads the signatures, struct layouts and constants
+from those headers, this module holds the calls).
 
 This is the only compute path of the package: there is no CPU or eager-PyTorch
 fallback.  If the library is missing or a tensor is not on a ROCm device the call
@@ -14,293 +15,16 @@ import torch  # imported first: its bundled libamdhip64.so.7 is the one HIP runt
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgnn_hip.so")
 
-GNN_ABI_VERSION = 7
-GNN_ERR_UNSUPPORTED = -10001
-GNN_ERR_BADARG = -10002
-GNN_ERR_WORKSPACE = -10003
-GNN_FLAG_EXP_PRODUCT = 1
-GNN_FLAG_BF16_MLP = 2
+from . import _abi
+from ._abi import *  # noqa: F401,F403 - the signature tables, the struct classes, the headers' constants, GnnHipError
 
-_f = ctypes.c_void_p          # device pointers travel as integers
-_i32, _i64, _sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
+GNN_ABI_VERSION = 7           # the ABI the call sequences below are written for: the one constant not taken from the headers
+GNN_FX_ROUNDING = {"trn": GNN_FX_TRN, "rnd": GNN_FX_RND}
+GNN_FX_OVERFLOW = {"wrap": GNN_FX_WRAP, "sat": GNN_FX_SAT}
 
-
-class GnnParams(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("Win", "bin", "W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4")] + \
-               [("F", _i32), ("D", _i32), ("flags", _i32)]
-
-
-class GnnGraph(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("X", "src", "dst", "in_ptr", "in_eid", "in_nbr",
-                                  "out_ptr", "out_eid", "out_nbr")] + \
-               [("n_hits", _i64), ("n_segments", _i64)]
-
-
-class GnnGrads(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("Win", "bin", "W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4")]
-
-
-class GnnPlan(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("X", "src", "dst", "in_off", "in_nbr", "out_off", "out_nbr",
-                                  "tiles", "chunks", "in_off16", "in_nbr16", "out_off16",
-                                  "out_nbr16", "sched_a", "sched_b", "sd16")] + \
-               [("n_pad", _i64), ("n_segments", _i64), ("n_tiles", _i64), ("n_chunks", _i64),
-                ("iter_lds_records", _i64), ("edge_lds_rows", _i64), ("n_lds_tiles", _i64),
-                ("iter_lds_in", _i64), ("iter_lds_out", _i64), ("tile_hits_max", _i64),
-                ("max_list_steps", _i64)]
-
-
-class GnnPlanSizes(ctypes.Structure):
-    _fields_ = [(n, _i64) for n in ("n_pad", "n_tiles", "n_slices", "n_chunks", "in_total", "out_total",
-                                    "in16_words", "out16_words", "n_sched", "iter_lds_records",
-                                    "edge_lds_rows", "n_lds_tiles", "n_lds_chunks", "iter_lds_in",
-                                    "iter_lds_out", "tile_hits_max", "max_list_steps", "n_valid",
-                                    "max_level", "status", "list_mode")]
-
-
-class GnnPlanOut(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("X", "x_absmax", "src", "dst", "sd16", "in_off", "in_nbr", "out_off",
-                                  "out_nbr", "in_off16", "in_nbr16", "out_off16", "out_nbr16", "tiles",
-                                  "chunks", "sched_a", "sched_b", "perm", "src_abs", "dst_abs", "level")]
-
-
-class GnnGraphBuildSizes(ctypes.Structure):
-    _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "n_rows", "n_tasks", "max_graph_hits",
-                                    "max_graph_segments", "status")]
-
-
-class GnnHitSamplesSizes(ctypes.Structure):
-    _fields_ = [(n, _i64) for n in ("n_samples", "n_hits", "n_segments", "n_kept", "n_groups", "n_tasks", "status")]
-
-
-class GnnEventGraphsSizes(ctypes.Structure):
-    _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "n_kept", "n_tasks", "n_tested", "status")]
-
-
-class GnnSelectHitsSizes(ctypes.Structure):
-    _fields_ = [(n, _i64) for n in ("n_kept", "status")]
-
-
-class GnnEmtfHits(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("z", "theta", "phi", "r", "bend", "tp1", "tp2", "station", "ring", "type",
-                                  "event_ptr")] + [("n_rows", _i64)]
-
-
-class GnnMuonGraphSizes(ctypes.Structure):
-    _fields_ = [(n, _i64) for n in ("n_graphs", "n_hits", "n_segments", "max_graph_hits", "max_graph_segments",
-                                    "status")]
-
-
-class GnnMuonGraphOut(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("X", "src", "dst", "y", "hit_source", "hit_row", "entry", "pt", "eta", "flags",
-                                  "graph_hits", "graph_segments")]
-
-
-GNN_GCN_MAX_LAYERS = 16
-
-
-class GnnGcnAdj(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("row_cnt", "row_idx", "row_val", "col_cnt", "col_idx", "col_val")] + \
-               [("B", _i64), ("N", _i32), ("W", _i32)]
-
-
-class GnnGcnNet(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("Wf", "bf", "Wc", "bc")] + \
-               [(n, _f * GNN_GCN_MAX_LAYERS) for n in ("Wn", "bn", "Wg")] + \
-               [("dims", _i32 * (GNN_GCN_MAX_LAYERS + 1))] + \
-               [(n, _i32 * GNN_GCN_MAX_LAYERS) for n in ("off_n", "off_b", "off_g")] + \
-               [(n, _i32) for n in ("off_f", "off_bf", "off_c", "off_bc", "n_params", "n_dims", "F", "residual",
-                                    "max_width")]
-
-
-# name -> (restype, argtypes); must list every function include/gnn_hip.h declares
-SIGNATURES = {
-    "gnn_abi_version": (ctypes.c_int, []),
-    "gnn_last_error": (ctypes.c_char_p, []),
-    "gnn_shape_supported": (ctypes.c_int, [_i32, _i32]),
-    "gnn_h_stride": (_i32, [_i32, _i32]),
-    "gnn_input_fwd": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i32, _i32, _i32, _f]),
-    "gnn_edge_fwd": (ctypes.c_int, [_f, _i32, _f, _f, _f, _f, _f, _f, _f, _f, _i64, _i64,
-                                    _i32, _i32, _f]),
-    "gnn_node_fwd": (ctypes.c_int, [_f, _i32, _f, ctypes.POINTER(GnnGraph), _f, _f, _f, _f, _f,
-                                    _i32, _i32, _f]),
-    "gnn_forward_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "gnn_segclf_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams),
-                                          _i32, _f, _f, _f, _f, _sz, _f]),
-    "gnn_events_supported": (ctypes.c_int, [_i32, _i32, _i64, _i64]),
-    "gnn_segclf_forward_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams),
-                                                 _f, _f, _i64, _i32, _i32, _i32, _f, _f]),
-    "gnn_segclf_forward_train_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams),
-                                                       _f, _f, _i64, _i32, _i32, _i32, _f, _f, _f]),
-    "gnn_events_backward_supported": (ctypes.c_int, [_i32, _i32, _i64, _i64]),
-    "gnn_backward_events_workspace_bytes": (_sz, [_i64, _i32, _i32]),
-    "gnn_segclf_backward_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams),
-                                                  _f, _f, _i64, _i32, _i32, _i32, _f, _f, _f,
-                                                  ctypes.POINTER(GnnGrads), _f, _sz, _f]),
-    "gnn_segclf_forward_train": (ctypes.c_int, [ctypes.POINTER(GnnGraph),
-                                                ctypes.POINTER(GnnParams), _i32, _f, _f, _f, _f, _sz, _f]),
-    "gnn_backward_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "gnn_segclf_backward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams),
-                                           _i32, _f, _f, _f, _f, ctypes.POINTER(GnnGrads), _f, _sz, _f]),
-    "gnn_nodeclf_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _i32, _f, _f,
-                                           _f, _sz, _f]),
-    "gnn_nodeclf_forward_train": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _i32, _f,
-                                                 _f, _f, _f, _f, _sz, _f]),
-    "gnn_nodeclf_backward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _i32, _f, _f,
-                                            _f, _f, _f, ctypes.POINTER(GnnGrads), _f, _f, _f, _sz, _f]),
-    "gnn_bce_loss": (ctypes.c_int, [_f, _f, _i64, ctypes.c_float, _f, _f, _f, _f]),
-    "gnn_dense_to_index": (ctypes.c_int, [_f, _f, _i64, _i64, _i64, _f, _f, _f, _f]),
-    "gnn_edge_bwd": (ctypes.c_int, [_f, _i32, ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f, _f,
-                                    ctypes.POINTER(GnnGrads), _f, _sz, _f]),
-    "gnn_node_bwd": (ctypes.c_int, [_f, _i32, _f, _f, ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnParams), _f, _f,
-                                    _f, ctypes.POINTER(GnnGrads), _f, _sz, _f]),
-    "gnn_plan_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "gnn_segclf_forward_plan": (ctypes.c_int, [ctypes.POINTER(GnnPlan), ctypes.POINTER(GnnParams),
-                                               _i32, _f, _f, _sz, _f]),
-    "gnn_segclf_forward_train_plan": (ctypes.c_int, [ctypes.POINTER(GnnPlan), ctypes.POINTER(GnnParams), _i32, _f, _f, _f,
-                                                     _f, _f, _f, _f, _f, _sz, _f]),
-    "gnn_plan_shape_supported": (ctypes.c_int, [_i32, _i32]),
-    "gnn_plan_limits": (ctypes.c_int, [_i32, _i32, ctypes.POINTER(_i32)]),
-    "gnn_plan_route": (ctypes.c_int, [ctypes.POINTER(GnnPlan), ctypes.POINTER(GnnParams), _i32, _i32,
-                                      ctypes.POINTER(_i32)]),
-    "gnn_exp_product_bound": (ctypes.c_int, [ctypes.POINTER(GnnParams), _f, _f, _f]),
-    "gnn_csr_build_workspace_bytes": (_sz, [_i64, _i64]),
-    "gnn_csr_build": (ctypes.c_int, [_f, _f, _i64, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _sz, _f]),
-    "gnn_plan_build_workspace_bytes": (_sz, [_i64, _i64, _i32]),
-    "gnn_plan_build_sizes": (ctypes.c_int, [_f, _f, _f, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f, _sz,
-                                            _f, _f]),
-    "gnn_plan_build_sizes_graphs": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
-                                                   _f, _sz, _f, _f]),
-    "gnn_plan_build_fill": (ctypes.c_int, [_f, _i32, _f, _f, _i64, _i64, _i32, ctypes.POINTER(GnnPlanSizes),
-                                           _f, _sz, ctypes.POINTER(GnnPlanOut), _f]),
-    "gnn_graph_build_workspace_bytes": (_sz, [_i64, _i64, _f, _i32, _i32, _i32]),
-    "gnn_graph_build_sizes": (ctypes.c_int, [_f, _f, _f, _f, _i64, _f, _i64, _f, _i32, _i32, _i32, ctypes.c_float,
-                                             ctypes.c_float, ctypes.c_float, _f, _sz, _f, _f, _f, _f]),
-    "gnn_graph_build_fill": (ctypes.c_int, [_f, _i64, _i64, _f, _i32, _i32, _i32, ctypes.c_float, ctypes.c_float,
-                                            ctypes.c_float, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                            ctypes.POINTER(GnnGraphBuildSizes), _f, _sz, _f, _f, _f, _f, _f, _f]),
-    "gnn_hit_samples_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "gnn_hit_samples_sizes": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _f, _i64, _i32, _i32, _f, _sz, _f, _f]),
-    "gnn_hit_samples_fill": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, _i32, _i32, _i32, ctypes.c_double,
-                                            ctypes.c_double, ctypes.c_double, ctypes.POINTER(GnnHitSamplesSizes), _f,
-                                            _sz, _f, _f, _f, _f, _f, _f, _f]),
-    "gnn_muon_graph_workspace_bytes": (_sz, [_i64]),
-    "gnn_muon_graph_sizes": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f,
-                                            _sz, _f, _f, _f, _f]),
-    "gnn_muon_graph_fill": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f, _f,
-                                           _i64, _i64, ctypes.POINTER(GnnMuonGraphSizes), _f, _sz,
-                                           ctypes.POINTER(GnnMuonGraphOut), _f]),
-    "gnn_muon_graph_padded": (ctypes.c_int, [ctypes.POINTER(GnnEmtfHits), ctypes.POINTER(GnnEmtfHits), _i64, _i32, _f,
-                                             _f, _i64, _i64, _f, _sz, ctypes.POINTER(GnnMuonGraphOut), _f, _f]),
-    "gnn_event_graphs_workspace_bytes": (_sz, [_i64, _i64]),
-    "gnn_event_graphs_sizes": (ctypes.c_int, [_f, _f, _f, _f, _f, _f, _i64, _f, _i64, ctypes.c_float, ctypes.c_float,
-                                              _i64, _i64, _i64, _f, _sz, _f, _f, _f, _f, _f]),
-    "gnn_event_graphs_fill": (ctypes.c_int, [_f, _f, _f, _f, _i64, _i64, ctypes.c_float, ctypes.c_float,
-                                             ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                             ctypes.POINTER(GnnEventGraphsSizes), _f, _sz, _f, _f, _f, _f, _f, _f, _f]),
-    "gnn_select_hits_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
-    "gnn_select_hits_sizes": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _f, _f, _f, _i64, _f, _f, _f, _f, _i64, _f, _i64,
-                                             _f, _i32, ctypes.c_float, _i32, _f, _sz, _f, _f, _f]),
-    "gnn_select_hits_fill": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _i64, _i64, _i64, _i32,
-                                            ctypes.POINTER(GnnSelectHitsSizes), _f, _sz, _f, _f, _f, _f, _f, _f, _f, _f]),
-    "gnn_metrics_bins": (_i64, [_i32]),
-    "gnn_metrics_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
-    "gnn_segment_metrics_update": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i32, _i32, _f, _f, _f, _i64, _f, _f, _f, _sz,
-                                                  _f]),
-    "gnn_track_build_workspace_bytes": (_sz, [_i64, _i64]),
-    "gnn_track_build_labels": (ctypes.c_int, [_f, _f, _f, _i64, _i64, _f, _i64, ctypes.c_float, _i32, _i32, _f, _sz, _f,
-                                              _f, _f, _f]),
-    "gnn_track_build_lists": (ctypes.c_int, [_f, _i64, _f, _i64, _i64, _i64, _f, _sz, _f, _f, _f, _f, _f]),
-    "gnn_track_match_workspace_bytes": (_sz, [_i64, _i64]),
-    "gnn_track_match": (ctypes.c_int, [_f, _f, _i64, _f, _i64, _f, _i64, _i32, _f, _sz, _f, _f, _f, _f, _f, _f]),
-    "gnn_track_fit": (ctypes.c_int, [_f, _f, _i64, _i64, _f, _f, _f, _i64, _i32, _f, _f, _f, _f, _f]),
-    "gnn_gcn_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32]),
-    "gnn_gcn_compress_count": (ctypes.c_int, [_f, _i64, _i32, _f, _f, _f, _f]),
-    "gnn_gcn_compress_fill": (ctypes.c_int, [_f, _i64, _i32, _i32, _f, _f, _f, _f, _f]),
-    "gnn_gcn_forward": (ctypes.c_int, [ctypes.POINTER(GnnGcnAdj), ctypes.POINTER(GnnGcnNet), _f, _f, _f, _f]),
-    "gnn_gcn_backward_workspace_bytes": (_sz, [_i64, _i32]),
-    "gnn_gcn_backward": (ctypes.c_int, [ctypes.POINTER(GnnGcnAdj), ctypes.POINTER(GnnGcnNet), _f, _f, _f, _f, _f, _sz,
-                                        _f]),
-    "gnn_toy_graphs_list_width": (_i32, [_i32, _i32, _i32, _i32]),
-    "gnn_toy_segment_graphs": (ctypes.c_int, [_f, _f, _f, _i64, _i32, _i32, ctypes.c_float, _f, _f, _f, _f, _f, _f]),
-    "gnn_toy_hit_graphs": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _i32, _i32, _i32, _i32, _i32, _f, _f, _f, _f, _f, _f,
-                                          _f, _f, _f, _f]),
-    "gnn_cut_study_workspace_bytes": (_sz, [_i64, _i64, _f, _i32, _i32, _i32, _i32, _i32]),
-    "gnn_cut_study": (ctypes.c_int, [_f, _f, _f, _f, _f, _i64, _f, _i64, _f, _i32, _i32, _i32, _f, _i32, _f, _i32, _f, _sz,
-                                     _f, _f, _f]),
-    "gnn_layer_census_workspace_bytes": (_sz, [_i64, _i64, _i32]),
-    "gnn_layer_census": (ctypes.c_int, [_f, _f, _f, _i64, _f, _i64, _i32, _i32, _i64, _f, _sz, _f, _f, _f]),
-    "gnn_profile_begin": (ctypes.c_int, [_i32]),
-    "gnn_profile_end": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p),
-                                       ctypes.POINTER(ctypes.c_float), _i32]),
-}
-
-GNN_ITER_MAX = 16           # include/gnn_hip_iter.h
-
-
-class GnnIterSet(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("Wa", "ba", "Wb", "bb")]
-
-
-class GnnIterParams(ctypes.Structure):
-    _fields_ = [("Win", _f), ("bin", _f), ("edge", GnnIterSet * GNN_ITER_MAX), ("node", GnnIterSet * GNN_ITER_MAX),
-                ("out", GnnIterSet)] + [(n, _i32) for n in ("F", "D", "n_iters", "shared")]
-
-
-# name -> (restype, argtypes); must list every function include/gnn_hip_iter.h declares
-ITER_SIGNATURES = {
-    "gnn_iter_events_supported": (ctypes.c_int, [_i32, _i32, _i64, _i64, _i32]),
-    "gnn_iter_forward_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnIterParams), _f, _f, _i64,
-                                               _i32, _i32, _f, _f, _f, _f]),
-    "gnn_iter_grad_floats": (_i64, [_i32, _i32, _i32, _i32]),
-    "gnn_iter_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32]),
-    "gnn_iter_backward_events": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnIterParams), _f, _f, _i64,
-                                                _i32, _i32, _f, _f, _f, _f, _f, _sz, _f]),
-    "gnn_iter_input_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
-    "gnn_iter_input_bwd": (ctypes.c_int, [_f, _f, _i32, _f, _i32, _i64, _i32, _i32, _f, _f, _sz, _f]),
-}
-
-GNN_FX_ROUNDING = {"trn": 0, "rnd": 1}        # include/gnn_hip_fixed.h GNN_FX_TRN / GNN_FX_RND
-GNN_FX_OVERFLOW = {"wrap": 0, "sat": 1}       # GNN_FX_WRAP / GNN_FX_SAT
-GNN_FX_STAGES = 6
-
-
-class GnnFxFormat(ctypes.Structure):
-    _fields_ = [(n, _i32) for n in ("total_bits", "int_bits", "rounding", "overflow", "table_bits")]
-
-
-class GnnFxParams(ctypes.Structure):
-    _fields_ = [(n, _f) for n in ("Win", "bin", "W1", "b1", "W2", "b2", "W3", "b3", "W4", "b4")] + \
-               [("F", _i32), ("D", _i32)]
-
-
-class GnnFxTables(ctypes.Structure):
-    _fields_ = [("tanh_table", _f), ("sigmoid_table", _f)]
-
-
-# name -> (restype, argtypes); must list every function include/gnn_hip_fixed.h declares
-FX_SIGNATURES = {
-    "gnn_fx_supported": (ctypes.c_int, [_i32, _i32, _i32, _i32, _i32]),
-    "gnn_fx_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "gnn_fx_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnFxParams),
-                                      ctypes.POINTER(GnnFxFormat), ctypes.POINTER(GnnFxTables), _i32, _f, _f, _f, _f, _f,
-                                      _f, _sz, _f]),
-}
-
-# name -> (restype, argtypes); must list every function include/gnn_hip_fixed_events.h declares
-FXEV_SIGNATURES = {
-    "gnn_fxev_lds_bytes": (_sz, [_i32, _i32, _i32, _i64, _i64]),
-    "gnn_fxev_supported": (ctypes.c_int, [_i32, _i32, _i32, _i64, _i64]),
-    "gnn_fxev_forward": (ctypes.c_int, [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnFxParams),
-                                        ctypes.POINTER(GnnFxFormat), ctypes.POINTER(GnnFxTables), _f, _f, _i64, _i32, _i32,
-                                        _i32, _f, _f, _f, _f, _f, _f, _f]),
-}
+_f, _i32 = ctypes.c_void_p, ctypes.c_int32          # a device pointer, as the struct fields hold it; a host int32
 
 _lib = None
-
-
-class GnnHipError(RuntimeError):
-    pass
 
 
 def load():
@@ -308,6 +32,9 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
+    if _abi.GNN_ABI_VERSION != GNN_ABI_VERSION:
+        raise GnnHipError("the headers declare ABI %d but the binding's calls are written for ABI %d"
+                          % (_abi.GNN_ABI_VERSION, GNN_ABI_VERSION))
     if not os.path.exists(LIB_PATH):
         raise GnnHipError(
             "HIP library %s is missing - build it with `python -c 'import __graft_entry__ as g; "
@@ -896,6 +623,10 @@ ROUTE_NAMES = {"records": ("fp32", "bf16", "exact"),
                "input": (None, "k_input4", "k_input4_bf", "k_input4_x"),
                "family": ("k_iter", "k_iter2", "k_iter_w", "k_iter_wx"),
                "edge": ("k_edge", "k_edge_w")}
+_ROUTE_ENUMS = {"records": "GNN_REC_", "input": "GNN_INPUT_", "family": "GNN_FAMILY_", "edge": "GNN_EDGE_"}
+if len(ROUTE_FIELDS) != GNN_ROUTE_FIELDS or any(len(ROUTE_NAMES[k]) != sum(n.startswith(prefix) for n in _abi.__all__)
+                                                for k, prefix in _ROUTE_ENUMS.items()):
+    raise GnnHipError("ROUTE_FIELDS / ROUTE_NAMES do not name what the GNN_ROUTE_* enums of include/gnn_hip.h hold")
 
 
 def plan_route(plan, F, D, n_iters, flags=0, training=False):
@@ -1143,7 +874,7 @@ def event_graphs_fill(ws, sizes, r, phi, z, barcode, n_events, cuts, feature_sca
     return X, src, dst, y, hit_index, layer
 
 
-SELECT_HITS_MAX_LAYERS = 64      # include/gnn_hip.h GNN_SELECT_HITS_MAX_LAYERS
+SELECT_HITS_MAX_LAYERS = GNN_SELECT_HITS_MAX_LAYERS
 
 
 def select_hits_sizes(hits, truth, particles, event_ptrs, barrel_layers, pt_min, no_missing_hits):
@@ -1323,7 +1054,7 @@ def segment_metrics_update(e, y, src, thresholds, key_shift, counts, hist, statu
 
 
 # ---- track candidates and their matching (csrc/track_build.hip) ---------------------------------------------------------
-TRACKS_MODES = {"components": 0, "best": 1}      # include/gnn_hip.h GNN_TRACKS_COMPONENTS / GNN_TRACKS_BEST
+TRACKS_MODES = {"components": GNN_TRACKS_COMPONENTS, "best": GNN_TRACKS_BEST}
 
 
 def track_build_labels(src, dst, scores, n_hits, hit_ptr, threshold, mode, min_hits):
@@ -1542,8 +1273,7 @@ def gcn_backward(adj, net, x, H_all, grad_out):
     return grads
 
 
-GNN_TOY_SEGMENTS, GNN_TOY_HITS = 0, 1
-GNN_TOY_NORMS = {None: 0, "row": 1, "kw": 2}
+GNN_TOY_NORMS = {None: GNN_TOY_NORM_NONE, "row": GNN_TOY_NORM_ROW, "kw": GNN_TOY_NORM_KW}
 
 
 def toy_list_width(kind, L, T, norm=None):

@@ -44,10 +44,10 @@ very many hits of an event is one lane's serial walk.
 import numpy as np
 import torch
 
+from ._abi import GNN_SELECT_HITS_MAX_LAYERS as MAX_LAYERS
 from .graph_build import _check_on_device, _host, _raise_builder_status, build_graphs
 
 BARREL_VLIDS = ((8, 2), (8, 4), (8, 6), (8, 8), (13, 2), (13, 4), (13, 6), (13, 8), (17, 2), (17, 4))   # :55-57
-MAX_LAYERS = 64                   # include/gnn_hip.h GNN_SELECT_HITS_MAX_LAYERS
 SH_STATUS_EVENTS = 4              # csrc/select_hits.hip: an event_ptr not 0 .. its table's rows, non-decreasing
 SH_STATUS_FINITE = 8              # a non-finite x or y
 SH_STATUS_DUPLICATE = 16          # an id twice in one event's table
