@@ -148,6 +148,12 @@ def cases():
     r = ev.r.copy()
     r[(ev.layer == 0) | (ev.layer == 1)] = np.float32(32.0)
     yield "inf_edge", ev._replace(r=r), adjacent_pairs(), [1e-3, 1e-2, inf], [200.0, inf], False
+    # 7. edges ON values of the data, each with its upper neighbour: one-ulp bins (tests/pair_value_cases.py chooses
+    # the values where a reciprocal-multiply differs from the division)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import pair_value_cases
+    se, ze = pair_value_cases.fixture_edges()
+    yield "pair_values", pair_value_cases.probe_event("one").cols, adjacent_pairs(), se, ze, False
 
 
 def main():

@@ -121,6 +121,12 @@ def cases():
     # 7. a separate outer cut (pairs starting at layer >= 5 take phi_slope_outer_max)
     ev = synth.barrel_event(150, 100, seed=8)
     yield "outer_cut", ev, adjacent_pairs(), 4, 0.0006, 0.002, 150.0
+    # 8. all three cuts ON values of the data (tests/pair_value_cases.py chooses them where a reciprocal-multiply
+    # differs from the division): the pair at each cut is not kept, and would be one ulp further up
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import pair_value_cases
+    psm, pso, z0m = pair_value_cases.fixture_cuts()
+    yield "pair_values", pair_value_cases.probe_event("one").cols, adjacent_pairs(), 1, psm, pso, z0m
 
 
 def write_npz(path, arrays):
