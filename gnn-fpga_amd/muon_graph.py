@@ -361,7 +361,7 @@ def build_muon_graphs_numpy(muon, pu, vp_pt, vp_eta, entry_start, muon_only):
             dphi = wrap_dphi32(phi[j] - phi[i])
             dz = z[j] - z[i]
             dr = r[j] - r[i]
-            with np.errstate(divide="ignore", invalid="ignore"):
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
                 slope = dphi / dr
                 z0 = z[i] - r[i] * dz / dr
             assert slope.dtype == z0.dtype == np.float32

@@ -29,6 +29,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 OUT = os.path.join(REPO, "tests", "golden", "muon_graph")
 
 from gnn_fpga_amd import synth  # noqa: E402
@@ -190,6 +191,23 @@ def cases():
     yield "no_file", _concat(d, synth.emtf_events(4, seed=9)), 0, False
     # 10. trap 10: --muononly
     yield "muononly", synth.emtf_events(10, seed=10), 0, True
+    # 11, 12. the builder's bounds (tests/muon_bound_cases.py): graphs of 42 hits with 6 on a signed layer, 140
+    # segments and all 25 layer values, PU rows first and muon rows first; 60 of the set-order entries
+    import muon_bound_cases as mb
+    by = {c.name: c for c in mb.batch()}
+    full = [c.name for c in mb.batch() if c.group in ("full", "neighbours")]
+    yield "bounds_full", _bound_entries([by[n] for n in full]), 0, False
+    orders = [c for c in mb.batch() if c.group == "explicit" and not c.mu_first]
+    seeded = [c for c in mb.batch() if c.group == "orders" and not c.mu_first]
+    orders += seeded[::mb.ORDERS_PER_N] + seeded[mb.ORDERS_PER_N * 10 + 1::mb.ORDERS_PER_N]
+    assert len(orders) == 60
+    yield "bounds_set_order", _bound_entries(orders), 0, False
+
+
+def _bound_entries(cases):
+    mu, pu, vp_pt, vp_eta = __import__("muon_bound_cases").columns([c.rows for c in cases])
+    return {"muon": mu, "pu": pu, "vp_pt": vp_pt, "vp_eta": vp_eta,
+            "vp_ptr": np.arange(len(cases) + 1, dtype=np.int64)}
 
 
 def _concat(a, b):
