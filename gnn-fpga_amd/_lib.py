@@ -738,28 +738,21 @@ def plan_build_workspace_bytes(n_hits, n_segments, chunk_segments):
     return int(load().gnn_plan_build_workspace_bytes(n_hits, n_segments, chunk_segments))
 
 
-PLAN_GRAPH_CAP_HITS = 19456      # csrc/plan_build.hip kGraphCapHits: LDS tables and sort keys of the graph-local stage 1
-PLAN_STATUS_FAST_MISS = 128
-
-
 def plan_build_sizes(src, dst, hit_ptr, n_hits, n_segments, n_graphs, tile_hits, iter_records,
                      chunk_segments, edge_records, workspace, seg_ptr=None, max_graph_hits=0, max_graph_segments=0):
     """Stage 1 of the GPU plan builder (csrc/plan_build.hip).  Returns a GnnPlanSizes read back from
     the device - the ONE host synchronisation of a plan build.  With `seg_ptr` (device int64 [G+1]) the
-    graph-local form runs (gnn_plan_build_sizes_graphs); status bit PLAN_STATUS_FAST_MISS = call again without."""
+    graph-local form runs (gnn_plan_build_sizes_graphs); status bit GNN_PLAN_ST_FAST_MISS = call again without."""
     sizes = torch.zeros(ctypes.sizeof(GnnPlanSizes) // 8, dtype=torch.int64, device=src.device)
     with _on(src) as st:
+        ptrs = (_dev(src, torch.int32, "src"), _dev(dst, torch.int32, "dst"), _dev(hit_ptr, torch.int64, "hit_ptr"))
+        rest = (n_hits, n_segments, n_graphs, tile_hits, iter_records, chunk_segments, edge_records,
+                workspace.data_ptr(), workspace.numel(), sizes.data_ptr(), st)
         if seg_ptr is not None:
-            _check(load().gnn_plan_build_sizes_graphs(
-                _dev(src, torch.int32, "src"), _dev(dst, torch.int32, "dst"), _dev(hit_ptr, torch.int64, "hit_ptr"),
-                _dev(seg_ptr, torch.int64, "seg_ptr"), int(max_graph_hits), int(max_graph_segments),
-                n_hits, n_segments, n_graphs, tile_hits, iter_records, chunk_segments, edge_records,
-                workspace.data_ptr(), workspace.numel(), sizes.data_ptr(), st))
+            _check(load().gnn_plan_build_sizes_graphs(*ptrs, _dev(seg_ptr, torch.int64, "seg_ptr"), int(max_graph_hits),
+                                                      int(max_graph_segments), *rest))
         else:
-            _check(load().gnn_plan_build_sizes(
-                _dev(src, torch.int32, "src"), _dev(dst, torch.int32, "dst"), _dev(hit_ptr, torch.int64, "hit_ptr"),
-                n_hits, n_segments, n_graphs, tile_hits, iter_records, chunk_segments, edge_records,
-                workspace.data_ptr(), workspace.numel(), sizes.data_ptr(), st))
+            _check(load().gnn_plan_build_sizes(*ptrs, *rest))
     return _read_back(GnnPlanSizes, sizes)[0]
 
 

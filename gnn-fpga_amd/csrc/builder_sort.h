@@ -7,13 +7,6 @@
 
 namespace gnn {
 
-inline int bits_for(u64 v)                             // bits to hold 0 .. v
-{
-    int b = 1;
-    while (b < 64 && (v >> b) != 0) ++b;
-    return b;
-}
-
 // the temporary storage a sort of n pairs on any number of key bits needs
 inline size_t sort_temp_bytes(int64_t n)
 {

@@ -144,6 +144,13 @@ __device__ __forceinline__ int64_t xcd_block()
 }
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+inline int bits_for(unsigned long long v)              // bits to hold 0 .. v (the key bits of a radix sort)
+{
+    int b = 1;
+    while (b < 64 && (v >> b) != 0) ++b;
+    return b;
+}
+
 // workspaces: the caller's pointer rounded up to 256 bytes, then carved
 inline char *align_ws(void *ws) { return reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255); }
 

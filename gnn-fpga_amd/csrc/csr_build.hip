@@ -328,8 +328,8 @@ struct CsrWs {
     int32_t *bad;            // the malformed-segment flag of the degrees pass (copied to the caller's status at the end)
     int32_t *deg;            // [2][stride]  counts, then countdown cursors
     int32_t *tmp_in, *tmp_out;   // [n_segments] each
-    int32_t *sums;           // [2][n_blocks + 1]
-    int64_t stride, n_blocks;
+    int32_t *sums;           // [scan_sums_words(n_hits)]  scan_counts' block sums
+    int64_t stride;
     size_t bytes;
 };
 
@@ -337,16 +337,14 @@ CsrWs carve_csr(char *base, int64_t n_hits, int64_t n_segments)
 {
     CsrWs w;
     w.stride = (n_hits + 63) & ~(int64_t)63;
-    w.n_blocks = (n_hits + kScanTile - 1) / kScanTile;
-    size_t off = 0;
-    auto take = [&](size_t n) { char *p = base ? base + off : nullptr; off += align256(n); return p; };
+    Carver c{base};
     // [bad word + 63 pad | counts in | counts out]: cleared by ONE memset
-    w.bad = reinterpret_cast<int32_t *>(take((size_t)(64 + 2 * w.stride) * sizeof(int32_t)));
+    w.bad = c.take<int32_t>((size_t)(64 + 2 * w.stride));
     w.deg = w.bad ? w.bad + 64 : nullptr;
-    w.tmp_in = reinterpret_cast<int32_t *>(take((size_t)n_segments * sizeof(int32_t)));
-    w.tmp_out = reinterpret_cast<int32_t *>(take((size_t)n_segments * sizeof(int32_t)));
-    w.sums = reinterpret_cast<int32_t *>(take((size_t)2 * (w.n_blocks + 1) * sizeof(int32_t)));
-    w.bytes = off + 256;
+    w.tmp_in = c.take<int32_t>((size_t)n_segments);
+    w.tmp_out = c.take<int32_t>((size_t)n_segments);
+    w.sums = c.take<int32_t>((size_t)scan_sums_words(n_hits));
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -366,6 +364,7 @@ int scan_counts(const int32_t *cnt, int64_t stride, int n_arrays, int32_t *ptr_a
     const int64_t n_blocks = (n + kScanTile - 1) / kScanTile;
     const dim3 g((unsigned)n_blocks, (unsigned)n_arrays);
     GNN_LAUNCH("k_csr_scan_sums", k_csr_scan_sums, g, kBlock, s, cnt, n, stride, sums, n_blocks);
+    // the block sums of the arrays, scanned in place ([n_blocks + 1] each: the last entry = the total)
     GNN_LAUNCH("k_csr_scan", k_csr_scan_one, n_arrays, kScanOneThreads, s, sums, sums, sums + (n_blocks + 1), n_blocks,
                n_blocks + 1);
     GNN_LAUNCH("k_csr_scan_blocks", k_csr_scan_blocks, g, kBlock, s, cnt, n, stride, sums, n_blocks, ptr_a, ptr_b);
@@ -398,8 +397,7 @@ int gnn_csr_build(const int32_t *src, const int32_t *dst, int64_t n_hits, int64_
         return fail(GNN_ERR_BADARG, "gnn_csr_build: segment array missing");
     const size_t need = gnn_csr_build_workspace_bytes(n_hits, n_segments);
     if (!workspace || workspace_bytes < need) return fail(GNN_ERR_WORKSPACE, "workspace too small: need %zu bytes", need);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    CsrWs w = carve_csr(base, n_hits, n_segments);
+    CsrWs w = carve_csr(align_ws(workspace), n_hits, n_segments);
     hipError_t err = hipMemsetAsync(n_segments > 0 ? w.bad : status, 0,
                                     n_segments > 0 ? (size_t)(64 + 2 * w.stride) * sizeof(int32_t) : sizeof(int32_t), s);
     if (err == hipSuccess && n_segments == 0 && w.stride > 0)
@@ -414,17 +412,7 @@ int gnn_csr_build(const int32_t *src, const int32_t *dst, int64_t n_hits, int64_
     else if (n_segments > 0)
         GNN_LAUNCH("k_csr_degrees", k_csr_degrees, gseg, kBlock, s, src, dst, n_hits, n_segments, w.deg, w.deg + w.stride,
                    w.bad);
-    if (n_hits <= kOneBlockMax) {
-        GNN_LAUNCH("k_csr_scan", k_csr_scan_one, 2, kScanOneThreads, s, w.deg, in_ptr, out_ptr, n_hits, w.stride);
-    } else {
-        const dim3 g((unsigned)w.n_blocks, 2);
-        GNN_LAUNCH("k_csr_scan_sums", k_csr_scan_sums, g, kBlock, s, w.deg, n_hits, w.stride, w.sums, w.n_blocks);
-        // the block sums of both arrays, scanned in place ([n_blocks + 1] each: the last entry = the total)
-        GNN_LAUNCH("k_csr_scan", k_csr_scan_one, 2, kScanOneThreads, s, w.sums, w.sums, w.sums + (w.n_blocks + 1), w.n_blocks,
-                   w.n_blocks + 1);
-        GNN_LAUNCH("k_csr_scan_blocks", k_csr_scan_blocks, g, kBlock, s, w.deg, n_hits, w.stride, w.sums, w.n_blocks, in_ptr,
-                   out_ptr);
-    }
+    if (int rc = scan_counts(w.deg, w.stride, 2, in_ptr, out_ptr, n_hits, w.sums, s)) return rc;
     if (n_segments > 0) {
         if (big)
             GNN_LAUNCH("k_csr_fill_wg", k_csr_fill_wg, gwg, kWgThreads, s, src, dst, n_hits, n_segments, in_ptr, out_ptr,

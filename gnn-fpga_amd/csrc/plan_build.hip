@@ -56,8 +56,9 @@ enum Hdr {
     H_NVALID, H_NUNITS, H_NTILES, H_NPAD, H_TILEMAX, H_NSCHED, H_NRUNS, H_NMARKS, H_NCHUNKS, H_STATUS,
     H_LDSREC, H_NLDSTILES, H_LDSIN, H_LDSOUT, H_EDGEROWS, H_NLDSCHUNKS, H_MAXSTEPS, H_MAXLEVEL, H_LISTMODE, H_SPARSE, H_COUNT = 32
 };
-enum Status { ST_OK = 0, ST_DEGREE = 1, ST_TILES = 2, ST_PAD = 4, ST_CHUNKS = 8, ST_SLICES = 16, ST_I32 = 32,
-              ST_ENDPOINT = 64 };   // ST_ENDPOINT: a segment end outside [0, n_hits), or exactly one end negative
+enum Status { ST_OK = 0, ST_DEGREE = GNN_PLAN_ST_DEGREE, ST_TILES = GNN_PLAN_ST_TILES, ST_PAD = GNN_PLAN_ST_PAD,
+              ST_CHUNKS = GNN_PLAN_ST_CHUNKS, ST_SLICES = GNN_PLAN_ST_SLICES, ST_I32 = GNN_PLAN_ST_I32,
+              ST_ENDPOINT = GNN_PLAN_ST_ENDPOINT };   // (the values and what they mean: include/gnn_hip.h)
 
 struct I2 { int a, b; };
 struct I4 { int a, b, c, d; };
@@ -108,25 +109,18 @@ struct Ws {
 size_t rocprim_temp_bytes(int64_t n, int64_t E, const Bounds &b)
 {
     size_t m = 0, t = 0;
-    auto up = [&](size_t x) { if (x > m) m = x; };
-    (void)rocprim::radix_sort_pairs(nullptr, t, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                    (const int *)nullptr, (int *)nullptr, (size_t)n, 0u, 64u, (hipStream_t)0, false);
-    up(t);
-    (void)rocprim::radix_sort_pairs(nullptr, t, (const int *)nullptr, (int *)nullptr, (const int *)nullptr,
-                                    (int *)nullptr, (size_t)E, 0u, 32u, (hipStream_t)0, false);
-    up(t);
-    (void)rocprim::exclusive_scan(nullptr, t, (const int *)nullptr, (int *)nullptr, 0, (size_t)(E > n ? E : n) + 1,
-                                  rocprim::plus<int>(), (hipStream_t)0, false);
-    up(t);
-    (void)rocprim::inclusive_scan(nullptr, t, (const int *)nullptr, (int *)nullptr, (size_t)E + 1,
-                                  CarryKey(), (hipStream_t)0, false);
-    up(t);
-    (void)rocprim::exclusive_scan(nullptr, t, (const I2 *)nullptr, (I2 *)nullptr, I2{0, 0}, (size_t)b.np_max + 1, PlusI2(),
-                                  (hipStream_t)0, false);
-    up(t);
-    (void)rocprim::exclusive_scan(nullptr, t, (const I4 *)nullptr, (I4 *)nullptr, I4{0, 0, 0, 0}, (size_t)b.ns_max + 1,
-                                  PlusI4(), (hipStream_t)0, false);
-    up(t);
+    auto up = [&](hipError_t) { if (t > m) m = t; };       // (after each size query: t is what it asks for)
+    const hipStream_t s0 = 0;
+    up(rocprim::radix_sort_pairs(nullptr, t, (const unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                 (const int *)nullptr, (int *)nullptr, (size_t)n, 0u, 64u, s0, false));
+    up(rocprim::radix_sort_pairs(nullptr, t, (const int *)nullptr, (int *)nullptr, (const int *)nullptr, (int *)nullptr,
+                                 (size_t)E, 0u, 32u, s0, false));
+    up(rocprim::exclusive_scan(nullptr, t, (const int *)nullptr, (int *)nullptr, 0, (size_t)(E > n ? E : n) + 1,
+                               rocprim::plus<int>(), s0, false));
+    up(rocprim::inclusive_scan(nullptr, t, (const int *)nullptr, (int *)nullptr, (size_t)E + 1, CarryKey(), s0, false));
+    up(rocprim::exclusive_scan(nullptr, t, (const I2 *)nullptr, (I2 *)nullptr, I2{0, 0}, (size_t)b.np_max + 1, PlusI2(), s0, false));
+    up(rocprim::exclusive_scan(nullptr, t, (const I4 *)nullptr, (I4 *)nullptr, I4{0, 0, 0, 0}, (size_t)b.ns_max + 1, PlusI4(), s0,
+                               false));
     return m + 256;
 }
 
@@ -134,28 +128,23 @@ Ws carve(char *p, int64_t n, int64_t E, int CH)
 {
     const Bounds b = bounds_of(n, E, CH);
     Ws w;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char *q = p ? p + off : nullptr;
-        off += align256(bytes);
-        return q;
-    };
-    auto ints = [&](int64_t k) { return reinterpret_cast<int *>(take((size_t)k * sizeof(int))); };
-    w.hdr = reinterpret_cast<int64_t *>(take(H_COUNT * sizeof(int64_t)));
+    Carver c{p};
+    auto ints = [&](int64_t k) { return c.take<int>((size_t)k); };
+    w.hdr = c.take<int64_t>(H_COUNT);
     w.chg = ints(kMaxLevelIters + 2);
     w.deg_in = ints(n); w.deg_out = ints(n);                    // (one memset clears hdr .. lvB)
     w.lvA = ints(n); w.lvB = ints(n);
     w.gid = ints(n); w.down = ints(n); w.hkey = ints(n);
     w.iota = ints(n); w.base = ints(n); w.oor = ints(n); w.tpos = ints(n); w.uflag = ints(n + 1); w.uscan = ints(n + 1);
     w.ustart = ints(n + 2); w.inv = ints(n + 1);
-    w.k64a = reinterpret_cast<unsigned long long *>(take((size_t)n * 8));
-    w.k64b = reinterpret_cast<unsigned long long *>(take((size_t)n * 8));
+    w.k64a = c.take<unsigned long long>((size_t)n);
+    w.k64b = c.take<unsigned long long>((size_t)n);
     w.tile_bounds = ints(b.nt_max + 2); w.tpad_off = ints(b.nt_max + 2); w.sbase = ints(b.nt_max + 2);
     w.t_desc = ints((b.nt_max + 1) * 8);
-    w.degn = reinterpret_cast<I2 *>(take((size_t)(b.np_max + 1) * sizeof(I2)));
-    w.ptr = reinterpret_cast<I2 *>(take((size_t)(b.np_max + 1) * sizeof(I2)));
-    w.sl4 = reinterpret_cast<I4 *>(take((size_t)(b.ns_max + 1) * sizeof(I4)));
-    w.off4 = reinterpret_cast<I4 *>(take((size_t)(b.ns_max + 1) * sizeof(I4)));
+    w.degn = c.take<I2>((size_t)b.np_max + 1);
+    w.ptr = c.take<I2>((size_t)b.np_max + 1);
+    w.sl4 = c.take<I4>((size_t)b.ns_max + 1);
+    w.off4 = c.take<I4>((size_t)b.ns_max + 1);
     w.slice_tile = ints(b.ns_max + 1);
     w.trange = ints((b.nt_max + 1) * 4);
     w.src_new = ints(E); w.dst_new = ints(E); w.kscr = ints(E + 1); w.sv_in = ints(E); w.sv_out = ints(E);
@@ -163,11 +152,11 @@ Ws carve(char *p, int64_t n, int64_t E, int CH)
     w.mscan = ints(E + 1);
     w.marks = ints(b.m_max + 2); w.parts = ints(b.m_max + 2); w.pscan = ints(b.m_max + 2);
     w.cb = ints(b.c_max + 2); w.c_desc = ints((b.c_max + 1) * 8);
-    w.pin = reinterpret_cast<I2 *>(take((size_t)E * sizeof(I2)));
-    w.pout = reinterpret_cast<I2 *>(take((size_t)E * sizeof(I2)));
+    w.pin = c.take<I2>((size_t)E);
+    w.pout = c.take<I2>((size_t)E);
     w.temp_bytes = rocprim_temp_bytes(n, E, b);
-    w.temp = take(w.temp_bytes);
-    w.bytes = off;
+    w.temp = c.take<char>(w.temp_bytes);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -408,9 +397,10 @@ __global__ __launch_bounds__(1024) void pb_levels_small(const int *__restrict__ 
 // The workgroup checks what it was told: a valid segment with an end outside its graph's hit range, hit / segment
 // ranges that do not tile [0, n) / [0, E), a graph larger than the LDS capacity: FAST_MISS, and the caller runs the
 // global form (every output of this kernel is rewritten there).
-constexpr int ST_FAST_MISS = 128;
+constexpr int ST_FAST_MISS = GNN_PLAN_ST_FAST_MISS;
 constexpr int kGraphLdsBytes = 152 * 1024;
 constexpr int kGraphCapHits = kGraphLdsBytes / 8;          // 19456 hits per graph: 8 bytes of tables, then the sort keys
+static_assert(kGraphCapHits == GNN_PLAN_GRAPH_CAP_HITS, "the header tells callers the cap");
 constexpr int kGraphCapHits64 = 16384;                     // ... 8-byte keys up to here, beyond it only 4-byte ones fit
 __host__ __device__ inline int pow2_ceil(int v) { int p = 2; while (p < v) p <<= 1; return p; }
 
@@ -754,7 +744,8 @@ __global__ __launch_bounds__(TB) void pb_sort_lists(const I2 *__restrict__ degn,
 constexpr int kTileListEntries = 16384;               // staged (segment, other end) pairs per tile and direction: 128 KB
 struct TR { int in_lo, in_nhi, out_lo, out_nhi; };    // (nhi = -max: one memset to 0x7F.. initialises all four for atomicMin)
 
-template <bool INV_LDS>
+// (the graph's new ids always fit the LDS: 4 bytes a hit, up to kGraphCapHits of them)
+static_assert((size_t)kGraphCapHits * 4 <= (size_t)kGraphLdsBytes / 2, "pb_graph_renumber keeps a graph's new ids in LDS");
 __global__ __launch_bounds__(1024) void pb_graph_renumber(const int *__restrict__ src, const int *__restrict__ dst,
                                                           const int64_t *__restrict__ hit_ptr,
                                                           const int64_t *__restrict__ seg_ptr, int64_t G, int n, int cap,
@@ -775,8 +766,7 @@ __global__ __launch_bounds__(1024) void pb_graph_renumber(const int *__restrict_
         const int64_t e0 = seg_ptr[g], e1 = seg_ptr[g + 1];
         const int lo = (int)hit_ptr[g], nh = (int)(hit_ptr[g + 1] - hit_ptr[g]);
         __syncthreads();
-        if (INV_LDS)
-            for (int i = threadIdx.x; i < nh; i += B) linv[i] = inv[lo + i];
+        for (int i = threadIdx.x; i < nh; i += B) linv[i] = inv[lo + i];
         __syncthreads();
         const int64_t span = 4 * (int64_t)B;
         auto load4 = [&](int64_t jb, int *sv, int *dv) {
@@ -797,8 +787,8 @@ __global__ __launch_bounds__(1024) void pb_graph_renumber(const int *__restrict_
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const bool ok = sv[u] >= 0;
-                sn[u] = ok ? (INV_LDS ? linv[sv[u] - lo] : inv[sv[u]]) : npad;
-                dn[u] = ok ? (INV_LDS ? linv[dv[u] - lo] : inv[dv[u]]) : npad;
+                sn[u] = ok ? linv[sv[u] - lo] : npad;
+                dn[u] = ok ? linv[dv[u] - lo] : npad;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {                 // (all eight tile look-ups in flight before anything waits)
@@ -1841,18 +1831,230 @@ __global__ __launch_bounds__(TB) void pb_fill_chunks(int nc, const int *__restri
     }
 }
 
-inline unsigned bit_width(uint64_t v)
-{
-    unsigned b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b ? b : 1;
-}
-
 #define HIP_OK(CALL, WHAT)                                                                            \
     do {                                                                                              \
         hipError_t e_ = (CALL);                                                                       \
         if (e_ != hipSuccess) return fail(-(int)e_, "%s failed: %s", WHAT, hipGetErrorString(e_));   \
     } while (0)
+
+// ---- host side of stage 1.  The builder's environment switch (tests, A / B timing): this is its one reader, called once
+// per library call and not cached - tests flip it inside one process.
+struct PlanSwitches { bool scatter_lists; };       // GNN_PLAN_SCATTER_LISTS=1: the graph-local form's scattered-pairs lists
+PlanSwitches read_plan_switches()
+{
+    const char *fs = getenv("GNN_PLAN_SCATTER_LISTS");
+    return {fs && fs[0] == '1'};
+}
+
+// Which recipe a build takes and the launch shape of its per-graph kernels: fixed by choose_plan_form before the first
+// launch.  The global form uses `local` alone.
+struct PlanForm {
+    bool local;                     // GRAPH-LOCAL (the caller named its graphs' segment ranges) or GLOBAL
+    int cap;                        // hits the per-graph LDS tables hold
+    unsigned threads, grid;         // of pb_graph_levels, pb_graph_renumber, pb_graph_lists
+    size_t levels_lds, renumber_lds, lists_lds;
+    bool lists_inv_lds;             // pb_graph_lists<true>: the graph's new ids fit the LDS next to its two cursor tables
+    bool scatter_lists;             // pb_lists_mode is told to refuse the per-tile lists
+};
+PlanForm choose_plan_form(bool local, int64_t max_graph_hits, int64_t max_graph_segments, int64_t G, const PlanSwitches &sw)
+{
+    PlanForm f = {};
+    if (!(f.local = local)) return f;
+    // the cap of the LDS tables: the largest graph, rounded (a fresh opt-in per size would cost more than it saves)
+    const int64_t rounded = (max_graph_hits + 1023) / 1024 * 1024;
+    f.cap = (int)(rounded < kGraphCapHits ? rounded : kGraphCapHits);
+    f.threads = max_graph_segments > 8192 ? 1024u : 256u;
+    f.grid = (unsigned)(G < 16384 ? G : 16384);
+    // sort keys of 8 bytes in a power-of-two table while they fit, of 4 bytes beyond (pb_graph_levels)
+    f.levels_lds = f.cap <= kGraphCapHits64 ? (size_t)pow2_ceil(f.cap) * 8 : (size_t)f.cap * 8;
+    f.renumber_lds = (size_t)f.cap * 4;
+    f.lists_inv_lds = (size_t)f.cap * 12 <= (size_t)kGraphLdsBytes;
+    f.lists_lds = (size_t)f.cap * (f.lists_inv_lds ? 12 : 8);
+    f.scatter_lists = sw.scatter_lists;
+    return f;
+}
+
+// dynamic LDS above 64 KB must be opted into, once per device (both forms' kernels, whichever form the first build takes)
+void opt_in_large_lds()
+{
+    static DevOnce attr_done;
+    if (!attr_done.need()) return;
+    const void *kernels[] = {reinterpret_cast<const void *>(&pb_graph_levels), reinterpret_cast<const void *>(&pb_graph_lists<true>),
+                             reinterpret_cast<const void *>(&pb_graph_lists<false>), reinterpret_cast<const void *>(&pb_graph_renumber),
+                             reinterpret_cast<const void *>(&pb_tile_lists), reinterpret_cast<const void *>(&pb_cut_tiles_par)};
+    for (const void *k : kernels) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
+}
+
+// One stage 1 in flight: what its launchers share.  One launcher per stage of the recipe in the file header; the two
+// forms differ in the hit order, the lists, the segment runs and the marks.
+struct PlanBuild {
+    const int32_t *src, *dst;
+    const int64_t *hit_ptr, *seg_ptr;
+    int64_t n, E, G;
+    int tile_hits, iter_records, CH, edge_records;
+    hipStream_t s;
+    PlanForm f;
+    Ws w;
+    Bounds b;
+    // the header and what follows it in the workspace up to `upto`, and the degrees per new id, start at zero
+    int zero(const void *upto) const
+    {
+        HIP_OK(hipMemsetAsync(w.hdr, 0, (size_t)(static_cast<const char *>(upto) - reinterpret_cast<char *>(w.hdr)), s), "memset");
+        HIP_OK(hipMemsetAsync(w.degn, 0, (size_t)(b.np_max + 1) * sizeof(I2), s), "memset");
+        return 0;
+    }
+    // rocPRIM's scans and sorts out of w.temp; `what` names a failure.  Scans start at zero (T{}) when exclusive
+    template <bool INCLUSIVE = false, typename T, typename Op>
+    int scan(const char *what, const T *in, T *out, int64_t count, Op op) const
+    {
+        size_t tb = w.temp_bytes;
+        if constexpr (INCLUSIVE) HIP_OK(rocprim::inclusive_scan(w.temp, tb, in, out, (size_t)count, op, s, false), what);
+        else HIP_OK(rocprim::exclusive_scan(w.temp, tb, in, out, T{}, (size_t)count, op, s, false), what);
+        return 0;
+    }
+    template <typename K>
+    int sort_pairs(const char *what, const K *kin, K *kout, const int *vin, int *vout, int64_t count, int bits) const
+    {
+        size_t tb = w.temp_bytes;
+        HIP_OK(rocprim::radix_sort_pairs(w.temp, tb, kin, kout, vin, vout, (size_t)count, 0u, (unsigned)bits, s, false), what);
+        return 0;
+    }
+
+    // hits in (graph, level, -in, -out) order and the unit flags, GLOBAL: degrees, level sweeps, one device-wide sort
+    int hit_order_global() const
+    {
+        if (int rc = zero(w.gid)) return rc;         // header, sweep flags, degrees and both level buffers (adjacent)
+        const int64_t nb = (E + kDegSegs - 1) / kDegSegs;
+        GNN_LAUNCH("pb_degrees", pb_degrees, (unsigned)(nb < 2048 ? nb : 2048), 1024, s, src, dst, E, (int)n, w.deg_in,
+                   w.deg_out, w.hdr);
+        GNN_LAUNCH("pb_gid", pb_gid, gs(n), TB, s, hit_ptr, G, n, w.gid);
+        int *level = w.lvA;
+        if (E <= kSmallSweepSegments) {
+            GNN_LAUNCH("pb_levels_small", pb_levels_small, 1, 1024, s, src, dst, (int)E, (int)n, level);
+        } else {
+            // in rounds of 12 sweeps (a 10-layer detector graph is done after 11); one 4-byte read-back per
+            // round costs ~15 us, the 52 launches it usually saves cost 0.3 ms
+            unsigned char *lv8 = reinterpret_cast<unsigned char *>(w.lvB);   // (zeroed with the header)
+            // the blocks' "dead" bytes live in the zeroed rest of lvB (4 n bytes, n of them levels)
+            const int blk = E >= (4ll << 20) ? 4096 : 1024;
+            const int64_t nblk = (E + blk - 1) / blk;
+            const int64_t dead_off = (n + 255) / 256 * 256;
+            unsigned char *dead = dead_off + nblk <= 4 * n ? lv8 + dead_off : nullptr;
+            const unsigned sg = (unsigned)(nblk < 1 ? 1 : nblk > 8192 ? 8192 : nblk);
+            for (int t = 1; t <= kMaxLevelIters; ++t) {
+                GNN_LAUNCH("pb_level_sweep", pb_level_sweep, sg, TB, s, src, dst, E, (int)n, lv8, w.chg, t, dead, blk);
+                if (t % kSweepRound == 0 && t < kMaxLevelIters) {
+                    int raised = 1;
+                    HIP_OK(hipMemcpyAsync(&raised, w.chg + t, sizeof(int), hipMemcpyDeviceToHost, s), "sweep flag read-back");
+                    HIP_OK(hipStreamSynchronize(s), "sweep flag read-back");
+                    if (!raised) break;
+                }
+            }
+            GNN_LAUNCH("pb_widen", pb_widen, gs(n), TB, s, lv8, level, n);
+        }
+        GNN_LAUNCH("pb_fill_i32", pb_fill_i32, gs(n), TB, s, w.down, n, 0x7FFFFFFF);
+        GNN_LAUNCH("pb_down", pb_down, gs(E), TB, s, src, dst, E, (int)n, level, w.deg_in, w.down);
+        GNN_LAUNCH("pb_key1", pb_key1, gs(n), TB, s, n, w.deg_in, w.deg_out, w.gid, level, w.down, w.k64a, w.iota, w.hkey, w.hdr);
+        if (int rc = sort_pairs("hit sort 1", w.k64a, w.k64b, w.iota, w.base, n, 39 + bits_for((unsigned long long)G))) return rc;
+        GNN_LAUNCH("pb_unit_flags", pb_unit_flags, gs(n + 1), TB, s, n, w.k64b, w.uflag);
+        return 0;
+    }
+    // the same, GRAPH-LOCAL: one workgroup per graph sorts its hits in LDS (and writes the run flags of segment_runs)
+    int hit_order_graphs() const
+    {
+        if (int rc = zero(w.deg_in)) return rc;      // header and sweep flags
+        GNN_LAUNCH_SH("pb_graph_levels", pb_graph_levels, f.grid, f.threads, f.levels_lds, s, src, dst, hit_ptr, seg_ptr, G, n,
+                      E, f.cap, w.deg_in, w.deg_out, w.gid, w.lvA, w.k64a, w.iota, w.hkey, w.mscan, w.base, w.uflag, w.hdr);
+        return 0;
+    }
+    // (graph, level) units, tiles cut from them, hits sorted by degree inside their tile
+    int units_and_tiles() const
+    {
+        if (int rc = scan("unit scan", w.uflag, w.uscan, n + 1, rocprim::plus<int>())) return rc;
+        GNN_LAUNCH("pb_compact", pb_compact, gs(n + 1), TB, s, n, w.uflag, w.uscan, w.ustart, w.hdr, (int)H_NUNITS);
+        GNN_LAUNCH_SH("pb_cut_tiles_par", pb_cut_tiles_par, 1, 1024, (size_t)(3 * kParUnits + 1) * 4, s, w.ustart, (int)n,
+                      tile_hits, w.tile_bounds, w.hdr, (int)b.nt_max);
+        GNN_LAUNCH("pb_cut_tiles", pb_cut_tiles, 1, 1024, s, w.ustart, (int)n, tile_hits, w.tile_bounds, w.hdr, (int)b.nt_max);
+        // (both forms: the second hit sort is local to a tile - one workgroup sorts it in LDS; the global form ran a
+        // device-wide radix sort of (tile, -ceil(in / 4), -out) keys here until late round 3)
+        GNN_LAUNCH("pb_tile_sort", pb_tile_sort, 4096, TB, s, n, w.base, w.deg_in, w.deg_out, w.tile_bounds, w.hdr, w.tpos, w.oor);
+        GNN_LAUNCH("pb_tile_offsets", pb_tile_offsets, 1, 1024, s, w.tile_bounds, w.tpad_off, w.sbase, w.hdr, b.np_max);
+        return 0;
+    }
+    // padded new ids, and where every new id's two lists start
+    int new_ids() const
+    {
+        GNN_LAUNCH("pb_new_ids", pb_new_ids, gs(n + 1), TB, s, n, w.oor, w.tpos, w.tile_bounds, w.tpad_off, w.deg_in, w.deg_out,
+                   w.inv, w.degn, w.slice_tile, w.hdr);
+        return scan("degree scan", w.degn, w.ptr, b.np_max + 1, PlusI2());
+    }
+    // renumbered endpoints and both neighbour lists, GLOBAL: two device-wide sorts of (end hit, other end) pairs
+    int lists_global() const
+    {
+        GNN_LAUNCH("pb_renumber", pb_renumber, gs(E), TB, s, src, dst, E, w.inv, (int)n, w.src_new, w.dst_new, w.hdr);
+        const int idbits = bits_for((unsigned long long)b.np_max);
+        if (int rc = sort_pairs("segment sort (in)", w.dst_new, w.kscr, w.src_new, w.sv_in, E, idbits)) return rc;
+        return sort_pairs("segment sort (out)", w.src_new, w.kscr, w.dst_new, w.sv_out, E, idbits);
+    }
+    // the same, GRAPH-LOCAL: per tile in LDS or by scattered pairs and a sort per list - pb_lists_mode decides on the
+    // device, both sets of kernels are launched and the wrong one returns at once
+    int lists_graphs() const
+    {
+        TR *trange = reinterpret_cast<TR *>(w.trange);
+        HIP_OK(hipMemsetAsync(w.trange, 0x7F, (size_t)(b.nt_max + 1) * sizeof(TR), s), "memset");
+        GNN_LAUNCH_SH("pb_graph_renumber", pb_graph_renumber, f.grid, f.threads, f.renumber_lds, s, src, dst, hit_ptr, seg_ptr,
+                      G, (int)n, f.cap, w.inv, w.slice_tile, w.src_new, w.dst_new, trange, w.hdr);
+        GNN_LAUNCH("pb_lists_mode", pb_lists_mode, 1, 1024, s, trange, w.tpad_off, w.ptr, E, f.scatter_lists ? 1 : 0, w.hdr);
+        GNN_LAUNCH_SH("pb_tile_lists", pb_tile_lists, 4096, 1024, (size_t)(2 * kTileListEntries + 2 * kMaxSlicesPerTile * SLICE) * 4,
+                      s, w.src_new, w.dst_new, trange, w.tpad_off, w.degn, w.ptr, w.sv_in, w.sv_out, w.sbase, iter_records,
+                      w.t_desc, w.hdr);
+        GNN_LAUNCH_SH("pb_graph_lists", f.lists_inv_lds ? pb_graph_lists<true> : pb_graph_lists<false>, f.grid, f.threads,
+                      f.lists_lds, s, src, dst, hit_ptr, seg_ptr, G, (int)n, f.cap, w.inv, w.ptr, w.src_new, w.dst_new, w.pin,
+                      w.pout, w.hdr);
+        GNN_LAUNCH("pb_sort_lists", pb_sort_lists, 4096, TB, s, w.degn, w.ptr, w.pin, w.pout, w.sv_in, w.sv_out, w.hdr);
+        return 0;
+    }
+    // SELL-16 slice lengths and offsets, the tiles' windows
+    int slices_and_windows() const
+    {
+        GNN_LAUNCH("pb_slices", pb_slices, gs(b.ns_max + 1), TB, s, b.ns_max, w.degn, w.sl4, w.hdr);
+        if (int rc = scan("slice scan", w.sl4, w.off4, b.ns_max + 1, PlusI4())) return rc;
+        GNN_LAUNCH("pb_tile_windows", pb_tile_windows, 2048, TB, s, w.tpad_off, w.sbase, w.degn, w.ptr, w.sv_in, w.sv_out,
+                   iter_records, w.t_desc, w.hdr);
+        return 0;
+    }
+    // edge chunks.  The flags of where a run of segments with one start hit key begins, GLOBAL only
+    int segment_runs() const
+    {
+        GNN_LAUNCH("pb_seg_keys", pb_seg_keys, gs(E), TB, s, src, E, (int)n, w.hkey, w.kscr);
+        if (int rc = scan<true>("key carry scan", w.kscr, w.rb, E, CarryKey())) return rc;
+        GNN_LAUNCH("pb_run_flags", pb_run_flags, gs(E + 1), TB, s, E, w.rb, w.mscan);
+        return 0;
+    }
+    // The runs' starts; from them the marks between chunks, in the form's own way - GRAPH-LOCAL: one workgroup (a few
+    // thousand runs, else FAST_MISS), GLOBAL: a flag, a scan and a compaction over all segments; the chunks, their windows
+    int marks_and_chunks() const
+    {
+        if (int rc = scan("run scan", w.mscan, w.c_scan, E + 1, rocprim::plus<int>())) return rc;
+        GNN_LAUNCH("pb_compact", pb_compact, gs(E + 1), TB, s, E, w.mscan, w.c_scan, w.rb, w.hdr, (int)H_NRUNS);
+        if (f.local) {
+            GNN_LAUNCH("pb_marks_fast", pb_marks_fast, 1, 1024, s, w.rb, E, CH, w.marks, b.m_max, w.hdr);
+        } else {
+            GNN_LAUNCH("pb_mark_flags", pb_mark_flags, gs(E + 1), TB, s, w.rb, E, CH, w.mscan, w.hdr);
+            if (int rc = scan("mark scan", w.mscan, w.c_scan, E + 1, rocprim::plus<int>())) return rc;
+            GNN_LAUNCH("pb_marks", pb_marks, gs(E + 1), TB, s, w.rb, E, w.mscan, w.c_scan, w.marks, b.m_max, w.hdr);
+        }
+        GNN_LAUNCH("pb_chunk_bounds", pb_chunk_bounds, 1, 1024, s, w.marks, CH, w.parts, w.pscan, w.cb, b.c_max, w.hdr);
+        GNN_LAUNCH("pb_chunk_windows", pb_chunk_windows, 2048, TB, s, w.cb, src, w.src_new, w.dst_new, edge_records, w.c_desc,
+                   w.hdr);
+        return 0;
+    }
+    int sizes(gnn_plan_sizes_t *sizes_out) const
+    {
+        GNN_LAUNCH("pb_sizes", pb_sizes, 1, 64, s, w.hdr, w.off4, sizes_out, b.np_max, b.ns_max);
+        return 0;
+    }
+};
 
 }  // namespace
 
@@ -1861,7 +2063,7 @@ extern "C" {
 size_t gnn_plan_build_workspace_bytes(int64_t n_hits, int64_t n_segments, int32_t chunk_segments)
 {
     if (n_hits <= 0 || n_segments <= 0 || chunk_segments <= 0) return 0;
-    return carve(nullptr, n_hits, n_segments, chunk_segments).bytes + 256;
+    return carve(nullptr, n_hits, n_segments, chunk_segments).bytes;
 }
 
 // seg_ptr != nullptr: the graph-local form (pb_graph_levels, pb_graph_lists); its FAST_MISS status sends the caller
@@ -1876,175 +2078,27 @@ static int plan_sizes_impl(const int32_t *src, const int32_t *dst, const int64_t
     if (!src || !dst || !hit_ptr || !workspace || !sizes_out || n <= 0 || E <= 0 || G <= 0 || tile_hits < SLICE ||
         tile_hits > kMaxSlicesPerTile * SLICE || chunk_segments <= 0 || iter_records < 0 || edge_records < 0)
         return fail(GNN_ERR_BADARG, "gnn_plan_build_sizes: bad argument");
-    const bool fast = seg_ptr != nullptr;
-    if (fast && (max_graph_hits <= 0 || max_graph_hits > kGraphCapHits || max_graph_segments < 0))
+    if (seg_ptr && (max_graph_hits <= 0 || max_graph_hits > kGraphCapHits || max_graph_segments < 0))
         return fail(GNN_ERR_UNSUPPORTED, "gnn_plan_build_sizes_graphs: a graph of %lld hits does not fit the graph-local form "
                     "(<= %d)", (long long)max_graph_hits, kGraphCapHits);
     if (n >= (1ll << 30) || E >= (1ll << 30) || G >= (1ll << 24))
         return fail(GNN_ERR_UNSUPPORTED, "gnn_plan_build_sizes: batch too large for 32-bit plan indices");
     if (workspace_bytes < gnn_plan_build_workspace_bytes(n, E, chunk_segments))
         return fail(GNN_ERR_WORKSPACE, "gnn_plan_build_sizes: workspace too small");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char *wb = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const Ws w = carve(wb, n, E, chunk_segments);
-    const Bounds b = bounds_of(n, E, chunk_segments);
-    int *level = w.lvA;
-    // the cap of the LDS tables: the largest graph, rounded (a fresh opt-in per size would cost more than it saves)
-    const int cap = (int)((max_graph_hits + 1023) / 1024 * 1024 < kGraphCapHits ? (max_graph_hits + 1023) / 1024 * 1024
-                                                                                : kGraphCapHits);
-    const unsigned gthreads = max_graph_segments > 8192 ? 1024u : 256u;
-    const unsigned ggrid = (unsigned)(G < 16384 ? G : 16384);
-    if (fast) {
-        static DevOnce attr_done;     // dynamic LDS above 64 KB must be opted into, once per device
-        if (attr_done.need()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_graph_levels),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_graph_lists<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_graph_lists<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_graph_renumber<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_tile_lists),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
-        }
-        HIP_OK(hipMemsetAsync(w.hdr, 0, (size_t)(reinterpret_cast<char *>(w.deg_in) - reinterpret_cast<char *>(w.hdr)), s),
-               "memset");
-        HIP_OK(hipMemsetAsync(w.degn, 0, (size_t)(b.np_max + 1) * sizeof(I2), s), "memset");
-        GNN_LAUNCH_SH("pb_graph_levels", pb_graph_levels, ggrid, gthreads,
-                      cap <= kGraphCapHits64 ? (size_t)pow2_ceil(cap) * 8 : (size_t)cap * 8, s, src, dst, hit_ptr, seg_ptr, G, n,
-                      E, cap, w.deg_in, w.deg_out, w.gid, level, w.k64a, w.iota, w.hkey, w.mscan, w.base, w.uflag, w.hdr);
-    } else {
-    // header, sweep flags, degrees and both level buffers start at zero (adjacent in the workspace)
-    HIP_OK(hipMemsetAsync(w.hdr, 0, (size_t)(reinterpret_cast<char *>(w.gid) - reinterpret_cast<char *>(w.hdr)), s), "memset");
-    HIP_OK(hipMemsetAsync(w.degn, 0, (size_t)(b.np_max + 1) * sizeof(I2), s), "memset");
-    {
-        const int64_t nb = (E + kDegSegs - 1) / kDegSegs;
-        GNN_LAUNCH("pb_degrees", pb_degrees, (unsigned)(nb < 2048 ? nb : 2048), 1024, s, src, dst, E, (int)n, w.deg_in,
-                   w.deg_out, w.hdr);
-    }
-    GNN_LAUNCH("pb_gid", pb_gid, gs(n), TB, s, hit_ptr, G, n, w.gid);
-    if (E <= kSmallSweepSegments)
-        GNN_LAUNCH("pb_levels_small", pb_levels_small, 1, 1024, s, src, dst, (int)E, (int)n, level);
-    else
-        // in rounds of 12 sweeps (a 10-layer detector graph is done after 11); one 4-byte read-back per
-        // round costs ~15 us, the 52 launches it usually saves cost 0.3 ms
-    {
-        unsigned char *lv8 = reinterpret_cast<unsigned char *>(w.lvB);   // (zeroed with the header)
-        // the blocks' "dead" bytes live in the zeroed rest of lvB (4 n bytes, n of them levels)
-        const int blk = E >= (4ll << 20) ? 4096 : 1024;
-        const int64_t nblk = (E + blk - 1) / blk;
-        const int64_t dead_off = (n + 255) / 256 * 256;
-        unsigned char *dead = dead_off + nblk <= 4 * n ? lv8 + dead_off : nullptr;
-        const unsigned sg = (unsigned)(nblk < 1 ? 1 : nblk > 8192 ? 8192 : nblk);
-        for (int t = 1; t <= kMaxLevelIters; ++t) {
-            GNN_LAUNCH("pb_level_sweep", pb_level_sweep, sg, TB, s, src, dst, E, (int)n, lv8, w.chg, t, dead, blk);
-            if (t % kSweepRound == 0 && t < kMaxLevelIters) {
-                int raised = 1;
-                HIP_OK(hipMemcpyAsync(&raised, w.chg + t, sizeof(int), hipMemcpyDeviceToHost, s), "sweep flag read-back");
-                HIP_OK(hipStreamSynchronize(s), "sweep flag read-back");
-                if (!raised) break;
-            }
-        }
-        GNN_LAUNCH("pb_widen", pb_widen, gs(n), TB, s, lv8, level, n);
-    }
-    GNN_LAUNCH("pb_fill_i32", pb_fill_i32, gs(n), TB, s, w.down, n, 0x7FFFFFFF);
-    GNN_LAUNCH("pb_down", pb_down, gs(E), TB, s, src, dst, E, (int)n, level, w.deg_in, w.down);
-    GNN_LAUNCH("pb_key1", pb_key1, gs(n), TB, s, n, w.deg_in, w.deg_out, w.gid, level, w.down, w.k64a, w.iota, w.hkey, w.hdr);
-    }
-    size_t tb = w.temp_bytes;
-    if (!fast) {                          // (graph-local form: pb_graph_levels sorted each graph's hits in LDS)
-        HIP_OK(rocprim::radix_sort_pairs(w.temp, tb, (const unsigned long long *)w.k64a, w.k64b, (const int *)w.iota, w.base,
-                                         (size_t)n, 0u, 39u + bit_width((uint64_t)G), s, false), "hit sort 1");
-        GNN_LAUNCH("pb_unit_flags", pb_unit_flags, gs(n + 1), TB, s, n, w.k64b, w.uflag);
-    }
-    tb = w.temp_bytes;
-    HIP_OK(rocprim::exclusive_scan(w.temp, tb, (const int *)w.uflag, w.uscan, 0, (size_t)n + 1, rocprim::plus<int>(), s, false),
-           "unit scan");
-    GNN_LAUNCH("pb_compact", pb_compact, gs(n + 1), TB, s, n, w.uflag, w.uscan, w.ustart, w.hdr, (int)H_NUNITS);
-    {
-        static DevOnce cut_attr;
-        if (cut_attr.need())
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&pb_cut_tiles_par),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kGraphLdsBytes);
-    }
-    GNN_LAUNCH_SH("pb_cut_tiles_par", pb_cut_tiles_par, 1, 1024, (size_t)(3 * kParUnits + 1) * 4, s, w.ustart, (int)n,
-                  (int)tile_hits, w.tile_bounds, w.hdr, (int)b.nt_max);
-    GNN_LAUNCH("pb_cut_tiles", pb_cut_tiles, 1, 1024, s, w.ustart, (int)n, (int)tile_hits, w.tile_bounds, w.hdr,
-               (int)b.nt_max);
-    // (both forms: the second hit sort is local to a tile - one workgroup sorts it in LDS; the global form ran a
-    // device-wide radix sort of (tile, -ceil(in / 4), -out) keys here until late round 3)
-    GNN_LAUNCH("pb_tile_sort", pb_tile_sort, 4096, TB, s, n, w.base, w.deg_in, w.deg_out, w.tile_bounds, w.hdr, w.tpos, w.oor);
-    GNN_LAUNCH("pb_tile_offsets", pb_tile_offsets, 1, 1024, s, w.tile_bounds, w.tpad_off, w.sbase, w.hdr, b.np_max);
-    GNN_LAUNCH("pb_new_ids", pb_new_ids, gs(n + 1), TB, s, n, w.oor, w.tpos, w.tile_bounds, w.tpad_off, w.deg_in, w.deg_out,
-               w.inv, w.degn, w.slice_tile, w.hdr);
-    tb = w.temp_bytes;
-    HIP_OK(rocprim::exclusive_scan(w.temp, tb, (const I2 *)w.degn, w.ptr, I2{0, 0}, (size_t)b.np_max + 1, PlusI2(), s, false),
-           "degree scan");
-    if (fast) {
-        HIP_OK(hipMemsetAsync(w.trange, 0x7F, (size_t)(b.nt_max + 1) * sizeof(TR), s), "memset");
-        if ((size_t)cap * 4 <= (size_t)kGraphLdsBytes / 2)
-            GNN_LAUNCH_SH("pb_graph_renumber", pb_graph_renumber<true>, ggrid, gthreads, (size_t)cap * 4, s, src, dst, hit_ptr,
-                          seg_ptr, G, (int)n, cap, w.inv, w.slice_tile, w.src_new, w.dst_new, reinterpret_cast<TR *>(w.trange),
-                          w.hdr);
-        else
-            GNN_LAUNCH_SH("pb_graph_renumber", pb_graph_renumber<false>, ggrid, gthreads, 0, s, src, dst, hit_ptr, seg_ptr, G,
-                          (int)n, cap, w.inv, w.slice_tile, w.src_new, w.dst_new, reinterpret_cast<TR *>(w.trange), w.hdr);
-        const char *fs = getenv("GNN_PLAN_SCATTER_LISTS");       // (tests and A / B timing: the scattered-pairs form)
-        GNN_LAUNCH("pb_lists_mode", pb_lists_mode, 1, 1024, s, reinterpret_cast<const TR *>(w.trange), w.tpad_off, w.ptr, E,
-                   (fs && fs[0] == '1') ? 1 : 0, w.hdr);
-        GNN_LAUNCH_SH("pb_tile_lists", pb_tile_lists, 4096, 1024, (size_t)(2 * kTileListEntries + 2 * kMaxSlicesPerTile * SLICE) * 4, s,
-                      w.src_new, w.dst_new, reinterpret_cast<const TR *>(w.trange), w.tpad_off, w.degn, w.ptr, w.sv_in, w.sv_out,
-                      w.sbase, (int)iter_records, w.t_desc, w.hdr);
-        if ((size_t)cap * 12 <= (size_t)kGraphLdsBytes)
-            GNN_LAUNCH_SH("pb_graph_lists", pb_graph_lists<true>, ggrid, gthreads, (size_t)cap * 12, s, src, dst, hit_ptr, seg_ptr,
-                          G, (int)n, cap, w.inv, w.ptr, w.src_new, w.dst_new, w.pin, w.pout, w.hdr);
-        else
-            GNN_LAUNCH_SH("pb_graph_lists", pb_graph_lists<false>, ggrid, gthreads, (size_t)cap * 8, s, src, dst, hit_ptr, seg_ptr,
-                          G, (int)n, cap, w.inv, w.ptr, w.src_new, w.dst_new, w.pin, w.pout, w.hdr);
-        GNN_LAUNCH("pb_sort_lists", pb_sort_lists, 4096, TB, s, w.degn, w.ptr, w.pin, w.pout, w.sv_in, w.sv_out, w.hdr);
-    } else {
-        GNN_LAUNCH("pb_renumber", pb_renumber, gs(E), TB, s, src, dst, E, w.inv, (int)n, w.src_new, w.dst_new, w.hdr);
-        const unsigned idbits = bit_width((uint64_t)b.np_max);
-        tb = w.temp_bytes;
-        HIP_OK(rocprim::radix_sort_pairs(w.temp, tb, (const int *)w.dst_new, w.kscr, (const int *)w.src_new, w.sv_in, (size_t)E,
-                                         0u, idbits, s, false), "segment sort (in)");
-        tb = w.temp_bytes;
-        HIP_OK(rocprim::radix_sort_pairs(w.temp, tb, (const int *)w.src_new, w.kscr, (const int *)w.dst_new, w.sv_out, (size_t)E,
-                                         0u, idbits, s, false), "segment sort (out)");
-    }
-    GNN_LAUNCH("pb_slices", pb_slices, gs(b.ns_max + 1), TB, s, b.ns_max, w.degn, w.sl4, w.hdr);
-    tb = w.temp_bytes;
-    HIP_OK(rocprim::exclusive_scan(w.temp, tb, (const I4 *)w.sl4, w.off4, I4{0, 0, 0, 0}, (size_t)b.ns_max + 1, PlusI4(), s, false),
-           "slice scan");
-    GNN_LAUNCH("pb_tile_windows", pb_tile_windows, 2048, TB, s, w.tpad_off, w.sbase, w.degn, w.ptr, w.sv_in, w.sv_out,
-               (int)iter_records, w.t_desc, w.hdr);
-    // edge chunks
-    if (!fast) {
-        GNN_LAUNCH("pb_seg_keys", pb_seg_keys, gs(E), TB, s, src, E, (int)n, w.hkey, w.kscr);
-        tb = w.temp_bytes;
-        HIP_OK(rocprim::inclusive_scan(w.temp, tb, (const int *)w.kscr, w.rb, (size_t)E, CarryKey(), s, false), "key carry scan");
-        GNN_LAUNCH("pb_run_flags", pb_run_flags, gs(E + 1), TB, s, E, w.rb, w.mscan);
-    }                                     // (graph-local form: pb_graph_levels wrote the run flags)
-    tb = w.temp_bytes;
-    HIP_OK(rocprim::exclusive_scan(w.temp, tb, (const int *)w.mscan, w.c_scan, 0, (size_t)E + 1, rocprim::plus<int>(), s, false),
-           "run scan");
-    GNN_LAUNCH("pb_compact", pb_compact, gs(E + 1), TB, s, E, w.mscan, w.c_scan, w.rb, w.hdr, (int)H_NRUNS);
-    if (fast) {
-        GNN_LAUNCH("pb_marks_fast", pb_marks_fast, 1, 1024, s, w.rb, E, (int)chunk_segments, w.marks, b.m_max, w.hdr);
-    } else {
-        GNN_LAUNCH("pb_mark_flags", pb_mark_flags, gs(E + 1), TB, s, w.rb, E, (int)chunk_segments, w.mscan, w.hdr);
-        tb = w.temp_bytes;
-        HIP_OK(rocprim::exclusive_scan(w.temp, tb, (const int *)w.mscan, w.c_scan, 0, (size_t)E + 1, rocprim::plus<int>(), s,
-                                       false), "mark scan");
-        GNN_LAUNCH("pb_marks", pb_marks, gs(E + 1), TB, s, w.rb, E, w.mscan, w.c_scan, w.marks, b.m_max, w.hdr);
-    }
-    GNN_LAUNCH("pb_chunk_bounds", pb_chunk_bounds, 1, 1024, s, w.marks, (int)chunk_segments, w.parts, w.pscan, w.cb, b.c_max,
-               w.hdr);
-    GNN_LAUNCH("pb_chunk_windows", pb_chunk_windows, 2048, TB, s, w.cb, src, w.src_new, w.dst_new, (int)edge_records, w.c_desc,
-               w.hdr);
-    GNN_LAUNCH("pb_sizes", pb_sizes, 1, 64, s, w.hdr, w.off4, sizes_out, b.np_max, b.ns_max);
-    return 0;
+    const PlanForm f = choose_plan_form(seg_ptr != nullptr, max_graph_hits, max_graph_segments, G, read_plan_switches());
+    const PlanBuild c = {src, dst, hit_ptr, seg_ptr, n, E, G, tile_hits, iter_records, chunk_segments, edge_records,
+                         static_cast<hipStream_t>(stream), f, carve(align_ws(workspace), n, E, chunk_segments),
+                         bounds_of(n, E, chunk_segments)};
+    opt_in_large_lds();
+    int rc = f.local ? c.hit_order_graphs() : c.hit_order_global();
+    if (!rc) rc = c.units_and_tiles();
+    if (!rc) rc = c.new_ids();
+    if (!rc) rc = f.local ? c.lists_graphs() : c.lists_global();
+    if (!rc) rc = c.slices_and_windows();
+    if (!rc && !f.local) rc = c.segment_runs();          // (graph-local form: pb_graph_levels wrote the run flags)
+    if (!rc) rc = c.marks_and_chunks();
+    if (!rc) rc = c.sizes(sizes_out);
+    return rc;
 }
 
 int gnn_plan_build_sizes(const int32_t *src, const int32_t *dst, const int64_t *hit_ptr, int64_t n_hits,
@@ -2082,8 +2136,7 @@ int gnn_plan_build_fill(const float *X, int32_t F, const int32_t *src, const int
         !out->chunks || !out->sched_a || !out->sched_b || !out->perm)
         return fail(GNN_ERR_BADARG, "gnn_plan_build_fill: output array missing");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    char *wb = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const Ws w = carve(wb, n, E, chunk_segments);
+    const Ws w = carve(align_ws(workspace), n, E, chunk_segments);
     const int64_t n_pad = sz->n_pad, ns = sz->n_slices;
     const int nt = (int)sz->n_tiles, nc = (int)sz->n_chunks;
     HIP_OK(hipMemsetAsync(out->X, 0, (size_t)(n_pad + 1 + 64) * F * sizeof(float), s), "memset X");

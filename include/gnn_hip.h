@@ -381,7 +381,16 @@ int gnn_node_bwd(const float *H, int32_t ldh, const float *e, const float *Hnext
  * != 0: this batch is outside the builder's static bounds (degree >= 65536, > n/16 + 1024 tiles,
  * ...) - build the plan with plan.py / plan_device.py instead; bit 64 of status: a segment end
  * outside [0, n_hits) or a segment with exactly one negative end (malformed batch: the kernels
- * skip such segments, the caller must raise).  n_hits, n_segments > 0. */
+ * skip such segments, the caller must raise).  n_hits, n_segments > 0.
+ * The bits of sizes.status: */
+#define GNN_PLAN_ST_DEGREE    1   /* a hit with >= 65536 segments in one direction                    */
+#define GNN_PLAN_ST_TILES     2   /* more than n_hits / 16 + 1024 tiles                               */
+#define GNN_PLAN_ST_PAD       4   /* more padded hits than the workspace holds                        */
+#define GNN_PLAN_ST_CHUNKS    8   /* more marks or chunks than the workspace holds                    */
+#define GNN_PLAN_ST_SLICES    16  /* (kept for the slice bound; no kernel sets it today)              */
+#define GNN_PLAN_ST_I32       32  /* (kept for the int32 list bound; the caller checks the totals)    */
+#define GNN_PLAN_ST_ENDPOINT  64  /* malformed endpoints (above): the caller must raise              */
+#define GNN_PLAN_ST_FAST_MISS 128 /* gnn_plan_build_sizes_graphs: call gnn_plan_build_sizes instead   */
 typedef struct gnn_plan_sizes {
     int64_t n_pad, n_tiles, n_slices, n_chunks;
     int64_t in_total, out_total;        /* entries of in_nbr / out_nbr before their 64 zero entries */
@@ -421,6 +430,7 @@ int gnn_plan_build_sizes(const int32_t *src, const int32_t *dst, const int64_t *
  * outside its graph's hit range, ranges that do not tile [0, n_hits) / [0, n_segments), a level above 64, a hit with
  * more than 1024 segments in one direction, a graph of more than 16384 hits whose level / degree / id bits exceed a 32-bit sort key) - call gnn_plan_build_sizes instead.  max_graph_hits > 19456:
  * GNN_ERR_UNSUPPORTED. */
+#define GNN_PLAN_GRAPH_CAP_HITS 19456   /* the largest graph of the graph-local form: its tables live in 152 KB of LDS */
 int gnn_plan_build_sizes_graphs(const int32_t *src, const int32_t *dst, const int64_t *hit_ptr, const int64_t *seg_ptr,
                                 int64_t max_graph_hits, int64_t max_graph_segments, int64_t n_hits,
                                 int64_t n_segments, int64_t n_graphs, int32_t tile_hits, int32_t iter_records,

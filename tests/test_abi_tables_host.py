@@ -177,12 +177,17 @@ def test_names_and_constants_are_the_headers():
         defines.update((n, int(v)) for n, v in re.findall(r"#define\s+(GNN_\w+)\s+\(?(-?\d+)\)?\s", text))
         for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S):
             enumerators.update((n.strip(), i) for i, n in enumerate(body.split(",")))
-    assert len(classes) == 20 and len(defines) == 22 and len(enumerators) == 26
+    assert len(classes) == 20 and len(defines) == 31 and len(enumerators) == 26
     for c_name in classes:
         assert issubclass(getattr(_lib, _class_name(c_name)), ctypes.Structure), c_name
     for name, value in {**defines, **enumerators}.items():
         assert getattr(_lib, name) == value and type(getattr(_lib, name)) is int, name
     assert _lib.SELECT_HITS_MAX_LAYERS == defines["GNN_SELECT_HITS_MAX_LAYERS"]
+    # the plan builder's status bits and the graph-local hit cap: what plan_hip.py decodes and decides with
+    status = {k: v for k, v in defines.items() if k.startswith("GNN_PLAN_ST_")}
+    assert sorted(status.values()) == [1, 2, 4, 8, 16, 32, 64, 128]
+    assert (status["GNN_PLAN_ST_ENDPOINT"], status["GNN_PLAN_ST_FAST_MISS"]) == (64, 128)
+    assert defines["GNN_PLAN_GRAPH_CAP_HITS"] == 19456
     assert len(_lib.ROUTE_FIELDS) == enumerators["GNN_ROUTE_FIELDS"]
 
 
